@@ -20,6 +20,11 @@ the ranks: strong scaling).  Reads are sharded by query read; ha_ft_gen counts k
 all-reduce), ha_pt_gen builds the index hash-partitioned and all-gathers it (SURVEY.md 8e layout i: replicated index, no query-time
 traffic).  Barrier + max-over-ranks timing, value = all ranks' overlaps / max time.
 
+A plain run times only the pass `value` is quoted on (the delivered one; the resident one with `--no-boundary`): set-up, --warmup steps, --steps timed
+steps, the line.  `--full` adds everything else the line can carry: the resident pass next to the delivered one and the roofline / stage figures taken from
+it, the check of the delivered bytes against the reference's digests, the variants (repeat-rich twin, length jitter, rank proxy, configs[3] with 2 - 7 GPUs),
+and the CPU baseline.  `--dump-outputs DIR` writes what the delivered pass handed its caller in the last timed step as .npy files (OutputSample).
+
 Prints ONE JSON line on rank 0.
 """
 import argparse
@@ -80,7 +85,7 @@ def cpu_baseline(workload, mode="sample", threads=None):
     reference binary is absent."""
     from hifiasm_amd import synth
     from hifiasm_amd.workloads import GENOME_SEED, READ_SEED
-    cores = threads or os.cpu_count() or 1
+    cores = threads or host_cores()
     g, cov, L, err, rr, ont = WORKLOADS[workload]
     gs = g if mode == "full" else min(g, 50_000_000)
     n = max(1, int(round(gs * cov / L)))
@@ -116,6 +121,18 @@ def cpu_baseline(workload, mode="sample", threads=None):
         tot += o.lchain(r)[0].shape[0]
     dt = time.time() - t0
     return {"value": tot / dt, "unit": "overlaps/s", "cores": 1, "kind": "port", "sample": f"first {nn} reads of: " + sample}
+
+
+def host_cores():
+    """CPUs this process may run on: its affinity mask, capped by a cgroup v2 CPU quota when one is set (os.cpu_count() counts the whole host)"""
+    n = len(os.sched_getaffinity(0))
+    try:
+        quota, period = open("/sys/fs/cgroup/cpu.max").read().split()
+        if quota != "max":
+            n = min(n, max(1, int(quota) // int(period)))
+    except (OSError, ValueError):
+        pass
+    return n
 
 
 def profile_file(name):
@@ -172,8 +189,60 @@ def verify_delivery(eng, workload, rs, dranges):
     return res
 
 
-def run_workload(a, workload, steps, warmup, rank, local_rank, world, dist, torch, force_sharded, check_delivery=True):
-    """one workload on this rank's GPU: resident and boundary-inclusive timings, roofline of the dominant kernel; returns the line's dict on rank 0 (None elsewhere)"""
+class OutputSample:
+    """--dump-outputs: what the delivered pass handed its caller in the LAST timed step, taken batch by batch while that step runs (a batch's arena is
+    reused two batches later).  Every read's overlap and chained-hit counts (the arenas' offset arrays) and, for a fixed seeded sample of
+    reads, the arrays h_ec_lchain's caller receives (ol->list, fake cigars, cl->list).  All float64 (every value is a 32-bit integer; a fake-cigar word is
+    split into its two halves), read ids local to this rank, at most BUDGET bytes: the sampled reads are kept in read-id order while they fit."""
+    SAMPLE_READS, SEED, BUDGET = 64, 20240611, 64 << 20
+
+    def __init__(self, n_reads):
+        import numpy as np
+        self.rids = np.sort(np.random.default_rng(self.SEED).choice(n_reads, size=min(n_reads, self.SAMPLE_READS), replace=False))
+        self.counts = np.zeros((n_reads, 2))
+        self.reads = {}
+
+    def delivered(self, e, d, lo, hi):      # a delivered batch of reads [lo, hi) whose arena has landed (the engine's read ids of the batch start at d.rid_lo)
+        import numpy as np
+        from hifiasm_amd.api import _arr
+        n = int(d.n_reads)
+        self.counts[lo:lo + n, 0] = np.diff(_arr(d.ol_off, n + 1, np.uint64))
+        self.counts[lo:lo + n, 1] = np.diff(_arr(d.cl_off, n + 1, np.uint64))
+        for r in self.rids[(self.rids >= lo) & (self.rids < hi)]:
+            self.reads[int(r)] = e.delivered_read(d, int(d.rid_lo) + int(r) - lo)
+
+    def write(self, out_dir):
+        import numpy as np
+        os.makedirs(out_dir, exist_ok=True)
+        arrays = {"overlaps_per_read": self.counts[:, 0], "chained_hits_per_read": self.counts[:, 1]}
+        used = sum(v.nbytes for v in arrays.values())
+        rids, ol, fc, fc_n, cl = [], [], [], [], []
+        for r in sorted(self.reads):
+            o, f, fo, c = self.reads[r]
+            size = 8 * (o.size + 2 * f.size + o.shape[0] + c.size + 3)      # rows of ol, both fake-cigar halves, one cigar length per overlap, cl, the offsets
+            if used + size > self.BUDGET - 4096:
+                break
+            used += size
+            rids.append(r); ol.append(o); fc.append(f); fc_n.append(np.diff(fo.astype(np.int64))); cl.append(c)
+        n_ol = np.array([x.shape[0] for x in ol], dtype=np.int64); n_cl = np.array([x.shape[0] for x in cl], dtype=np.int64)
+        f = np.concatenate(fc) if fc else np.zeros(0, dtype=np.uint64)
+        arrays.update({
+            "sample_read_ids": np.array(rids, dtype=np.float64),
+            "sample_ol_offsets": np.concatenate([[0], np.cumsum(n_ol)]).astype(np.float64),          # ol rows of sampled read i: [off[i], off[i + 1])
+            "sample_ol": (np.concatenate(ol) if ol else np.zeros((0, 12), dtype=np.uint32)).astype(np.float64),
+            "sample_fake_cigar_offsets": np.concatenate([[0], np.cumsum(np.concatenate(fc_n) if fc_n else [])]).astype(np.float64),   # per ol row
+            "sample_fake_cigar": np.stack([f >> np.uint64(32), f & np.uint64(0xffffffff)], axis=1).astype(np.float64),                   # (high, low) 32 bits
+            "sample_cl_offsets": np.concatenate([[0], np.cumsum(n_cl)]).astype(np.float64),
+            "sample_cl": (np.concatenate(cl) if cl else np.zeros((0, 4), dtype=np.uint32)).astype(np.float64),
+        })
+        for k, v in arrays.items():
+            np.save(os.path.join(out_dir, k + ".npy"), np.asarray(v, dtype=np.float64))
+        return {"dir": out_dir, "files": len(arrays), "bytes": int(sum(np.asarray(v).nbytes for v in arrays.values())), "sampled_reads": len(rids)}
+
+
+def run_workload(a, workload, steps, warmup, rank, local_rank, world, dist, torch, force_sharded, check_delivery=True, dump_dir=None):
+    """one workload on this rank's GPU: the boundary-inclusive timing (or the resident one with --no-boundary); with --full both, roofline of the dominant kernel
+    and the check of the delivered bytes.  dump_dir: OutputSample of the last timed step written there.  Returns the line's dict on rank 0 (None elsewhere)"""
     from hifiasm_amd.api import Engine
     mode = "single GPU"
     rs, is_ont = make_reads(workload, rank=rank, world=world)
@@ -233,7 +302,7 @@ def run_workload(a, workload, steps, warmup, rank, local_rank, world, dist, torc
             views[len(views)] = eng.attach()
         return [eng] + [views[i] for i in range(k - 1)]
 
-    def step(deliver=False, n_ctx=1):
+    def step(deliver=False, n_ctx=1, capture=None):
         eng.ha_pt_gen()
         st = {k: v for k, v in eng.stage_times()}
         keys0 = {"overlaps": 0, "chained_hits": 0, "seed_hits": 0, "groups": 0, "minimizers": 0, "seq_groups": 0, "seq_group_hits": 0, "host_bytes": 0, "copy_ms": 0.0, "t_async": 0.0, "t_wait": 0.0, "code_bytes": 0, "delivered_hits": 0, "exceptions": 0}
@@ -250,10 +319,12 @@ def run_workload(a, workload, steps, warmup, rank, local_rank, world, dist, torc
                         slot = e.overlap_batch_async(lo, hi)      # compute of this batch; its copy runs under the next batch's kernels
                         t_b = time.time()
                         if prev is not None:                      # the consumer takes the previous batch now (its copy ran under this batch's kernels)
-                            d = e.deliver_wait(prev)
+                            d = e.deliver_wait(prev[0])
+                            if capture is not None:
+                                capture.delivered(e, d, prev[1], prev[2])
                             tot["host_bytes"] += int(d.bytes); tot["copy_ms"] += float(d.copy_ms); tot["code_bytes"] += int(d.n_codes); tot["delivered_hits"] += int(d.n_cl); tot["exceptions"] += int(d.n_exc)
                         tot["t_async"] += (t_b - t_a) * 1e3; tot["t_wait"] += (time.time() - t_b) * 1e3
-                        prev = slot
+                        prev = (slot, lo, hi)
                     else:
                         e.overlap_batch(lo, hi)
                     t = e.batch_totals()
@@ -263,7 +334,9 @@ def run_workload(a, workload, steps, warmup, rank, local_rank, world, dist, torc
                     for k, v in e.stage_times():
                         sst[k] = sst.get(k, 0.0) + v
                 if deliver and prev is not None:
-                    d = e.deliver_wait(prev)                      # every batch's results are in host memory
+                    d = e.deliver_wait(prev[0])                   # every batch's results are in host memory
+                    if capture is not None:
+                        capture.delivered(e, d, prev[1], prev[2])
                     tot["host_bytes"] += int(d.bytes); tot["copy_ms"] += float(d.copy_ms); tot["code_bytes"] += int(d.n_codes); tot["delivered_hits"] += int(d.n_cl); tot["exceptions"] += int(d.n_exc)
                 res[ci] = (tot, sst)
             except Exception as ex:      # noqa: BLE001 - raised again on the main thread
@@ -290,14 +363,14 @@ def run_workload(a, workload, steps, warmup, rank, local_rank, world, dist, torc
         if dist is not None:
             dist.barrier()
 
-    def timed(deliver, n_ctx=1):
+    def timed(deliver, n_ctx=1, capture=None):
         for _ in range(warmup):
             step(deliver, n_ctx)
         sync()
         t0 = time.time()
         ssum = {}
-        for _ in range(steps):
-            tot, st = step(deliver, n_ctx)
+        for i in range(steps):
+            tot, st = step(deliver, n_ctx, capture if i == steps - 1 else None)
             for k, v in st.items():
                 ssum[k] = ssum.get(k, 0.0) + v
         sync()
@@ -312,92 +385,101 @@ def run_workload(a, workload, steps, warmup, rank, local_rank, world, dist, torc
             ov = int(oo.item())
         return dt, ov, tot, ssum
 
-    dt, overlaps, tot, stage_sum = timed(False, max(1, a.contexts))
-    ms_per_step = dt / steps * 1e3
-    value = overlaps / (dt / steps)
+    # `value` is quoted on the delivered pass unless --no-boundary; the resident pass runs beside it only with --full (it feeds value_resident, stage_ms, roofline)
+    with_boundary = not a.no_boundary and hasattr(eng, "overlap_batch_async")
+    capture = OutputSample(n_reads) if dump_dir else None
+    value = ms_per_step = tot = stage_sum = None
+    if a.full or not with_boundary:
+        dt, overlaps, tot, stage_sum = timed(False, max(1, a.contexts))
+        ms_per_step = dt / steps * 1e3
+        value = overlaps / (dt / steps)
     boundary = None
-    if not a.no_boundary and hasattr(eng, "overlap_batch_async"):
-        bdt, bov, btot, bst = timed(True, max(1, a.boundary_contexts))
+    if with_boundary:
+        bdt, bov, btot, bst = timed(True, max(1, a.boundary_contexts), capture)
         boundary = {"q_assemble_ms_per_step": bst.get("q_assemble", 0.0) / steps, "stage_ms": {k: round(v / steps, 2) for k, v in bst.items()},"value": bov / (bdt / steps), "ms_per_step": bdt / steps * 1e3, "host_bytes_per_gpu_step": btot["host_bytes"], "wire_bytes_per_chained_hit": (btot["delivered_hits"] / 8 + btot["delivered_hits"] / 16 + btot["code_bytes"]) / max(1, btot["delivered_hits"]),
                     "copy_ms_per_step": btot["copy_ms"], "verbatim_hits_per_step": btot["exceptions"], "host_ms_in_async": btot["t_async"], "host_ms_in_wait": btot["t_wait"], "copy_gb_per_s": btot["host_bytes"] / max(1e-9, btot["copy_ms"] * 1e-3) / 1e9}
 
     # What `value` was quoted on must be what the reference computes: one more delivered pass (untimed), every read's digest computed on the HOST from the bytes
     # in the pinned arena (hao_delivery_digest: ol->list, fake cigars, cl->list decoded out of the wire format) against the digests of the real reference's run on
     # the same reads (tests/golden/<workload>.npz, made by tests/golden/make_golden_big.py from oracle/_ref/ref_harness; compared by value, nothing under oracle/ runs here)
-    if boundary is not None and world == 1 and not a.no_verify:
+    if boundary is not None and world == 1 and a.full and not a.no_verify:
         boundary["delivered_bytes_check"] = verify_delivery(eng, workload, rs, dranges)
+    dumped = capture.write(dump_dir) if capture is not None else None
 
     if rank == 0:
-        stage_ms = {k: v / steps for k, v in stage_sum.items()}
-        # roofline of the dominant kernel: live HIP-event time of its stage on the engine's stream
-        # which kernels carried the seed stage: the engine says (hao_batch_seed_path: the choice is made per batch in hao_batch.hpp - repeat-rich batches keep the table kernels)
-        try:
-            seed_path = eng.batch_seed_path()
-        except Exception:      # (the owner context ran no batch of its own: --contexts > 1)
-            seed_path = {"first_launch": "seed_bin_kernel" if os.environ.get("HAO_SEED_LDS") == "0" else "seed_lds_kernel", "left_to_tables": None}
-        seed_kernel = seed_path["first_launch"]
-        KERN_STAGE = {"sketch_unit_kernel": "sk_chunks", "chain_group_kernel": "q_chain", seed_kernel: "q_sort_bins"}
-        dom = max(KERN_STAGE, key=lambda k: stage_ms.get(KERN_STAGE[k], 0.0))
-        unit, bpu = ALG[dom]
-        units = rs.total_bases if unit == "base" else tot["seed_hits"]
-        n_batches = 1 if unit == "base" else len(ranges)
-        # per batch: all launches of the kernel in one batch count as one "launch" (chain_group_kernel runs once per size class,
-        # seed_bin_kernel once per bin-table size); the stage time brackets exactly those launches
-        k_ms = stage_ms.get(KERN_STAGE[dom], 0.0) / n_batches
-        alg_bytes = bpu * units / n_batches
-        achieved = alg_bytes / (k_ms * 1e-3) / 1e9 if k_ms > 0 else 0.0
-        roofline = {"bound": "hbm", "kernel": dom, "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                    "frac": round(achieved / HBM_PEAK_GBS, 5), "traffic": None,
-                    "kernel_ms": round(k_ms, 4), "alg_bytes_per_launch": int(alg_bytes)}
-        # the same figure for each of the three kernels that carry the step (the dominant one is `roofline` itself)
-        def kernel_line(kn):
-            u_, b_ = ALG[kn]; un_ = rs.total_bases if u_ == "base" else tot["seed_hits"]; nb_ = 1 if u_ == "base" else len(ranges)
-            ms_ = stage_ms.get(KERN_STAGE[kn], 0.0) / nb_
-            ach_ = b_ * un_ / nb_ / (ms_ * 1e-3) / 1e9 if ms_ > 0 else 0.0
-            return {"kernel": kn, "kernel_ms": round(ms_, 4), "launches_per_step": nb_, "alg_bytes_per_launch": int(b_ * un_ / nb_), "achieved": round(ach_, 2), "frac": round(ach_ / HBM_PEAK_GBS, 5)}
-        roofline["kernels"] = [kernel_line(kn) for kn in KERN_STAGE]
-        # what the device gives this byte mix (8 in + 16 out per seed hit) with no computation attached: profiles/r05/ubench_gather.txt (tools/ubench_gather.hip)
-        roofline["seed_stage"] = {"first_launch": seed_kernel, "reads_left_to_the_table_kernels_in_the_last_batch": seed_path["left_to_tables"]}
-        # what the device gives this byte mix (8 in + 16 out per seed hit) with no computation attached: constants measured by tools/ubench_gather.hip, NOT in this run
-        ub, ub_rel = profile_file("ubench_gather.json")
-        if ub:
+        stage_ms = roofline = sk = None
+        if stage_sum is not None:      # the resident pass ran (--full or --no-boundary): its stage times give the per-kernel figures
+            stage_ms = {k: v / steps for k, v in stage_sum.items()}
+            # roofline of the dominant kernel: live HIP-event time of its stage on the engine's stream
+            # which kernels carried the seed stage: the engine says (hao_batch_seed_path: the choice is made per batch in hao_batch.hpp - repeat-rich batches keep the table kernels)
             try:
-                roofline["seed_stage_ceilings"] = dict(json.load(open(ub)), source=ub_rel + " (tools/ubench_gather.hip, its own run)")
-            except Exception:
-                pass
-        prof, prof_rel = profile_file("pmc_traffic.json")
-        if prof and world == 1:      # PMC counters need their own rocprofv3 passes (tools/r06_final.sh pmc): not measurable inside this run
-            try:
-                pj = json.load(open(prof))
-                if pj.get("workload") == workload:
-                    tt = [v["hbm_bytes_per_launch"] * v["launches"] for k, v in pj["kernels"].items() if k.split("<")[0] == dom]
-                    if tt:
-                        roofline["traffic"] = int(sum(tt) / max(1, n_batches))      # (the profile's launches of one pass, spread over this run's launches per pass)
-                        roofline["traffic_source"] = prof_rel + ": separate rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this command, FETCH_SIZE x 2 (gfx950 correction of MI355X_MICROARCH.md; calibrated for wide coalesced reads only - for this kernel's 8-byte gathers the true value lies between traffic_lo and traffic)"
-                        lo_ = [v.get("hbm_bytes_per_launch_raw", v["hbm_bytes_per_launch"]) * v["launches"] for k, v in pj["kernels"].items() if k.split("<")[0] == dom]
-                        roofline["traffic_lo"] = int(sum(lo_) / max(1, n_batches))
-            except Exception:
-                pass
-        # the sketch kernel is instruction-issue bound, not HBM bound: report its VALU issue rate next to the HBM fraction (counters: profiles/r0N/sketch_alu.json)
-        sk_ms = stage_ms.get("sk_chunks", 0.0)
-        sk = {"kernel": "sketch_unit_kernel", "kernel_ms": round(sk_ms, 4), "bases": rs.total_bases,
-              "gbases_per_s": round(rs.total_bases / (sk_ms * 1e-3) / 1e9, 2) if sk_ms > 0 else None,
-              "hbm_frac": round(ALG["sketch_unit_kernel"][1] * rs.total_bases / (sk_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 5) if sk_ms > 0 else None}
-        alu, alu_rel = profile_file("sketch_alu.json")
-        if alu:
-            try:
-                aj = json.load(open(alu))
-                if not str(aj.get("kernel", "")).startswith("sketch_unit_kernel"):
-                    raise KeyError("counters of another kernel")
-                per_base = aj["valu_wave_insts_per_base"]
-                ach = per_base * rs.total_bases / (sk_ms * 1e-3) / 1e9 if sk_ms > 0 else 0.0
-                sk["roofline_alu"] = {"achieved_valu_issue": round(ach, 1), "peak": VALU_PEAK_GINST, "unit": "G wave-instructions/s",
-                                      "frac": round(ach / VALU_PEAK_GINST, 4), "valu_wave_insts_per_base": per_base,
-                                      "source": alu_rel + " (rocprofv3 --pmc SQ_INSTS_VALU ...) x this run's kernel time",
-                                      "peak_is": "the guide's 2 cycles per wave64 instruction; measured on the device (profiles/r06/ubench_valu.txt) only the simple two-operand "
-                                                 "integer instructions issue in 2.2 - 2.6 cycles, everything else in 4.0 - 4.5: this kernel's mix runs at its issue limit (DESIGN 8)"}
-            except Exception:
-                pass
+                seed_path = eng.batch_seed_path()
+            except Exception:      # (the owner context ran no batch of its own: --contexts > 1)
+                seed_path = {"first_launch": "seed_bin_kernel" if os.environ.get("HAO_SEED_LDS") == "0" else "seed_lds_kernel", "left_to_tables": None}
+            seed_kernel = seed_path["first_launch"]
+            KERN_STAGE = {"sketch_unit_kernel": "sk_chunks", "chain_group_kernel": "q_chain", seed_kernel: "q_sort_bins"}
+            dom = max(KERN_STAGE, key=lambda k: stage_ms.get(KERN_STAGE[k], 0.0))
+            unit, bpu = ALG[dom]
+            units = rs.total_bases if unit == "base" else tot["seed_hits"]
+            n_batches = 1 if unit == "base" else len(ranges)
+            # per batch: all launches of the kernel in one batch count as one "launch" (chain_group_kernel runs once per size class,
+            # seed_bin_kernel once per bin-table size); the stage time brackets exactly those launches
+            k_ms = stage_ms.get(KERN_STAGE[dom], 0.0) / n_batches
+            alg_bytes = bpu * units / n_batches
+            achieved = alg_bytes / (k_ms * 1e-3) / 1e9 if k_ms > 0 else 0.0
+            roofline = {"bound": "hbm", "kernel": dom, "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                        "frac": round(achieved / HBM_PEAK_GBS, 5), "traffic": None,
+                        "kernel_ms": round(k_ms, 4), "alg_bytes_per_launch": int(alg_bytes)}
+            # the same figure for each of the three kernels that carry the step (the dominant one is `roofline` itself)
+            def kernel_line(kn):
+                u_, b_ = ALG[kn]; un_ = rs.total_bases if u_ == "base" else tot["seed_hits"]; nb_ = 1 if u_ == "base" else len(ranges)
+                ms_ = stage_ms.get(KERN_STAGE[kn], 0.0) / nb_
+                ach_ = b_ * un_ / nb_ / (ms_ * 1e-3) / 1e9 if ms_ > 0 else 0.0
+                return {"kernel": kn, "kernel_ms": round(ms_, 4), "launches_per_step": nb_, "alg_bytes_per_launch": int(b_ * un_ / nb_), "achieved": round(ach_, 2), "frac": round(ach_ / HBM_PEAK_GBS, 5)}
+            roofline["kernels"] = [kernel_line(kn) for kn in KERN_STAGE]
+            # what the device gives this byte mix (8 in + 16 out per seed hit) with no computation attached: profiles/r05/ubench_gather.txt (tools/ubench_gather.hip)
+            roofline["seed_stage"] = {"first_launch": seed_kernel, "reads_left_to_the_table_kernels_in_the_last_batch": seed_path["left_to_tables"]}
+            # what the device gives this byte mix (8 in + 16 out per seed hit) with no computation attached: constants measured by tools/ubench_gather.hip, NOT in this run
+            ub, ub_rel = profile_file("ubench_gather.json")
+            if ub:
+                try:
+                    roofline["seed_stage_ceilings"] = dict(json.load(open(ub)), source=ub_rel + " (tools/ubench_gather.hip, its own run)")
+                except Exception:
+                    pass
+            prof, prof_rel = profile_file("pmc_traffic.json")
+            if prof and world == 1:      # PMC counters need their own rocprofv3 passes (tools/r06_final.sh pmc): not measurable inside this run
+                try:
+                    pj = json.load(open(prof))
+                    if pj.get("workload") == workload:
+                        tt = [v["hbm_bytes_per_launch"] * v["launches"] for k, v in pj["kernels"].items() if k.split("<")[0] == dom]
+                        if tt:
+                            roofline["traffic"] = int(sum(tt) / max(1, n_batches))      # (the profile's launches of one pass, spread over this run's launches per pass)
+                            roofline["traffic_source"] = prof_rel + ": separate rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this command, FETCH_SIZE x 2 (gfx950 correction of MI355X_MICROARCH.md; calibrated for wide coalesced reads only - for this kernel's 8-byte gathers the true value lies between traffic_lo and traffic)"
+                            lo_ = [v.get("hbm_bytes_per_launch_raw", v["hbm_bytes_per_launch"]) * v["launches"] for k, v in pj["kernels"].items() if k.split("<")[0] == dom]
+                            roofline["traffic_lo"] = int(sum(lo_) / max(1, n_batches))
+                except Exception:
+                    pass
+            # the sketch kernel is instruction-issue bound, not HBM bound: report its VALU issue rate next to the HBM fraction (counters: profiles/r0N/sketch_alu.json)
+            sk_ms = stage_ms.get("sk_chunks", 0.0)
+            sk = {"kernel": "sketch_unit_kernel", "kernel_ms": round(sk_ms, 4), "bases": rs.total_bases,
+                  "gbases_per_s": round(rs.total_bases / (sk_ms * 1e-3) / 1e9, 2) if sk_ms > 0 else None,
+                  "hbm_frac": round(ALG["sketch_unit_kernel"][1] * rs.total_bases / (sk_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 5) if sk_ms > 0 else None}
+            alu, alu_rel = profile_file("sketch_alu.json")
+            if alu:
+                try:
+                    aj = json.load(open(alu))
+                    if not str(aj.get("kernel", "")).startswith("sketch_unit_kernel"):
+                        raise KeyError("counters of another kernel")
+                    per_base = aj["valu_wave_insts_per_base"]
+                    ach = per_base * rs.total_bases / (sk_ms * 1e-3) / 1e9 if sk_ms > 0 else 0.0
+                    sk["roofline_alu"] = {"achieved_valu_issue": round(ach, 1), "peak": VALU_PEAK_GINST, "unit": "G wave-instructions/s",
+                                          "frac": round(ach / VALU_PEAK_GINST, 4), "valu_wave_insts_per_base": per_base,
+                                          "source": alu_rel + " (rocprofv3 --pmc SQ_INSTS_VALU ...) x this run's kernel time",
+                                          "peak_is": "the guide's 2 cycles per wave64 instruction; measured on the device (profiles/r06/ubench_valu.txt) only the simple two-operand "
+                                                     "integer instructions issue in 2.2 - 2.6 cycles, everything else in 4.0 - 4.5: this kernel's mix runs at its issue limit (DESIGN 8)"}
+                except Exception:
+                    pass
+        ctot = tot if tot is not None else btot      # (both passes count the same work: the resident pass's totals when it ran, else the delivered pass's)
         out = {
             "metric": "read-pair overlaps/sec (sum ol->length / (ha_pt_gen + all-reads h_ec_lchain pass))",
             "value": round(boundary["value"] if boundary else value, 1), "unit": "overlaps/s", "n_gpus": world, "steps": steps, "warmup": warmup,
@@ -405,7 +487,7 @@ def run_workload(a, workload, steps, warmup, rank, local_rank, world, dist, torc
             "vs_baseline": None, "dtype": "u64 hashing / int32 + f64 chain scores", "data": "synthetic",
             "value_is": ("boundary: every batch's ol->list, fake cigars and cl->list (wire format) delivered into pinned host memory inside the timed region" if boundary
                          else "resident: results stay in HBM (--no-boundary)"),
-            "value_resident": round(value, 1), "ms_per_step_resident": round(ms_per_step, 3),
+            "value_resident": round(value, 1) if value is not None else None, "ms_per_step_resident": round(ms_per_step, 3) if value is not None else None,
             "value_boundary": round(boundary["value"], 1) if boundary else None,
             "boundary": ({"ms_per_step": round(boundary["ms_per_step"], 3), "host_bytes_per_gpu_step": boundary["host_bytes_per_gpu_step"], "wire_bytes_per_chained_hit": round(boundary["wire_bytes_per_chained_hit"], 4),
                           "copy_ms_per_step": round(boundary["copy_ms_per_step"], 2), "verbatim_hits_per_step": boundary["verbatim_hits_per_step"], "copy_gb_per_s": round(boundary["copy_gb_per_s"], 2),
@@ -416,14 +498,15 @@ def run_workload(a, workload, steps, warmup, rank, local_rank, world, dist, torc
                           "what": "same step with every batch's ol->list, fake cigars and packed cl->list delivered into pinned host memory (per batch context: double-buffered, copy stream under the next batch's compute); contexts = batch contexts (hao_attach), one host thread each, that share the pass"}
                          if boundary else None),
             "config": {"workload": workload, "batch_contexts": max(1, a.contexts), "reads_per_gpu": n_reads, "bases_per_gpu": rs.total_bases, "batches_per_pass": len(ranges),
-                       "overlaps_per_gpu_step": tot["overlaps"], "seed_hits_per_gpu_step": tot["seed_hits"],
-                       "chained_hits_per_gpu_step": tot["chained_hits"], "groups_per_gpu_step": tot["groups"],
-                       "groups_on_sequential_path": tot["seq_groups"], "k": 51, "w": 51, "hpc": 1,
+                       "overlaps_per_gpu_step": ctot["overlaps"], "seed_hits_per_gpu_step": ctot["seed_hits"],
+                       "chained_hits_per_gpu_step": ctot["chained_hits"], "groups_per_gpu_step": ctot["groups"],
+                       "groups_on_sequential_path": ctot["seq_groups"], "k": 51, "w": 51, "hpc": 1,
                        "parallelism": mode, "ha_ft_gen_s": round(t_ft, 3), "hom_cov_ft": hom_ft},
             "roofline": roofline,
             "device_memory": (lambda fr_to: {"used_gb_at_end_of_run": round((fr_to[1] - fr_to[0]) / 1e9, 1), "total_gb": round(fr_to[1] / 1e9, 1)})(torch.cuda.mem_get_info(local_rank)),
             "sketch": sk,
-            "stage_ms": {k: round(v, 3) for k, v in stage_ms.items()},
+            "stage_ms": {k: round(v, 3) for k, v in stage_ms.items()} if stage_ms is not None else None,
+            "outputs": dumped,
         }
         for v_ in views.values():
             v_.close()
@@ -454,9 +537,16 @@ def main():
     ap.add_argument("--tail-split", action="store_true", help="delivered pass: cut the last batch into 1/2 + 1/4 + 1/4 (A/B: the default of rounds 4 - 5)")
     ap.add_argument("--no-verify", action="store_true", help="skip the untimed pass that digests the delivered bytes and compares them with the reference's digests")
     ap.add_argument("--verbose", action="store_true")
+    ap.add_argument("--full", action="store_true", help="besides the headline pass: the resident pass and its per-kernel figures, the delivered-bytes check, the variants and the CPU baseline "
+                                                        "(the options above that tune those legs act only with --full)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the delivered pass handed its caller in its last timed step to DIR/<name>.npy (float64, at most 64 MB; rank 0's reads)")
     a = ap.parse_args()
+    if a.dump_outputs and a.no_boundary:      # the resident pass's results reach a caller only through a whole-batch download that is not part of its timed step
+        ap.error("--dump-outputs needs the delivered pass: drop --no-boundary")
     if a.no_cpu_baseline:
         a.cpu_baseline = "none"
+    if not a.full:      # a plain run: set-up, warm-up, the timed steps of the headline pass, the line
+        a.no_variants, a.cpu_baseline = True, "none"
     if a.workload is None:
         a.workload = METRIC_WORKLOAD if a.gpus == 8 else "chr1_250M_hifi30x"
 
@@ -481,7 +571,7 @@ def main():
         dist.init_process_group("nccl", rank=rank, world_size=world, device_id=torch.device("cuda", local_rank))
     from hifiasm_amd.api import Engine
 
-    out = run_workload(a, a.workload, a.steps, a.warmup, rank, local_rank, world, dist, torch, force_sharded)
+    out = run_workload(a, a.workload, a.steps, a.warmup, rank, local_rank, world, dist, torch, force_sharded, dump_dir=a.dump_outputs if rank == 0 else None)
     # 2 <= N < 8 ranks: the line's headline stays the weak-scaled configs[2] (comparable across N); the configuration the metric is quoted on - configs[3], the
     # fixed 8 M-read set split over the N ranks - rides along as variants.metric_config (one untimed + one timed step, results left in HBM) when the memory plan of
     # a rank says it fits (hifiasm_amd/memplan.py); every rank takes part

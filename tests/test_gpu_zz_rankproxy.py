@@ -5,7 +5,7 @@ left open.  The fixture (tests/golden/human375M_hifi40x.npz) is the unmodified r
 thresholds, minimizer histogram, totals, and a digest of EVERY read's seed hits and (ol, fake cigars, cl).
 
 What the proxy does not contain: the exchanges of a sharded round (all-to-all-v of hashes and minimizers, one all-gather of the index) and target ids spread over 8 M
-reads.  No multi-GPU box was available in any round: no scaling curve has been measured; bench.py prints the same run as variants.rank_proxy_configs3 with a
+reads.  No multi-GPU box was available in any round: no scaling curve has been measured; bench.py --full prints the same run as variants.rank_proxy_configs3 with a
 PREDICTION of the 8-GPU rate next to it."""
 import os
 import time

@@ -3,7 +3,7 @@ tag=$1; shift; what="${*:-tests bench benchall}"; R=$GRAFT_REPO_ROOT; O=$R/gpuru
 has() { case " $what " in *" $1 "*) return 0;; esac; return 1; }
 WLMAIN=${WLMAIN:-chr1_250M_hifi30x}
 if has tests; then t0=$(date +%s); timeout ${TEST_TIMEOUT:-1100} python -m pytest tests -q -m gpu --durations=12 -rxXfs > $O/pytest_gpu_last.log 2>&1; echo "pytest rc=$? $(( $(date +%s) - t0 )) s" >> $O/pytest_gpu_last.log; tail -22 $O/pytest_gpu_last.log; grep -h '^\[rank share\]\|^\[dropin configs1\]' $O/pytest_gpu_last.log | cut -c1-1200; fi
-if has bench; then timeout 900 python bench.py --cpu-baseline sample --steps 20 --warmup 5 > $O/bench_$WLMAIN.json 2> $O/bench.err; echo "bench rc=$?"; python - $O/bench_$WLMAIN.json <<'PY'
+if has bench; then timeout 900 python bench.py --full --cpu-baseline sample --steps 20 --warmup 5 > $O/bench_$WLMAIN.json 2> $O/bench.err; echo "bench rc=$?"; python - $O/bench_$WLMAIN.json <<'PY'
 import json,sys
 d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); v=(d.get('variants') or {}).get('repeat_rich') or {}
 print('value', d['value'], 'ms', d['ms_per_step'], 'resident', d['value_resident'], d['ms_per_step_resident'], 'roofline', {k:d['roofline'][k] for k in ('kernel','achieved','frac','kernel_ms')}, [ (k['kernel'],k['kernel_ms'],k['frac']) for k in d['roofline'].get('kernels',[])])
@@ -11,7 +11,7 @@ print('stage', d['stage_ms']); print('boundary', (d.get('boundary') or {}).get('
 print('rr', v.get('value'), v.get('ms_per_step'), v.get('value_resident'), v.get('ms_per_step_resident'), (v.get('boundary') or {}).get('delivered_bytes_check')); print('cpu', d.get('cpu_baseline'))
 PY
 fi
-if has benchall; then for wl in bacterial5M_hifi30x bacterial5M_hifi30x_repeat ont5M_30x; do timeout 300 python bench.py --workload $wl --cpu-baseline none --no-variants > $O/bench_$wl.json 2>> $O/bench.err; python - $O/bench_$wl.json $wl <<'PY'
+if has benchall; then for wl in bacterial5M_hifi30x bacterial5M_hifi30x_repeat ont5M_30x; do timeout 300 python bench.py --full --workload $wl --cpu-baseline none --no-variants > $O/bench_$wl.json 2>> $O/bench.err; python - $O/bench_$wl.json $wl <<'PY'
 import json,sys
 d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
 print(sys.argv[2], 'ms', d['ms_per_step'], 'M ov/s', round(d['value']/1e6,2), 'resident', d.get('ms_per_step_resident'), round(d['value_resident']/1e6,2), 'ok', ((d.get('boundary') or {}).get('delivered_bytes_check') or {}).get('equal_to_reference'))
