@@ -50,7 +50,12 @@ class Delivery(C.Structure):
                 ("cl_exc", C.c_void_p), ("exact", C.c_void_p), ("copy_ms", C.c_double), ("qmz_pos", C.c_void_p), ("qmz_cnt", C.c_void_p)]
 
 
-DELIVER_OL, DELIVER_CL, DELIVER_EXACT = 1, 2, 4
+class EdDelivery(C.Structure):
+    """hao_ed_delivery_t: the window-alignment results of a batch delivered with HAO_DELIVER_ED (pointers into the same pinned arena as its Delivery)"""
+    _fields_ = [("n_pairs", C.c_uint64), ("window", C.c_uint32), ("thre", C.c_uint32), ("ed_off", C.c_void_p), ("err", C.c_void_p), ("pe", C.c_void_p)]
+
+
+DELIVER_OL, DELIVER_CL, DELIVER_EXACT, DELIVER_ED = 1, 2, 4, 8
 
 ABI_SYMBOLS = [
     "hao_opt_default", "hao_create", "hao_destroy", "hao_last_error", "hao_set_reads", "hao_ft_gen", "hao_pt_gen",
@@ -58,6 +63,7 @@ ABI_SYMBOLS = [
     "hao_fetch_sketch", "hao_overlap_batch", "hao_fetch_seed_hits", "hao_fetch_overlaps", "hao_batch_totals", "hao_batch_seed_path",
     "hao_stage_times", "hao_pass_default", "hao_overlap_batch_ex", "hao_set_shard", "hao_dist_unique_id", "hao_dist_init",
     "hao_loop_create", "hao_loop_destroy", "hao_dist_init_loopback", "hao_batch_digest", "hao_selftest_rocprim", "hao_selftest_big", "hao_selftest_sortbits", "hao_unpack_cigar", "hao_unpack_overlaps", "hao_overlap_batch_async", "hao_deliver_wait", "hao_unpack_hits", "hao_exact_check", "hao_fetch_exact", "hao_window_ed_batch", "hao_index_save", "hao_index_load", "hao_next_slot", "hao_attach", "hao_window_trace_batch", "hao_delivery_digest", "hao_ft_passes", "hao_ovlp_bin_read", "hao_ovlp_bin_write", "hao_window_ed_grid", "hao_fetch_ed_grid",
+    "hao_deliver_ed_config", "hao_deliver_ed", "hao_unpack_ed",
 ]
 
 
@@ -111,6 +117,9 @@ def lib():
         L.hao_unpack_cigar.argtypes = [C.POINTER(Delivery), C.c_uint64, vp, C.c_uint32]; L.hao_unpack_cigar.restype = C.c_uint32
         L.hao_unpack_overlaps.argtypes = [C.POINTER(Delivery), C.c_uint64, vp, C.c_uint64]; L.hao_unpack_overlaps.restype = C.c_uint64
         L.hao_delivery_digest.argtypes = [C.POINTER(Delivery), u64p, C.c_int]
+        L.hao_deliver_ed_config.argtypes = [vp, C.c_uint32, C.c_uint32]
+        L.hao_deliver_ed.argtypes = [vp, C.c_int, C.POINTER(EdDelivery)]
+        L.hao_unpack_ed.argtypes = [C.POINTER(EdDelivery), C.POINTER(Delivery), u32p, C.c_uint64, vp, vp, C.c_uint64]; L.hao_unpack_ed.restype = C.c_uint64
         L.hao_set_shard.argtypes = [vp, C.c_uint64, C.c_uint64, u32p]
         L.hao_dist_unique_id.argtypes = [u8p]
         L.hao_dist_init.argtypes = [vp, u8p, C.c_int, C.c_int]
@@ -151,7 +160,7 @@ class Engine:
     def attach(self):
         """hao_attach: a second batch context (own stream, scratch, results) over this engine's reads and index, for a second host thread"""
         v = Engine.__new__(Engine)
-        v.L = self.L; v.opt = self.opt; v.bw_thres = self.bw_thres; v.n_reads = self.n_reads; v.owner = self
+        v.L = self.L; v.opt = self.opt; v.bw_thres = self.bw_thres; v.n_reads = self.n_reads; v.owner = self; v.lengths = getattr(self, "lengths", None)
         h = C.c_void_p()
         self._ck(self.L.hao_attach(self.h, C.byref(h)), "hao_attach")
         v.h = h
@@ -192,6 +201,7 @@ class Engine:
                                       ns_off.ctypes.data_as(u64p) if ns_off is not None else None,
                                       ns.ctypes.data_as(u32p) if ns is not None else None), "hao_set_reads")
         self.n_reads = n
+        self.lengths = lengths.copy()      # (hao_unpack_ed rebuilds delivered window pairs from the lengths of all reads)
 
     def set_readset(self, rs):
         self.set_reads(rs.packed, rs.pk_off, rs.lengths, rs.n_mask(), rs.code_off)
@@ -300,13 +310,46 @@ class Engine:
                 p.bw_thres = bw_thres
         slot = C.c_int(-1)
         self._ck(self.L.hao_overlap_batch_async(self.h, lo, hi, C.byref(p) if p is not None else None, parts, C.byref(slot)), "hao_overlap_batch_async")
+        if not hasattr(self, "_ed_slot"):
+            self._ed_slot = {}
+        self._ed_slot[slot.value] = bool(parts & DELIVER_ED)
         return slot.value
 
     def deliver_wait(self, slot):
-        """the Delivery view of a slot (blocks until its copy has landed)"""
+        """the Delivery view of a slot (blocks until its copy has landed); with DELIVER_ED its window-alignment view rides along as ``d.ed``"""
         d = Delivery()
         self._ck(self.L.hao_deliver_wait(self.h, slot, C.byref(d)), "hao_deliver_wait")
+        d.ed = self.deliver_ed(slot) if getattr(self, "_ed_slot", {}).get(slot) else None
         return d
+
+    def deliver_ed_config(self, window=375, thre=15):
+        """the window grid of this context's DELIVER_ED batches (hao_deliver_ed_config: windows of `window` query bases, threshold thre)"""
+        self._ck(self.L.hao_deliver_ed_config(self.h, C.c_uint32(window), C.c_uint32(thre)), "hao_deliver_ed_config")
+
+    def deliver_ed(self, slot):
+        """the EdDelivery view of a waited-for slot whose batch asked for DELIVER_ED"""
+        e = EdDelivery()
+        self._ck(self.L.hao_deliver_ed(self.h, slot, C.byref(e)), "hao_deliver_ed")
+        return e
+
+    def delivered_ed(self, d, rid, lengths=None):
+        """(tasks uint32 [n,10], results int32 [n,2]) of read rid's window pairs out of a Delivery with DELIVER_ED - fetch_ed_grid's shapes and values for the read:
+        the tasks rebuilt from the delivered overlaps (hao_unpack_ed), the results widened (err INT32_MAX / pe -1 without an alignment)"""
+        e = getattr(d, "ed", None)
+        if e is None:
+            raise HaoError("delivered_ed: the batch was not delivered with DELIVER_ED")
+        if lengths is None:
+            lengths = getattr(self, "lengths", None)
+        if lengths is None:
+            raise HaoError("delivered_ed: the lengths of all reads are needed (pass lengths=)")
+        L = np.ascontiguousarray(lengths, dtype=np.uint32)
+        u32p = C.POINTER(C.c_uint32)
+        n = int(self.L.hao_unpack_ed(C.byref(e), C.byref(d), L.ctypes.data_as(u32p), rid, None, None, 0))
+        t = np.zeros((n, 10), dtype=np.uint32); r = np.zeros((n, 2), dtype=np.int32)
+        got = int(self.L.hao_unpack_ed(C.byref(e), C.byref(d), L.ctypes.data_as(u32p), rid, t.ctypes.data_as(C.c_void_p), r.ctypes.data_as(C.c_void_p), n))
+        if got != n:
+            raise HaoError(f"hao_unpack_ed: read {rid}: the pairs rebuilt from the delivered overlaps do not match the delivered count (lengths of another read set?)")
+        return t, r
 
     def delivered_read(self, d, rid):
         """(ol uint32 [n,12], fc uint64, fc_off uint64 [n+1], cl uint32 [m,4]) of read rid out of a Delivery view: what the h_ec_lchain shim hands to its caller"""

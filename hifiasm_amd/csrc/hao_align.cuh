@@ -349,26 +349,19 @@ __global__ void hao_al_key_kernel(const hao_ed_task_t *task, uint64_t n, uint64_
 __global__ void hao_al_iota_kernel(uint32_t *idx, uint64_t n) { const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; if (i < n) idx[i] = (uint32_t)i; }
 struct hao_al_flagged { const uint8_t *f; __host__ __device__ bool operator()(const uint32_t &i) const { return f[i] != 0; } };
 
+// The sweep of one wave's tile of 64 tasks (T: the lane's task, mine: the lane has a task of this launch's band word; codes: the wave's HAO_AL_CH bytes of LDS):
+// set-up of every lane's state, the tile's texts staged in LDS strip by strip, every lane stepped over its text.  hao_al_kernel and the delivery path's
+// kernel (hao_ed_deliver.cuh), which builds its tasks in the lane, share it.
 template<typename WT, int MODE, bool TRACE>
-__global__ __launch_bounds__(256) void hao_al_kernel(hao_ed_reads R, const hao_ed_task_t *task, const uint32_t *order, uint64_t n_order, uint64_t *path, uint64_t stride,
-		hao_ed_result_t *out_ed, hao_trace_result_t *out_tr, uint8_t *want_trace, uint16_t *cig, uint32_t cap)
+__device__ __forceinline__ void hao_al_tile_sweep(const hao_ed_reads &R, const hao_ed_task_t &T, bool mine, hao_al_state<WT> &S, uint8_t *codes, int lane, uint64_t *col, uint64_t stride)
 {
-	__shared__ uint8_t s_text[4][HAO_AL_CH];
-	const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
-	uint8_t *codes = s_text[wv];
-	const uint64_t slot = ((uint64_t)blockIdx.x * 4 + wv) * 64 + lane;
-	const bool have = slot < n_order;
-	const uint32_t ti = have ? order[slot] : 0;
-	hao_ed_task_t T; if (have) T = task[ti]; else { T.p_rid = T.p_pos = T.p_len = T.p_rev = T.t_rid = T.t_pos = T.t_len = T.t_rev = T.thre = T.abs_diag = 0; }
-	const bool mine = have && hao_al_mine<WT>(T.thre);
 	// the tile's text windows: a lane starts a segment when its text differs from its left neighbour's (neighbour fields through DPP moves)
 	hao_ed_task_t L = T;
 	L.t_rid = hao_wave_shr1(T.t_rid, 0xffffffffu); L.t_pos = hao_wave_shr1(T.t_pos, 0u); L.t_len = hao_wave_shr1(T.t_len, 0u); L.t_rev = hao_wave_shr1(T.t_rev, 0u); L.thre = hao_wave_shr1(T.thre, 0u);
 	const bool head = mine && (lane == 0 || !hao_al_same_text(T, L) || !hao_al_mine<WT>(L.thre));
 	const unsigned long long heads = __ballot(head), live = __ballot(mine);
-	hao_al_state<WT> S; S.alive = 0; S.dead = 0;
+	S.alive = 0; S.dead = 0;
 	if (mine) hao_al_init<WT, MODE>(S, R, T);
-	uint64_t *col = path + slot;      // (TRACE only)
 	// All segments of the tile sweep TOGETHER: the wave's HAO_AL_CH staged bytes are cut into one strip of `chs` columns per segment (one segment: all of
 	// them; 64 different texts: 16 columns each), every lane reads the column's character from its own segment's strip, and the wave refills the strips every chs
 	// columns - 16 base decodes per lane and refill whatever the number of segments, i.e. at worst (no two tasks share a text) what decoding one's own text costs.
@@ -409,6 +402,22 @@ __global__ __launch_bounds__(256) void hao_al_kernel(hao_ed_reads R, const hao_e
 			for (int32_t i = k0; i < k0 + chs && i < S.tn && !S.dead; ++i) hao_al_column<WT, MODE, TRACE>(S, strip[i - k0], i, col, stride);
 	}
 	(void)live;
+}
+
+template<typename WT, int MODE, bool TRACE>
+__global__ __launch_bounds__(256) void hao_al_kernel(hao_ed_reads R, const hao_ed_task_t *task, const uint32_t *order, uint64_t n_order, uint64_t *path, uint64_t stride,
+		hao_ed_result_t *out_ed, hao_trace_result_t *out_tr, uint8_t *want_trace, uint16_t *cig, uint32_t cap)
+{
+	__shared__ uint8_t s_text[4][HAO_AL_CH];
+	const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
+	const uint64_t slot = ((uint64_t)blockIdx.x * 4 + wv) * 64 + lane;
+	const bool have = slot < n_order;
+	const uint32_t ti = have ? order[slot] : 0;
+	hao_ed_task_t T; if (have) T = task[ti]; else { T.p_rid = T.p_pos = T.p_len = T.p_rev = T.t_rid = T.t_pos = T.t_len = T.t_rev = T.thre = T.abs_diag = 0; }
+	const bool mine = have && hao_al_mine<WT>(T.thre);
+	uint64_t *col = path + slot;      // (TRACE only)
+	hao_al_state<WT> S;
+	hao_al_tile_sweep<WT, MODE, TRACE>(R, T, mine, S, s_text[wv], lane, col, stride);
 	if (mine) {
 		hao_trace_result_t res;
 		const bool tr = hao_al_finish<WT, MODE, TRACE>(S, T, res, col, stride, TRACE ? cig + (uint64_t)ti * cap : nullptr, cap);

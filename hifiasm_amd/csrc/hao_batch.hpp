@@ -28,7 +28,8 @@ struct hao_ctx::Batch {
 		//      // ol->list in final order, per-read offsets, fake cigars
 		DevBuf<hao_chain_hdr_t> hdr; DevBuf<uint64_t> bits; DevBuf<uint32_t> rank, rank4; DevBuf<uint8_t> codes; DevBuf<hao_exc_t> exc; DevBuf<hao_qmz_t> qmz; DevBuf<uint16_t> qmz_pos, qmz_cnt; bool qmz16 = false;   // cl->list in the wire format (hao_deliver.cuh)
 		DevBuf<uint8_t> exact;                                                                        // exact-overlap flags of ol_out
-		void release() { fcw_off.release(); fcw.release(); ol_out.release(); ol_wire.release(); fin_off.release(); fc_out.release(); fc_out_off.release(); ch_off.release(); cl_off.release(); qm_off.release(); hdr.release(); bits.release(); rank.release(); rank4.release(); codes.release(); exc.release(); qmz.release(); qmz_pos.release(); qmz_cnt.release(); exact.release(); }
+		DevBuf<uint64_t> ed_off; DevBuf<uint8_t> ed_err; DevBuf<uint16_t> ed_pe;                      // HAO_DELIVER_ED: pairs per read, error byte and pattern end per pair (hao_ed_deliver.cuh)
+		void release() { ed_off.release(); ed_err.release(); ed_pe.release(); fcw_off.release(); fcw.release(); ol_out.release(); ol_wire.release(); fin_off.release(); fc_out.release(); fc_out_off.release(); ch_off.release(); cl_off.release(); qm_off.release(); hdr.release(); bits.release(); rank.release(); rank4.release(); codes.release(); exc.release(); qmz.release(); qmz_pos.release(); qmz_cnt.release(); exact.release(); }
 	} out[2];
 	int cur = 0;
 	OutSet &O() { return out[cur]; }
@@ -37,6 +38,8 @@ struct hao_ctx::Batch {
 	void arena_free(int x) { if (!arena[x]) return; if (arena_reg[x]) { (void)hipHostUnregister(arena[x]); (void)munmap(arena[x], arena_cap[x]); } else (void)hipHostFree(arena[x]); arena[x] = nullptr; arena_cap[x] = 0; arena_reg[x] = false; } hipStream_t copy_stream = nullptr; hipEvent_t ev_ready[2], ev_done[2], ev_cstart[2]; bool arena_bad[2] = { false, false }; int arena_retry[2] = { 0, 0 }, arena_node = -1;      /* arena_node: the NUMA node a probe found best (a box of round 6 reported the GPU on node 0 and copied at 30 GB/s into node 0, 56 into node 1) */ bool dl_ready = false, dl_pending[2] = { false, false };
 	uint32_t wgt_hi = 0xffffffffu, wgt_lo = 0xffffffffu, wgt_max = 0xffffffffu;      // (wgt_max: the largest k_mer_hit::cnt the pass's weight table can give)
 	double t_evsync = 0, t_enq = 0, t_alloc = 0, t_s1 = 0, t_s2 = 0, t_s3 = 0, t_run = 0, t_pre = 0; uint64_t t_n = 0, t_nrun = 0;      // host-side time spent in the delivery plumbing (HAO_DBG_PRINT=dl)
+	DevBuf<uint64_t> ed_nwin, ed_wbase, ed_wcnt, ed_woff; DevBuf<hao_ed_pair> ed_pairs; uint64_t ed_n = 0;      // HAO_DELIVER_ED scratch (compute stream only: not per output set); ed_n = pairs of the batch
+	hao_ed_delivery_t ed_dl[2] = {};      // the ED view of each slot (window 0: the slot's batch did not ask for HAO_DELIVER_ED)
 	hao_delivery_t dl[2]; uint64_t dl_seq = 0, n_exc = 0; uint32_t dl_parts = 0; bool exact_valid = false; std::vector<uint8_t> h_exact;
 	// host copies for fetch
 	std::vector<uint64_t> h_seg, h_fin_off, h_cl_off, h_fc_out_off; std::vector<hao_hit_t> h_hits, h_cl; std::vector<hao_ovlp_t> h_ol; std::vector<uint64_t> h_fc;
@@ -48,6 +51,7 @@ struct hao_ctx::Batch {
 		fc_base.release(); fcs.release(); fc_raw.release(); ol_fc_off.release(); cc_off.release(); cc.release(); fc_final.release(); fcf_off.release();
 		nch64.release(); g_tmp.release(); cls_cc.release(); cls_co.release(); glist.release(); g_cls.release(); slow.release(); ovf_list.release(); q_pos.release(); q_cnt.release(); s_n.release(); g_read.release(); wgt.release(); nch.release(); nout.release(); perm.release(); n_final.release(); fclen.release();
 		tm.release(); key_sc.release(); key_xs.release(); key_al.release(); key_tmp.release(); hits.release(); ohits.release(); cl.release(); f.release(); ii.release(); p.release(); t.release(); rec.release(); ol.release(); cd.release(); pk_cnt.release(); pk_ecnt.release(); pk_erank.release(); hq.release(); ohq.release(); hcode.release(); out[0].release(); out[1].release();
+		ed_nwin.release(); ed_wbase.release(); ed_wcnt.release(); ed_woff.release(); ed_pairs.release();
 		if (dl_ready) { (void)hipStreamSynchronize(copy_stream); (void)hipStreamDestroy(copy_stream); for (int x = 0; x < 2; ++x) { (void)hipEventDestroy(ev_ready[x]); (void)hipEventDestroy(ev_done[x]); (void)hipEventDestroy(ev_cstart[x]); arena_free(x); } dl_ready = false; }
 	}
 };
@@ -195,16 +199,52 @@ static int hao_ed_grid_run(hao_ctx *c, uint32_t wl, uint32_t thre, uint64_t *n_t
 	DevBuf<uint64_t> &cnt = c->al_path, off; HIP_TRY(cnt.reserve(W + 2)); HIP_TRY(off.reserve(W + 2));
 	HIP_TRY(hipMemsetAsync(cnt.p + W, 0, 8, c->stream));
 	const dim3 g_((unsigned)((n + 3) / 4)), b_(256);
-	hipLaunchKernelGGL((ed_grid_kernel<false>), g_, b_, 0, c->stream, B.O().ol_out.p, B.O().fin_off.p, c->d_len.p, B.lo, n, wl, thre, nword, wbase.p, cnt.p, (hao_ed_task_t*)nullptr); HAO_CHECK_LAUNCH();
+	hipLaunchKernelGGL((ed_grid_kernel<ED_GRID_COUNT>), g_, b_, 0, c->stream, B.O().ol_out.p, B.O().fin_off.p, c->d_len.p, B.lo, n, wl, thre, nword, wbase.p, cnt.p, (hao_ed_task_t*)nullptr, (hao_ed_pair*)nullptr); HAO_CHECK_LAUNCH();
 	if (int rc = hao_excl_scan_u64(c, cnt.p, off.p, W + 1)) return rc;
 	uint64_t T = 0; HIP_TRY(hipMemcpyAsync(&T, off.p + W, 8, hipMemcpyDeviceToHost, c->stream)); HIP_TRY(hipStreamSynchronize(c->stream));
 	if (T >= (1ULL << 32)) { hao_set_err(c, "hao_window_ed_grid: more than 2^32 pairs in one batch"); return HAO_EUNSUPP; }
 	HIP_TRY(c->al_task.reserve(T + 1));
-	if (T) { hipLaunchKernelGGL((ed_grid_kernel<true>), g_, b_, 0, c->stream, B.O().ol_out.p, B.O().fin_off.p, c->d_len.p, B.lo, n, wl, thre, nword, wbase.p, off.p, c->al_task.p); HAO_CHECK_LAUNCH(); }
+	if (T) { hipLaunchKernelGGL((ed_grid_kernel<ED_GRID_TASKS>), g_, b_, 0, c->stream, B.O().ol_out.p, B.O().fin_off.p, c->d_len.p, B.lo, n, wl, thre, nword, wbase.p, off.p, c->al_task.p, (hao_ed_pair*)nullptr); HAO_CHECK_LAUNCH(); }
 	HIP_TRY(hipStreamSynchronize(c->stream));      // (off is a local buffer)
 	off.release();
 	*n_tasks = T; c->al_grid_n = T;
 	return T ? hao_al_ed_resident(c, T, nword) : HAO_OK;
+}
+
+// HAO_DELIVER_ED (hao_overlap_batch_async): the grid pairs of the current batch's final ol->list (hao_deliver_ed_config's window and threshold) aligned on the
+// compute stream into the output set's compact records (hao_ed_deliver.cuh), so that they travel with the batch.  Scratch and results are the batch's own: the
+// blocking path's task / result buffers (c->al_*) are not touched.  Windows per read (from the host's copy of the lengths: no device round trip), pairs per
+// window (ed_grid_kernel), a scan, the per-read offsets, one peek at the total, the pair list (8 bytes a pair), one alignment launch.
+int hao_al_ed_deliver(hao_ctx *c, const hao_ovlp_t *ol, const hao_ed_pair *pairs, uint64_t n, uint32_t wl, uint32_t thre, uint8_t *err, uint16_t *pe);      // (hao_f3.hip)
+static int hao_ed_deliver_run(hao_ctx *c)
+{
+	hao_ctx::Batch &B = *c->batch; hao_ctx::Batch::OutSet &O = B.O(); const uint64_t n = B.n;
+	const uint32_t wl = c->ded_window, thre = c->ded_thre, nword = (2 * thre + 1 + 63) / 64;
+	B.ed_n = 0;
+	c->timer.mark("q_totals");      // (labels what ran since q_final - the totals' read-back and, with HAO_DELIVER_EXACT, the exact check - so that ed_grid / ed_align time the ED stage alone)
+	if (B.n_ol >= (1ULL << 32)) { hao_set_err(c, "HAO_DELIVER_ED: more than 2^32 overlaps in one batch"); return HAO_EUNSUPP; }
+	uint64_t W = 0;
+	for (uint64_t r = 0; r < n; ++r) W += (c->h_len[B.lo + r] + wl - 1) / wl;
+	HIP_TRY(B.ed_nwin.reserve(n + 2)); HIP_TRY(B.ed_wbase.reserve(n + 2)); HIP_TRY(B.ed_wcnt.reserve(W + 2)); HIP_TRY(B.ed_woff.reserve(W + 2)); HIP_TRY(O.ed_off.reserve(n + 2));
+	hipLaunchKernelGGL(ed_grid_nwin_kernel, dim3((unsigned)((n + 256) / 256)), dim3(256), 0, c->stream, c->d_len.p, B.lo, n, wl, B.ed_nwin.p); HAO_CHECK_LAUNCH();
+	if (int rc = hao_excl_scan_u64(c, B.ed_nwin.p, B.ed_wbase.p, n + 1)) return rc;
+	HIP_TRY(hipMemsetAsync(B.ed_wcnt.p + W, 0, 8, c->stream));
+	const dim3 g_((unsigned)((n + 3) / 4)), b_(256);
+	hipLaunchKernelGGL((ed_grid_kernel<ED_GRID_COUNT>), g_, b_, 0, c->stream, O.ol_out.p, O.fin_off.p, c->d_len.p, B.lo, n, wl, thre, nword, B.ed_wbase.p, B.ed_wcnt.p, (hao_ed_task_t*)nullptr, (hao_ed_pair*)nullptr); HAO_CHECK_LAUNCH();
+	if (int rc = hao_excl_scan_u64(c, B.ed_wcnt.p, B.ed_woff.p, W + 1)) return rc;
+	hipLaunchKernelGGL(ed_read_off_kernel, dim3((unsigned)((n + 256) / 256)), dim3(256), 0, c->stream, B.ed_wbase.p, B.ed_woff.p, n, O.ed_off.p); HAO_CHECK_LAUNCH();
+	// the total through mapped host memory, not a copy: a device-to-host copy would queue behind the previous batch's delivery on the DMA engine (hao_peek_kernel)
+	hipLaunchKernelGGL(hao_peek_kernel, dim3(1), dim3(64), 0, c->stream, (const unsigned long long*)(B.ed_woff.p + W), 1, c->peek_d + 32); HAO_CHECK_LAUNCH();
+	HIP_TRY(hipStreamSynchronize(c->stream));
+	const uint64_t T = c->peek_h[32];
+	if (T >= (1ULL << 32)) { hao_set_err(c, "HAO_DELIVER_ED: more than 2^32 pairs in one batch"); return HAO_EUNSUPP; }
+	HIP_TRY(B.ed_pairs.reserve(T + 1)); HIP_TRY(O.ed_err.reserve(T + 64)); HIP_TRY(O.ed_pe.reserve(T + 64));
+	if (T) { hipLaunchKernelGGL((ed_grid_kernel<ED_GRID_PAIRS>), g_, b_, 0, c->stream, O.ol_out.p, O.fin_off.p, c->d_len.p, B.lo, n, wl, thre, nword, B.ed_wbase.p, B.ed_woff.p, (hao_ed_task_t*)nullptr, B.ed_pairs.p); HAO_CHECK_LAUNCH(); }
+	c->timer.mark("ed_grid");
+	if (T) { if (int rc = hao_al_ed_deliver(c, O.ol_out.p, B.ed_pairs.p, T, wl, thre, O.ed_err.p, O.ed_pe.p)) return rc; }
+	c->timer.mark("ed_align");
+	B.ed_n = T;
+	return HAO_OK;
 }
 
 // Queue the copy of the current batch's results into the slot's pinned arena (copy stream, after everything on the compute stream so far).
@@ -212,7 +252,7 @@ static int hao_deliver_enqueue(hao_ctx *c)
 {
 	hao_ctx::Batch &B = *c->batch; const int s = B.cur; hao_ctx::Batch::OutSet &O = B.O(); const uint64_t n = B.n; const uint32_t parts = B.dl_parts;
 	auto al = [](size_t v) { return (v + 63) & ~(size_t)63; };
-	const bool ol = parts & HAO_DELIVER_OL, cl = parts & HAO_DELIVER_CL, ex = parts & HAO_DELIVER_EXACT;
+	const bool ol = parts & HAO_DELIVER_OL, cl = parts & HAO_DELIVER_CL, ex = parts & HAO_DELIVER_EXACT, ed = parts & HAO_DELIVER_ED;
 	size_t o_oloff = 0, o_ol = o_oloff + (ol ? al((n + 1) * 8) : 0), o_fcoff = o_ol + (ol ? al(B.n_ol * sizeof(hao_ovlp_wire_t)) : 0), o_fc = o_fcoff + (ol ? al((B.n_ol + 1) * 8) : 0);
 	size_t o_choff = o_fc + (ol ? al(B.n_fcw * 4) : 0), o_cloff = o_choff + (cl ? al((n + 1) * 8) : 0), o_qmoff = o_cloff + (cl ? al((n + 1) * 8) : 0), o_hdr = o_qmoff + (cl ? al((n + 1) * 8) : 0);
 	const bool q16 = O.qmz16;      // the minimizer tables in 2 + 2 bytes per minimizer (hao_qtab16_kernel) instead of 8
@@ -220,7 +260,8 @@ static int hao_deliver_enqueue(hao_ctx *c)
 	const uint64_t nw_ = cl ? (B.n_anchor + 63) / 64 : 0;      // 64-position words of the batch's bit stream (positions = seed hits)
 	const uint64_t nr4_ = cl ? nw_ / 4 + 1 : 0;      // rank directory entries on the wire: one per 256 positions
 	size_t o_rank = o_bits + (cl ? al(nw_ * 8) : 0), o_codes = o_rank + (cl ? al(nr4_ * 4) : 0), o_exc = o_codes + (cl ? al(B.n_codes) : 0);
-	size_t o_ex = o_exc + (cl ? al(B.n_exc * sizeof(hao_exc_t)) : 0), total = o_ex + (ex ? al(B.n_ol) : 0);
+	size_t o_ex = o_exc + (cl ? al(B.n_exc * sizeof(hao_exc_t)) : 0), o_edoff = o_ex + (ex ? al(B.n_ol) : 0);
+	size_t o_ederr = o_edoff + (ed ? al((n + 1) * 8) : 0), o_edpe = o_ederr + (ed ? al(B.ed_n) : 0), total = o_edpe + (ed ? al(B.ed_n * 2) : 0);      // (without HAO_DELIVER_ED: total = o_edoff, the layout of before)
 	if (total > B.arena_cap[s] || B.arena_bad[s]) {
 		const bool redo_ = B.arena_bad[s]; B.arena_bad[s] = false;      // (hao_deliver_wait saw this slot's last batch copied at less than 40 GB/s: the probe below tries every NUMA node)
 		B.arena_free(s);
@@ -305,6 +346,12 @@ static int hao_deliver_enqueue(hao_ctx *c)
 		d.bytes += 3 * (n + 1) * 8 + B.n_chains * sizeof(hao_chain_hdr_t) + B.n_mz * (q16 ? 4 : sizeof(hao_qmz_t)) + nw_ * 8 + nr4_ * 4 + B.n_codes + B.n_exc * sizeof(hao_exc_t);
 	}
 	if (ex && n) { HIP_TRY(cp(o_ex, O.exact.p, B.n_ol)); d.exact = a + o_ex; d.n_ol = B.n_ol; d.bytes += B.n_ol; }
+	if (ed && n) {
+		HIP_TRY(cp(o_edoff, O.ed_off.p, (n + 1) * 8)); HIP_TRY(cp(o_ederr, O.ed_err.p, B.ed_n)); HIP_TRY(cp(o_edpe, O.ed_pe.p, B.ed_n * 2));
+		hao_ed_delivery_t &e = B.ed_dl[s];
+		e.n_pairs = B.ed_n; e.ed_off = (const uint64_t*)(a + o_edoff); e.err = a + o_ederr; e.pe = (const uint16_t*)(a + o_edpe);
+		d.bytes += (n + 1) * 8 + B.ed_n * 3;
+	}
 	HIP_TRY(hipEventRecord(B.ev_done[s], B.copy_stream));
 	B.dl_pending[s] = true;
 	return HAO_OK;
@@ -339,7 +386,8 @@ static int hao_overlap_run(hao_ctx *c, uint64_t lo, uint64_t hi, const hao_pass_
 	}
 	// the output set about to be written may still be feeding a copy (its previous async batch): wait for that copy, never for the other slot's
 	if (B.dl_ready && B.dl_pending[B.cur]) { const double t0_ = hao_now(); HIP_TRY(hipEventSynchronize(B.ev_done[B.cur])); B.dl_pending[B.cur] = false; B.t_evsync += hao_now() - t0_; }
-	if (parts) { memset(&B.dl[B.cur], 0, sizeof(hao_delivery_t)); B.dl[B.cur].rid_lo = lo; B.dl[B.cur].n_reads = n; }
+	if (parts) { memset(&B.dl[B.cur], 0, sizeof(hao_delivery_t)); B.dl[B.cur].rid_lo = lo; B.dl[B.cur].n_reads = n;
+		memset(&B.ed_dl[B.cur], 0, sizeof(hao_ed_delivery_t)); if (parts & HAO_DELIVER_ED) { B.ed_dl[B.cur].window = c->ded_window; B.ed_dl[B.cur].thre = c->ded_thre; } }
 	if (n == 0) { B.n_anchor = B.n_groups = B.n_chains = B.n_cl = B.n_ol = B.n_fc = B.n_fcw = B.n_mz = 0; B.valid = true; return HAO_OK; }      // (an empty delivery: nothing to copy, the view stays zeroed)
 	// minimizer range of the batch (host knows the per-read offsets? keep a host copy once)
 	if (c->h_ix_mz_off.size() != c->n_reads + 1) {
@@ -699,6 +747,7 @@ static int hao_overlap_run(hao_ctx *c, uint64_t lo, uint64_t hi, const hao_pass_
 		fprintf(stderr, "  hits %llu  dp range %llu  spec-committed %llu  spec-failures %llu\n", slow_st[HAO_NCLS], slow_st[HAO_NCLS + 3], slow_st[HAO_NCLS + 1], slow_st[HAO_NCLS + 2]); }
 	B.valid = true;
 	if (parts & HAO_DELIVER_EXACT) { if (int rc = hao_exact_run(c)) return rc; }
+	if (parts & HAO_DELIVER_ED) { if (int rc = hao_ed_deliver_run(c)) return rc; }
 	if (parts) { const double t0_ = hao_now(); const int rc_ = hao_deliver_enqueue(c); B.t_enq += hao_now() - t0_; ++B.t_n; if (c->sw.dltime && (B.t_n & 15) == 0) fprintf(stderr, "[deliver] %llu batches: slot wait %.1f ms, enqueue %.1f ms (arena alloc %.1f ms)\n", (unsigned long long)B.t_n, B.t_evsync * 1e3, B.t_enq * 1e3, B.t_alloc * 1e3); return rc_; }
 	return HAO_OK;
 }

@@ -131,12 +131,18 @@ int hao_overlap_batch_async(hao_ctx *c, uint64_t rid_lo, uint64_t rid_hi, const 
 {
 	if (c) { if (int rc = hao_view_refresh(c)) return rc; }
 	if (!c || rid_lo > rid_hi || rid_hi > c->n_reads || !(parts & (HAO_DELIVER_OL | HAO_DELIVER_CL | HAO_DELIVER_EXACT))) return HAO_EINVAL;
+	if (parts & HAO_DELIVER_ED) {
+		if (hao_is_sharded(c)) { hao_set_err(c, "HAO_DELIVER_ED needs the bases of both reads: single-device mode only"); return HAO_EUNSUPP; }
+		if (!(parts & HAO_DELIVER_OL)) { hao_set_err(c, "HAO_DELIVER_ED needs HAO_DELIVER_OL: the decoder rebuilds the pairs from the delivered overlaps"); return HAO_EINVAL; }
+		if (!c->ded_window) { hao_set_err(c, "HAO_DELIVER_ED before hao_deliver_ed_config"); return HAO_EINVAL; }
+	}
 	hao_pass_t ps;
 	if (!pass) { if (int rc = hao_pass_default(c, &ps)) return rc; pass = &ps; }
 	HIP_TRY(hipSetDevice(c->device));
 	c->timer.begin(c->stream);
 	int rc = hao_overlap_run(c, rid_lo, rid_hi, *pass, parts, slot);
 	if (rc != HAO_OK) return rc;
+	if (parts & HAO_DELIVER_ED) HIP_TRY(hipStreamSynchronize(c->stream));      // (the ED stage's kernels run after the read-back of the totals: they too are done when the call returns)
 	c->timer.collect(c->stage_ms);      // (the batch's kernels are complete: hao_overlap_run ends with the read-back of its totals; only the copy is still running)
 	return HAO_OK;
 }
@@ -329,6 +335,50 @@ int hao_fetch_ed_grid(hao_ctx *c, hao_ed_task_t *tasks, hao_ed_result_t *res, ui
 	if (n && res) HIP_TRY(hipMemcpyAsync(res, c->al_res.p, n * sizeof(hao_ed_result_t), hipMemcpyDeviceToHost, c->stream));
 	HIP_TRY(hipStreamSynchronize(c->stream));
 	return HAO_OK;
+}
+
+int hao_deliver_ed_config(hao_ctx *c, uint32_t window, uint32_t thre)
+{
+	if (!c) return HAO_EINVAL;
+	if (window == 0 || thre > HAO_ED_MAX_THRE || (uint64_t)window + 2 * (uint64_t)thre >= 0xffff) { hao_set_err(c, "hao_deliver_ed_config: window length 0, threshold beyond the widest band, or window + 2 thre beyond 16 bits"); return HAO_EINVAL; }
+	c->ded_window = window; c->ded_thre = thre;
+	return HAO_OK;
+}
+
+int hao_deliver_ed(hao_ctx *c, int slot, hao_ed_delivery_t *out)
+{
+	if (!c || !out || slot < 0 || slot > 1 || !c->batch || !c->batch->dl_ready) return HAO_EINVAL;
+	hao_ctx::Batch &B = *c->batch;
+	if (!B.ed_dl[slot].window) { hao_set_err(c, "hao_deliver_ed: the slot's batch did not ask for HAO_DELIVER_ED"); return HAO_EINVAL; }
+	if (B.dl_pending[slot]) { hao_set_err(c, "hao_deliver_ed: hao_deliver_wait has not been called on the slot"); return HAO_EINVAL; }
+	*out = B.ed_dl[slot];
+	return HAO_OK;
+}
+
+// pure function of the two views of a delivered batch: read rid's grid pairs rebuilt from its delivered overlaps with the device's own hao_grid_pair, in the
+// device's order (grid window, then position in ol->list), and their results widened
+uint64_t hao_unpack_ed(const hao_ed_delivery_t *e, const hao_delivery_t *d, const uint32_t *len, uint64_t rid, hao_ed_task_t *tasks, hao_ed_result_t *res, uint64_t cap)
+{
+	if (!e || !d || !len || !e->window || !e->ed_off || rid < d->rid_lo || rid >= d->rid_lo + d->n_reads || !d->ol_off || !d->ol) return 0;
+	const uint64_t r = rid - d->rid_lo, p0 = e->ed_off[r], np = e->ed_off[r + 1] - p0;
+	if (np > cap || !tasks || !res) return np;
+	const uint32_t wl = e->window, thre = e->thre, nword = (2 * thre + 1 + 63) / 64, nw = (uint32_t)(((uint64_t)len[rid] + wl - 1) / wl);
+	const uint64_t o0 = d->ol_off[r], o1 = d->ol_off[r + 1];
+	uint64_t k = 0;
+	for (uint32_t w = 0; w < nw; ++w)
+		for (uint64_t i = o0; i < o1; ++i) {
+			const hao_ovlp_wire_t &x = d->ol[i]; hao_ovlp_t z;      // (hao_unpack_overlaps' record)
+			z.x_id = (uint32_t)rid; z.x_pos_s = x.x_pos_s; z.x_pos_e = x.x_pos_e; z.x_pos_strand = 0; z.y_id = x.y & 0x7fffffffu; z.y_pos_s = x.y_pos_s; z.y_pos_e = x.y_pos_e;
+			z.y_pos_strand = x.y >> 31; z.shared_seed = x.shared_seed; z.align_length = 0; z.non_homopolymer_errors = x.non_homopolymer_errors; z.fc_len = x.fc_len;
+			hao_ed_task_t t;
+			if (!hao_grid_pair(z, w, wl, thre, nword, len, &t)) continue;
+			if (k == np) return UINT64_MAX;
+			tasks[k] = t;
+			const uint8_t er = e->err[p0 + k]; const uint16_t pe = e->pe[p0 + k];
+			res[k].err = er == 0xff ? INT32_MAX : (int32_t)er; res[k].pe = pe == 0xffff ? -1 : (int32_t)pe;
+			++k;
+		}
+	return k == np ? np : UINT64_MAX;
 }
 
 int hao_fetch_exact(hao_ctx *c, uint64_t rid, const uint8_t **flags, uint64_t *n)

@@ -161,6 +161,7 @@ struct hao_ctx {
 	uint64_t al_grid_n = 0;      // pairs hao_window_ed_grid left in al_task / al_res
 	DevBuf<hao_ed_task_t> al_task; DevBuf<uint64_t> al_k1, al_k2, al_path; DevBuf<uint32_t> al_i1, al_order, al_sel; DevBuf<hao_ed_result_t> al_res; DevBuf<hao_trace_result_t> al_tres;
 	DevBuf<uint8_t> al_want; DevBuf<uint16_t> al_cig;
+	uint32_t ded_window = 0, ded_thre = 0;      // hao_deliver_ed_config: the grid of HAO_DELIVER_ED (window 0: not configured); per context, a view has its own
 	struct Batch;
 	Batch *batch = nullptr;
 	StageTimer timer; std::vector<std::pair<std::string, float> > stage_ms;

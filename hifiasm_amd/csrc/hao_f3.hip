@@ -1,11 +1,13 @@
 // libhao.so, second translation unit: f3, the window-alignment batches (hao_align.cuh) - 36 instantiations of hao_al_kernel (five modes, with and without
-// traceback, bands of one to four words) that the rest of the library does not depend on; compiled beside hao_capi.hip (hifiasm_amd/build.py).
+// traceback, bands of one to four words) and the four of the delivery path's kernel (hao_ed_deliver.cuh) that the rest of the library reaches through
+// hao_al_ed_resident / hao_al_ed_deliver only; compiled beside hao_capi.hip (hifiasm_amd/build.py).
 #include <algorithm>
 #include <cmath>
 #include <cstring>
 #include "hao_ctx.hpp"
 #include "hao_comm.hpp"
 #include "hao_align.cuh"
+#include "hao_ed_deliver.cuh"
 
 // ---- f3 (hao_align.cuh): host side of the window-alignment batches ----
 // tasks -> device, and their order by text window (hao_align.cuh: a wave takes 64 neighbours of that order, which mostly share one text)
@@ -72,6 +74,20 @@ int hao_al_ed_resident(hao_ctx *c, uint64_t n, uint32_t nword)
 	else if (nword == 2) hipLaunchKernelGGL((hao_al_kernel<hao_u128, HAO_AL_ED, false>), g_, b_, 0, c->stream, R, dt, order, n, (uint64_t*)nullptr, (uint64_t)0, dr, (hao_trace_result_t*)nullptr, (uint8_t*)nullptr, (uint16_t*)nullptr, 0u);
 	else if (nword == 3) hipLaunchKernelGGL((hao_al_kernel<hao_wide<3>, HAO_AL_ED, false>), g_, b_, 0, c->stream, R, dt, order, n, (uint64_t*)nullptr, (uint64_t)0, dr, (hao_trace_result_t*)nullptr, (uint8_t*)nullptr, (uint16_t*)nullptr, 0u);
 	else hipLaunchKernelGGL((hao_al_kernel<hao_wide<4>, HAO_AL_ED, false>), g_, b_, 0, c->stream, R, dt, order, n, (uint64_t*)nullptr, (uint64_t)0, dr, (hao_trace_result_t*)nullptr, (uint8_t*)nullptr, (uint16_t*)nullptr, 0u);
+	HAO_CHECK_LAUNCH();
+	return HAO_OK;
+}
+
+// the delivery path's alignment (HAO_DELIVER_ED, hao_batch.hpp): n pairs (overlap, window) of the batch's ol->list in text order -> err[n] / pe[n] of the output set
+int hao_al_ed_deliver(hao_ctx *c, const hao_ovlp_t *ol, const hao_ed_pair *pairs, uint64_t n, uint32_t wl, uint32_t thre, uint8_t *err, uint16_t *pe)
+{
+	const hao_ed_reads R = hao_al_reads_of(c);
+	const dim3 g_((unsigned)((n + 255) / 256)), b_(256);
+	const uint32_t nword = hao_al_nword(thre);
+	if (nword == 1) hipLaunchKernelGGL((hao_ed_deliver_kernel<uint64_t>), g_, b_, 0, c->stream, R, ol, pairs, n, wl, thre, err, pe);
+	else if (nword == 2) hipLaunchKernelGGL((hao_ed_deliver_kernel<hao_u128>), g_, b_, 0, c->stream, R, ol, pairs, n, wl, thre, err, pe);
+	else if (nword == 3) hipLaunchKernelGGL((hao_ed_deliver_kernel<hao_wide<3> >), g_, b_, 0, c->stream, R, ol, pairs, n, wl, thre, err, pe);
+	else hipLaunchKernelGGL((hao_ed_deliver_kernel<hao_wide<4> >), g_, b_, 0, c->stream, R, ol, pairs, n, wl, thre, err, pe);
 	HAO_CHECK_LAUNCH();
 	return HAO_OK;
 }

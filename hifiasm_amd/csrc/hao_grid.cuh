@@ -6,6 +6,7 @@
 // want (hao_align.cuh: a wave takes 64 neighbours, which share their text), so nothing is uploaded, sorted or downloaded: two counting kernels, two scans, one fill.
 #pragma once
 #include "hao_common.cuh"
+#include "hao_grid_pair.cuh"      // (hao_grid_pair: one pair of the grid)
 
 __global__ void ed_grid_nwin_kernel(const uint32_t *len, uint64_t rid_lo, uint64_t n, uint32_t wl, uint64_t *nwin)
 {
@@ -14,28 +15,14 @@ __global__ void ed_grid_nwin_kernel(const uint32_t *len, uint64_t rid_lo, uint64
 	nwin[r] = r < n ? (len[rid_lo + r] + wl - 1) / wl : 0;
 }
 
-// the pair of overlap z and grid window w (helpers.ed_tasks_grid); false: the overlap does not cover the window, or the pair is empty / not expressible
-__device__ __forceinline__ bool hao_grid_pair(const hao_ovlp_t &z, uint32_t w, uint32_t wl, uint32_t thre, uint32_t nword, const uint32_t *len, hao_ed_task_t *t)
-{
-	const int64_t xs = z.x_pos_s, xe = z.x_pos_e, g0 = (int64_t)w * wl;
-	if (xs / wl > (int64_t)w || xe / wl < (int64_t)w) return false;
-	const int64_t ws = g0 > xs ? g0 : xs, we = g0 + wl - 1 < xe ? g0 + wl - 1 : xe, tn = we + 1 - ws, tl = len[z.y_id];
-	int64_t p0 = (int64_t)z.y_pos_s + (ws - xs) - (int64_t)thre, p1 = p0 + tn + 2 * (int64_t)thre, ad = 0;
-	if (p0 < 0) { ad = -p0 < 2 * (int64_t)thre ? -p0 : 2 * (int64_t)thre; p0 = 0; }
-	if (p1 > tl) p1 = tl;
-	if (p1 <= p0 || tn <= 0) return false;
-	// bands of more than one word: the final scan reads bit i of VP / VN for i < p_len - t_len + abs_diag, which must lie inside the band's words (hao_window_ed_batch refuses such a task)
-	if (nword > 1 && (p1 - p0) - tn + ad > 64 * (int64_t)nword) return false;
-	t->p_rid = z.y_id; t->p_pos = (uint32_t)p0; t->p_len = (uint32_t)(p1 - p0); t->p_rev = z.y_pos_strand;
-	t->t_rid = z.x_id; t->t_pos = (uint32_t)ws; t->t_len = (uint32_t)tn; t->t_rev = 0; t->thre = thre; t->abs_diag = (uint32_t)ad;
-	return true;
-}
-
-// one wave per read of the batch, a lane per grid window (64 at a time); FILL = false: pairs per window -> cnt[wbase[r] + w]; FILL = true: the pairs themselves at off[wbase[r] + w] ..
-template<bool FILL>
+// one wave per read of the batch, a lane per grid window (64 at a time); OUT = ED_GRID_COUNT: pairs per window -> cnt[wbase[r] + w]; ED_GRID_TASKS: the pairs themselves at
+// off[wbase[r] + w] ..; ED_GRID_PAIRS: the same places as (overlap, window) (the delivery path, HAO_DELIVER_ED: its alignment kernel rebuilds the tasks in the lane)
+enum { ED_GRID_COUNT = 0, ED_GRID_TASKS = 1, ED_GRID_PAIRS = 2 };
+template<int OUT>
 __global__ __launch_bounds__(256) void ed_grid_kernel(const hao_ovlp_t *ol, const uint64_t *fin_off, const uint32_t *len, uint64_t rid_lo, uint64_t n, uint32_t wl, uint32_t thre, uint32_t nword,
-		const uint64_t *wbase, uint64_t *cnt_or_off, hao_ed_task_t *tasks)
+		const uint64_t *wbase, uint64_t *cnt_or_off, hao_ed_task_t *tasks, hao_ed_pair *pairs)
 {
+	constexpr bool FILL = OUT != ED_GRID_COUNT;
 	const uint64_t r = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
 	if (r >= n) return;
 	const int lane = hao_lane();
@@ -45,9 +32,17 @@ __global__ __launch_bounds__(256) void ed_grid_kernel(const hao_ovlp_t *ol, cons
 		for (uint64_t i = o0; i < o1; ++i) {
 			hao_ed_task_t t;
 			if (!hao_grid_pair(ol[i], w, wl, thre, nword, len, &t)) continue;
-			if (FILL) tasks[at + k] = t;
+			if (OUT == ED_GRID_TASKS) tasks[at + k] = t;
+			if (OUT == ED_GRID_PAIRS) { hao_ed_pair q; q.ol = (uint32_t)i; q.w = w; pairs[at + k] = q; }
 			++k;
 		}
 		if (!FILL) cnt_or_off[wb + w] = k;
 	}
+}
+
+// the delivery path's per-read pair offsets: pairs of read r start at woff[wbase[r]] (r = 0 .. n; woff = exclusive scan of the per-window counts)
+__global__ void ed_read_off_kernel(const uint64_t *wbase, const uint64_t *woff, uint64_t n, uint64_t *ed_off)
+{
+	const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+	if (r <= n) ed_off[r] = woff[wbase[r]];
 }

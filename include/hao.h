@@ -254,6 +254,33 @@ int hao_window_ed_batch(hao_ctx *c, const hao_ed_task_t *tasks, uint64_t n_tasks
 int hao_window_ed_grid(hao_ctx *c, uint32_t window, uint32_t thre, uint64_t *n_tasks);
 int hao_fetch_ed_grid(hao_ctx *c, hao_ed_task_t *tasks, hao_ed_result_t *res, uint64_t cap);
 
+/* f3 in the streaming pass: the window alignment delivered WITH each batch.  HAO_DELIVER_ED in the parts of hao_overlap_batch_async (with HAO_DELIVER_OL; after
+ * hao_deliver_ed_config on this context, else HAO_EINVAL; sharded mode: HAO_EUNSUPP) aligns, on the device and right after chaining, every grid pair of the batch -
+ * the pairs hao_window_ed_grid(window, thre) forms from the batch's final ol->list, in the same text order (query read, grid window, position in ol->list), with
+ * the same (err, pe) - and the results cross PCIe in the batch's arena: 3 bytes per pair (an error byte, 0xff = no alignment within thre, and a 16-bit pattern
+ * end, 0xffff = -1) plus the pairs' offsets per read.  Tasks do not travel: hao_unpack_ed rebuilds them from the delivered overlaps.  The blocking path's
+ * task / result scratch (hao_window_ed_grid / hao_fetch_ed_grid) is not touched; batches without HAO_DELIVER_ED keep their arena layout and byte count.
+ * Not covered: the fake-cigar shift of the window's target start (Correct.cpp:3897), traced modes, the sharded path.
+ *   hao_deliver_ed_config: the grid of this context's HAO_DELIVER_ED batches (an attached view has its own).  window == 0, thre > HAO_ED_MAX_THRE or
+ *                          window + 2 thre >= 65535 (pe travels in 16 bits): HAO_EINVAL.  Bands of two or more words leave out the pairs hao_window_ed_grid leaves out.
+ *   hao_deliver_ed:        the ED view of a slot whose batch asked for HAO_DELIVER_ED, valid after hao_deliver_wait on that slot; its pointers live in the slot's
+ *                          pinned arena, with the same lifetime as the hao_delivery_t's.  HAO_EINVAL for a slot without ED results or not yet waited for.
+ *   hao_unpack_ed:         read rid's pairs as hao_ed_task_t records rebuilt from the delivered overlaps (d: the same slot's hao_delivery_t; len: the lengths of
+ *                          ALL reads, as given to hao_set_reads) and their results widened to hao_ed_result_t (err INT32_MAX / pe -1 without an alignment).
+ *                          Returns the pair count; nothing is written when it exceeds cap (or tasks / res is NULL); 0 for a read outside the batch;
+ *                          UINT64_MAX when the rebuilt pairs do not match the delivered count (len is not the batch's).  A pure function of the two views. */
+#define HAO_DELIVER_ED 8u      /* window-alignment results of the batch's grid pairs (hao_deliver_ed_config, hao_deliver_ed, hao_unpack_ed) */
+typedef struct {
+	uint64_t n_pairs;           /* pairs of the batch */
+	uint32_t window, thre;      /* the grid the batch was aligned on (hao_deliver_ed_config at the time of the batch) */
+	const uint64_t *ed_off;     /* [n_reads + 1]: pairs of read r = [ed_off[r], ed_off[r + 1]) */
+	const uint8_t *err;         /* [n_pairs]: edit distance, 0xff = no alignment within thre */
+	const uint16_t *pe;         /* [n_pairs]: end of the alignment on the pattern, 0xffff = -1 */
+} hao_ed_delivery_t;
+int hao_deliver_ed_config(hao_ctx *c, uint32_t window, uint32_t thre);
+int hao_deliver_ed(hao_ctx *c, int slot, hao_ed_delivery_t *out);
+uint64_t hao_unpack_ed(const hao_ed_delivery_t *e, const hao_delivery_t *d, const uint32_t *len, uint64_t rid, hao_ed_task_t *tasks, hao_ed_result_t *res, uint64_t cap);
+
 /* Second variant: global alignment inside the band WITH traceback - ed_band_cal_global_64_w_trace (Levenshtein_distance.h:3370-3442) on a
  * cleared bit_extz_t followed by gen_trace(ez, thre, 1) (:903-985), the call cal_exz_global / Correct.cpp:14537 make once a window's end points are fixed.
  * Same task records (abs_diag is ignored); both strings are consumed entirely, so |p_len - t_len| <= thre or there is no alignment.  Per task: err

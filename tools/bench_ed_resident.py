@@ -1,5 +1,10 @@
 """f3 end to end on the device (hao_window_ed_grid): pairs/s INCLUDING task generation on BASELINE configs[1] (10 000 reads of 15 kb) - every overlap of every read of
-one all-reads batch on the reference's window grid (WINDOW = 375), one threshold per call.  Prints one JSON line.  usage: python tools/bench_ed_resident.py [thre] [reps]"""
+one all-reads batch on the reference's window grid (WINDOW = 375), one threshold per call.  Prints one JSON line.  usage: python tools/bench_ed_resident.py [thre] [reps]
+
+--deliver: the same alignment in the streaming pass (HAO_DELIVER_ED): passes of hao_overlap_batch_async batches (both slots in flight) with OL|CL and with OL|CL|ED,
+alternately; per batch the ED stage's device time (stage_times "ed_grid" + "ed_align"), its pairs/s and the arena bytes it adds; per pass the wall time of the
+delivered step.  usage: python tools/bench_ed_resident.py --deliver [--workload W] [--batch-reads N] [--max-batches K] [--thre T] [--reps R]"""
+import argparse
 import json
 import os
 import sys
@@ -29,5 +34,62 @@ def main():
     e.close()
 
 
+def deliver(a):
+    from hifiasm_amd import workloads
+    from hifiasm_amd.api import Engine, DELIVER_OL, DELIVER_CL, DELIVER_ED
+    hi_all = workloads.n_reads_of(a.workload)
+    rs = workloads.workload_reads(a.workload)
+    e = Engine(0); e.set_readset(rs); e.ha_ft_gen(); e.ha_pt_gen()
+    e.deliver_ed_config(375, a.thre)
+    br = a.batch_reads or (rs.n + 1) // 2
+    ranges = [(lo, min(hi_all, lo + br)) for lo in range(0, rs.n, br)][:a.max_batches]
+
+    def one_pass(parts):
+        per, pending, t0 = [], None, time.time()
+
+        def take(slot, k):
+            d = e.deliver_wait(slot)
+            per[k].update(bytes=int(d.bytes), pairs=int(d.ed.n_pairs) if d.ed is not None else 0)
+        for k, (lo, hi) in enumerate(ranges):
+            slot = e.overlap_batch_async(lo, hi, parts=parts)
+            st = {}
+            for nm, ms in e.stage_times():
+                st[nm] = st.get(nm, 0.0) + ms
+            per.append(dict(reads=hi - lo, ed_grid_ms=st.get("ed_grid", 0.0), ed_align_ms=st.get("ed_align", 0.0), kernels_ms=sum(st.values())))
+            if pending is not None:
+                take(*pending)
+            pending = (slot, k)
+        take(*pending)
+        return (time.time() - t0) * 1e3, per
+
+    one_pass(DELIVER_OL | DELIVER_CL | DELIVER_ED); one_pass(DELIVER_OL | DELIVER_CL)      # warm-up (allocations, arenas)
+    walls = {"ol_cl": [], "ol_cl_ed": []}; last = {}
+    for _ in range(a.reps):
+        for key, parts in (("ol_cl", DELIVER_OL | DELIVER_CL), ("ol_cl_ed", DELIVER_OL | DELIVER_CL | DELIVER_ED)):
+            w, per = one_pass(parts); walls[key].append(round(w, 2)); last[key] = per
+    batches = []
+    for b0, b1 in zip(last["ol_cl"], last["ol_cl_ed"]):
+        ed_ms = b1["ed_grid_ms"] + b1["ed_align_ms"]
+        batches.append(dict(reads=b1["reads"], pairs=b1["pairs"], ed_grid_ms=round(b1["ed_grid_ms"], 3), ed_align_ms=round(b1["ed_align_ms"], 3), ed_ms=round(ed_ms, 3),
+                            pairs_per_s_ed_stage=round(b1["pairs"] / max(1e-9, ed_ms * 1e-3)), pairs_per_s_align=round(b1["pairs"] / max(1e-9, b1["ed_align_ms"] * 1e-3)),
+                            arena_bytes_ol_cl=b0["bytes"], arena_bytes_ol_cl_ed=b1["bytes"], extra_bytes=b1["bytes"] - b0["bytes"],
+                            kernels_ms_ol_cl=round(b0["kernels_ms"], 3), kernels_ms_ol_cl_ed=round(b1["kernels_ms"], 3)))
+    print(json.dumps({"workload": a.workload, "reads_indexed": int(rs.n), "window": 375, "thre": a.thre, "batches": batches,
+                      "delivered_step_ms_ol_cl": walls["ol_cl"], "delivered_step_ms_ol_cl_ed": walls["ol_cl_ed"],
+                      "delivered_step_ms_best": {k: min(v) for k, v in walls.items()},
+                      "what": "passes over the listed batches with both slots in flight: host wall time per pass with OL|CL and with OL|CL|ED (alternating), the ED stage's device time per batch (stage_times), the bytes it adds to the arena"}))
+    e.close()
+
+
 if __name__ == "__main__":
-    main()
+    if "--deliver" in sys.argv:
+        ap = argparse.ArgumentParser()
+        ap.add_argument("--deliver", action="store_true")
+        ap.add_argument("--workload", default="bacterial5M_hifi30x")
+        ap.add_argument("--batch-reads", type=int, default=0, help="reads per batch (0: two batches over the read set)")
+        ap.add_argument("--max-batches", type=int, default=1 << 30)
+        ap.add_argument("--thre", type=int, default=15)
+        ap.add_argument("--reps", type=int, default=3)
+        deliver(ap.parse_args())
+    else:
+        main()
