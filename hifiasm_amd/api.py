@@ -55,7 +55,12 @@ class EdDelivery(C.Structure):
     _fields_ = [("n_pairs", C.c_uint64), ("window", C.c_uint32), ("thre", C.c_uint32), ("ed_off", C.c_void_p), ("err", C.c_void_p), ("pe", C.c_void_p)]
 
 
-DELIVER_OL, DELIVER_CL, DELIVER_EXACT, DELIVER_ED = 1, 2, 4, 8
+class TraceDelivery(C.Structure):
+    """hao_trace_delivery_t: the traceback of a batch's aligned grid pairs delivered with HAO_DELIVER_TRACE (pointers into the same pinned arena as its Delivery)"""
+    _fields_ = [("n_traced", C.c_uint64), ("n_cigar", C.c_uint64), ("cg_off", C.c_void_p), ("ps", C.c_void_p), ("n_cig", C.c_void_p), ("cigar", C.c_void_p)]
+
+
+DELIVER_OL, DELIVER_CL, DELIVER_EXACT, DELIVER_ED, DELIVER_TRACE = 1, 2, 4, 8, 16
 
 ABI_SYMBOLS = [
     "hao_opt_default", "hao_create", "hao_destroy", "hao_last_error", "hao_set_reads", "hao_ft_gen", "hao_pt_gen",
@@ -64,6 +69,7 @@ ABI_SYMBOLS = [
     "hao_stage_times", "hao_pass_default", "hao_overlap_batch_ex", "hao_set_shard", "hao_dist_unique_id", "hao_dist_init",
     "hao_loop_create", "hao_loop_destroy", "hao_dist_init_loopback", "hao_batch_digest", "hao_selftest_rocprim", "hao_selftest_big", "hao_selftest_sortbits", "hao_unpack_cigar", "hao_unpack_overlaps", "hao_overlap_batch_async", "hao_deliver_wait", "hao_unpack_hits", "hao_exact_check", "hao_fetch_exact", "hao_window_ed_batch", "hao_index_save", "hao_index_load", "hao_next_slot", "hao_attach", "hao_window_trace_batch", "hao_delivery_digest", "hao_ft_passes", "hao_ovlp_bin_read", "hao_ovlp_bin_write", "hao_window_ed_grid", "hao_fetch_ed_grid",
     "hao_deliver_ed_config", "hao_deliver_ed", "hao_unpack_ed",
+    "hao_window_trace_grid", "hao_fetch_trace_grid", "hao_deliver_trace", "hao_unpack_trace",
 ]
 
 
@@ -120,6 +126,11 @@ def lib():
         L.hao_deliver_ed_config.argtypes = [vp, C.c_uint32, C.c_uint32]
         L.hao_deliver_ed.argtypes = [vp, C.c_int, C.POINTER(EdDelivery)]
         L.hao_unpack_ed.argtypes = [C.POINTER(EdDelivery), C.POINTER(Delivery), u32p, C.c_uint64, vp, vp, C.c_uint64]; L.hao_unpack_ed.restype = C.c_uint64
+        L.hao_window_trace_grid.argtypes = [vp, C.c_uint32, C.c_uint32, u64p]
+        L.hao_fetch_trace_grid.argtypes = [vp, vp, vp, u64p, vp, C.c_uint64, C.c_uint64]
+        L.hao_deliver_trace.argtypes = [vp, C.c_int, C.POINTER(TraceDelivery)]
+        L.hao_unpack_trace.argtypes = [C.POINTER(TraceDelivery), C.POINTER(EdDelivery), C.POINTER(Delivery), u32p, C.c_uint64, vp, vp, u64p, vp, C.c_uint64, C.c_uint64]
+        L.hao_unpack_trace.restype = C.c_uint64
         L.hao_set_shard.argtypes = [vp, C.c_uint64, C.c_uint64, u32p]
         L.hao_dist_unique_id.argtypes = [u8p]
         L.hao_dist_init.argtypes = [vp, u8p, C.c_int, C.c_int]
@@ -313,6 +324,9 @@ class Engine:
         if not hasattr(self, "_ed_slot"):
             self._ed_slot = {}
         self._ed_slot[slot.value] = bool(parts & DELIVER_ED)
+        if not hasattr(self, "_tr_slot"):
+            self._tr_slot = {}
+        self._tr_slot[slot.value] = bool(parts & DELIVER_TRACE)
         return slot.value
 
     def deliver_wait(self, slot):
@@ -320,6 +334,7 @@ class Engine:
         d = Delivery()
         self._ck(self.L.hao_deliver_wait(self.h, slot, C.byref(d)), "hao_deliver_wait")
         d.ed = self.deliver_ed(slot) if getattr(self, "_ed_slot", {}).get(slot) else None
+        d.tr = self.deliver_trace(slot) if getattr(self, "_tr_slot", {}).get(slot) else None
         return d
 
     def deliver_ed_config(self, window=375, thre=15):
@@ -350,6 +365,34 @@ class Engine:
         if got != n:
             raise HaoError(f"hao_unpack_ed: read {rid}: the pairs rebuilt from the delivered overlaps do not match the delivered count (lengths of another read set?)")
         return t, r
+
+    def deliver_trace(self, slot):
+        """the TraceDelivery view of a waited-for slot whose batch asked for DELIVER_TRACE"""
+        t = TraceDelivery()
+        self._ck(self.L.hao_deliver_trace(self.h, slot, C.byref(t)), "hao_deliver_trace")
+        return t
+
+    def delivered_trace(self, d, rid, lengths=None):
+        """(tasks uint32 [n,10], results int32 [n,6] (err, ps, pe, ts, te, cigar entries), cig_off uint64 [n+1], cigars uint16) of read rid's window pairs out of a
+        Delivery with DELIVER_TRACE - fetch_trace_grid's shapes and values for the read (hao_unpack_trace; cig_off counts from the read's first entry)"""
+        t, e = getattr(d, "tr", None), getattr(d, "ed", None)
+        if t is None or e is None:
+            raise HaoError("delivered_trace: the batch was not delivered with DELIVER_ED | DELIVER_TRACE")
+        if lengths is None:
+            lengths = getattr(self, "lengths", None)
+        if lengths is None:
+            raise HaoError("delivered_trace: the lengths of all reads are needed (pass lengths=)")
+        L = np.ascontiguousarray(lengths, dtype=np.uint32)
+        u32p, u64p = C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)
+        n = int(self.L.hao_unpack_trace(C.byref(t), C.byref(e), C.byref(d), L.ctypes.data_as(u32p), rid, None, None, None, None, 0, 0))
+        co = _arr(t.cg_off + 8 * (rid - d.rid_lo), 2, np.uint64) if n else np.zeros(2, np.uint64)
+        m = int(co[1] - co[0])
+        tk = np.zeros((n, 10), dtype=np.uint32); r = np.zeros((n, 6), dtype=np.int32); off = np.zeros(n + 1, dtype=np.uint64); cg = np.zeros(max(m, 1), dtype=np.uint16)
+        got = int(self.L.hao_unpack_trace(C.byref(t), C.byref(e), C.byref(d), L.ctypes.data_as(u32p), rid, tk.ctypes.data_as(C.c_void_p), r.ctypes.data_as(C.c_void_p),
+                                          off.ctypes.data_as(u64p), cg.ctypes.data_as(C.c_void_p), n, m))
+        if got != n:
+            raise HaoError(f"hao_unpack_trace: read {rid}: the pairs rebuilt from the delivered overlaps do not match the delivered counts (lengths of another read set?)")
+        return tk, r, off, cg[:m]
 
     def delivered_read(self, d, rid):
         """(ol uint32 [n,12], fc uint64, fc_off uint64 [n+1], cl uint32 [m,4]) of read rid out of a Delivery view: what the h_ec_lchain shim hands to its caller"""
@@ -416,6 +459,21 @@ class Engine:
         t = np.zeros((n, 10), dtype=np.uint32); r = np.zeros((n, 2), dtype=np.int32)
         self._ck(self.L.hao_fetch_ed_grid(self.h, t.ctypes.data_as(C.c_void_p), r.ctypes.data_as(C.c_void_p), C.c_uint64(n)), "hao_fetch_ed_grid")
         return t, r
+
+    def window_trace_grid(self, window=375, thre=15):
+        """hao_window_trace_grid: the last batch's grid pairs aligned with traceback where they align inside the semi-global domain;
+        returns (grid pairs, traced pairs, cigar entries, aligned but untraced pairs)"""
+        out = (C.c_uint64 * 4)()
+        self._ck(self.L.hao_window_trace_grid(self.h, C.c_uint32(window), C.c_uint32(thre), out), "hao_window_trace_grid")
+        return tuple(int(x) for x in out)
+
+    def fetch_trace_grid(self, n, n_cigar):
+        """(tasks uint32 [n,10], results int32 [n,6] (err, ps, pe, ts, te, cigar entries), cig_off uint64 [n+1], cigars uint16 [n_cigar]) of the last
+        hao_window_trace_grid: every grid pair, cigars in CSR form"""
+        t = np.zeros((n, 10), dtype=np.uint32); r = np.zeros((n, 6), dtype=np.int32); off = np.zeros(n + 1, dtype=np.uint64); cg = np.zeros(max(n_cigar, 1), dtype=np.uint16)
+        self._ck(self.L.hao_fetch_trace_grid(self.h, t.ctypes.data_as(C.c_void_p), r.ctypes.data_as(C.c_void_p), off.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                             cg.ctypes.data_as(C.c_void_p), C.c_uint64(n), C.c_uint64(n_cigar)), "hao_fetch_trace_grid")
+        return t, r, off, cg[:n_cigar]
 
     def fetch_exact(self, rid):
         """exact-overlap flags (uint8, aligned with h_ec_lchain(rid)[0]) of a read of the last batch"""

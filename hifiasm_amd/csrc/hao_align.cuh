@@ -203,10 +203,20 @@ template<typename WT> HAO_AL_FN void hao_al_keep(const hao_al_state<WT> &S, uint
 	HAO_AL_PUT(0, S.D0) HAO_AL_PUT(1, S.VP) HAO_AL_PUT(2, S.VN) HAO_AL_PUT(3, S.HP) HAO_AL_PUT(4, S.HN)
 #undef HAO_AL_PUT
 }
-
-// text column i (character tc) of the sweep.  KEEP: the column's vectors go to the scratch array.
-template<typename WT, int MODE, bool KEEP> HAO_AL_FN void hao_al_column(hao_al_state<WT> &S, uint32_t tc, int32_t i, uint64_t *col, uint64_t stride)
+// the three-word form (KW = 3, hao_trace_grid.cuh): D0, VP and VN of text column i in slot i + 1, and slot 0 holding VP / VN as they were before column 0.
+// HP and HN of a column follow from its D0 and the VP / VN of the column before (hao_al_column), so the walk derives them (hao_al_walk_back): 24 bytes per
+// band word and column instead of 40.
+template<typename WT> HAO_AL_FN void hao_al_keep3(const WT &D0, const WT &VP, const WT &VN, uint64_t *col, uint64_t stride, int32_t s)
 {
+	constexpr int NW = sizeof(WT) / 8;
+	uint64_t *w_ = col + 3 * NW * (uint64_t)s * stride;
+	for (int h_ = 0; h_ < NW; ++h_) { w_[(uint64_t)h_ * stride] = hao_al_word64(D0, h_); w_[((uint64_t)NW + h_) * stride] = hao_al_word64(VP, h_); w_[((uint64_t)2 * NW + h_) * stride] = hao_al_word64(VN, h_); }
+}
+
+// text column i (character tc) of the sweep.  KEEP: the column's vectors go to the scratch array, KW words per band word (5: hao_al_keep, 3: hao_al_keep3).
+template<typename WT, int MODE, bool KEEP, int KW = 5> HAO_AL_FN void hao_al_column(hao_al_state<WT> &S, uint32_t tc, int32_t i, uint64_t *col, uint64_t stride)
+{
+	if (KEEP && KW == 3 && i == 0) hao_al_keep3(S.D0, S.VP, S.VN, col, stride, 0);      // (slot 0: the vectors the first column starts from)
 	WT X = hao_al_eq_of(S, tc) | S.VN;
 	S.D0 = ((S.VP + (X & S.VP)) ^ S.VP) | X; S.HN = S.VP & S.D0; S.HP = S.VN | ~(S.VP | S.D0);
 	X = S.D0 >> 1; S.VN = X & S.HP; S.VP = S.HN | ~(X | S.HP);
@@ -221,7 +231,7 @@ template<typename WT, int MODE, bool KEEP> HAO_AL_FN void hao_al_column(hao_al_s
 		}
 	}
 	if (!last) { S.eq[0] >>= 1; S.eq[1] >>= 1; S.eq[2] >>= 1; S.eq[3] >>= 1; }
-	if (KEEP) hao_al_keep(S, col, stride, i);
+	if (KEEP) { if (KW == 5) hao_al_keep(S, col, stride, i); else hao_al_keep3(S.D0, S.VP, S.VN, col, stride, i + 1); }
 	if (!last) {
 		++S.i_bd;
 		if (S.i_bd < S.pn) hao_al_eq_or(S, hao_al_pstream_next(S.ps), S.top);
@@ -236,18 +246,25 @@ HAO_AL_FN void hao_al_push(uint16_t *cg, uint32_t cap, int32_t &n, int32_t op, i
 }
 // gen_trace (:903-985) over the kept columns: from text column i (exclusive), band bit sft, pattern offset poff and error cur back to the start; indels are
 // preferred over (mis)matches on ties (:924-936).  Emits push_trace's entries in walking order (op << 14 | len; 0 match, 1 mismatch, 2 more pattern,
-// 3 more text); returns the pattern offset where the walk ended, + 1.
-template<typename WT> HAO_AL_FN int32_t hao_al_walk_back(const uint64_t *col, uint64_t stride, int32_t thre, int32_t i, int32_t sft, int32_t poff, int32_t cur,
+// 3 more text); returns the pattern offset where the walk ended, + 1.  KW = 3: the three-word columns of hao_al_keep3, HP / HN of column c taken from its
+// D0 and column c - 1's VP / VN by hao_al_column's recurrence (HN = VP' & D0, HP = VN' | ~(VP' | D0), bit by bit) - the same bits, so the same walk.
+template<typename WT, int KW = 5> HAO_AL_FN int32_t hao_al_walk_back(const uint64_t *col, uint64_t stride, int32_t thre, int32_t i, int32_t sft, int32_t poff, int32_t cur,
 		uint16_t *cg, uint32_t cap, int32_t &ncg, int32_t &pdir, int32_t &pdn)
 {
 	constexpr int NW = sizeof(WT) / 8;
 	const int32_t low = thre << 1; int32_t d = 0;
 	while (i > 0 && cur > 0) {
-		const uint64_t *w_ = col + 5 * NW * (uint64_t)(i - 1) * stride;
-#define HAO_AL_BIT(k_, b_) ((int32_t)((w_[((uint64_t)(k_) * NW + ((b_) >> 6)) * stride] >> ((b_) & 63)) & 1ULL))      /* bit b_ of kept value k_ (D0, VP, VN, HP, HN) */
-		const int32_t D = cur - (HAO_AL_BIT(0, sft) ^ 1); int32_t mn = D; d = 0;
-		if (sft != low) { const int32_t H = cur + HAO_AL_BIT(4, sft) - HAO_AL_BIT(3, sft); if (H + 1 == cur && H <= mn) { mn = H; d = 3; } }
-		if (sft != 0) { const int32_t V = cur + HAO_AL_BIT(2, sft - 1) - HAO_AL_BIT(1, sft - 1); if (V + 1 == cur && V <= mn) { mn = V; d = 2; } }
+		const uint64_t *w_ = col + KW * NW * (uint64_t)(KW == 5 ? i - 1 : i) * stride;
+#define HAO_AL_BIT(p_, k_, b_) ((int32_t)((p_[((uint64_t)(k_) * NW + ((b_) >> 6)) * stride] >> ((b_) & 63)) & 1ULL))      /* bit b_ of kept value k_ (D0, VP, VN, HP, HN) */
+		const int32_t d0 = HAO_AL_BIT(w_, 0, sft);
+		const int32_t D = cur - (d0 ^ 1); int32_t mn = D; d = 0;
+		if (sft != low) {
+			int32_t hp, hn;
+			if (KW == 5) { hp = HAO_AL_BIT(w_, 3, sft); hn = HAO_AL_BIT(w_, 4, sft); }
+			else { const uint64_t *q_ = w_ - 3 * NW * stride; const int32_t vp = HAO_AL_BIT(q_, 1, sft), vn = HAO_AL_BIT(q_, 2, sft); hn = vp & d0; hp = vn | ((vp | d0) ^ 1); }
+			const int32_t H = cur + hn - hp; if (H + 1 == cur && H <= mn) { mn = H; d = 3; }
+		}
+		if (sft != 0) { const int32_t V = cur + HAO_AL_BIT(w_, 2, sft - 1) - HAO_AL_BIT(w_, 1, sft - 1); if (V + 1 == cur && V <= mn) { mn = V; d = 2; } }
 #undef HAO_AL_BIT
 		if (d == 0) { if (D != cur) d = 1; --i; --poff; }
 		else if (d == 2) { --sft; --poff; }
@@ -260,8 +277,8 @@ template<typename WT> HAO_AL_FN int32_t hao_al_walk_back(const uint64_t *col, ui
 }
 
 // after the last column: the final scans along the last text column, the result, and - TRACE - the traceback into cg.
-// Returns true iff the task has (TRACE: got) a cigar: the first, column-free sweep uses it to select the tasks of the second.
-template<typename WT, int MODE, bool TRACE> HAO_AL_FN bool hao_al_finish(hao_al_state<WT> &S, const hao_ed_task_t &T, hao_trace_result_t &res, const uint64_t *col, uint64_t stride,
+// Returns true iff the task has (TRACE: got) a cigar: the first, column-free sweep uses it to select the tasks of the second.  KW: hao_al_column's column form.
+template<typename WT, int MODE, bool TRACE, int KW = 5> HAO_AL_FN bool hao_al_finish(hao_al_state<WT> &S, const hao_ed_task_t &T, hao_trace_result_t &res, const uint64_t *col, uint64_t stride,
 		uint16_t *cg, uint32_t cap)
 {
 	const bool back = MODE == HAO_AL_EXT_BWD, ext = MODE == HAO_AL_EXT_FWD || MODE == HAO_AL_EXT_BWD;
@@ -287,7 +304,7 @@ template<typename WT, int MODE, bool TRACE> HAO_AL_FN bool hao_al_finish(hao_al_
 		if (S.dead || S.best > thre) return false;      // (an end found before the sweep was abandoned keeps its coordinates but gets no cigar, as in the reference)
 		if (TRACE) {
 			int32_t ncg = 0, pdir = -1, pdn = 0;
-			const int32_t poff = hao_al_walk_back<WT>(col, stride, thre, S.a_t + 1, thre + S.a_p - S.a_t, S.a_p, S.best, cg, cap, ncg, pdir, pdn);
+			const int32_t poff = hao_al_walk_back<WT, KW>(col, stride, thre, S.a_t + 1, thre + S.a_p - S.a_t, S.a_p, S.best, cg, cap, ncg, pdir, pdn);
 			if (poff > 0) { if (pdir == 2) pdn += poff; else { if (pdn > 0) hao_al_push(cg, cap, ncg, pdir, pdn); pdir = 2; pdn = poff; } }
 			if (pdn > 0) hao_al_push(cg, cap, ncg, pdir, pdn);
 			if (!back && (uint32_t)ncg <= cap) for (int32_t q = 0; q < ncg / 2; ++q) { const uint16_t x_ = cg[q]; cg[q] = cg[ncg - 1 - q]; cg[ncg - 1 - q] = x_; }
@@ -319,7 +336,7 @@ template<typename WT, int MODE, bool TRACE> HAO_AL_FN bool hao_al_finish(hao_al_
 	if (TRACE) {
 		const int32_t low = thre << 1, ptrim = MODE == HAO_AL_GLOBAL ? thre : S.adiag;
 		int32_t ncg = 0, pdir = -1, pdn = 0;
-		const int32_t poff = hao_al_walk_back<WT>(col, stride, thre, tn, (low + 1) - (tn + low - pe - ptrim), pe, ez, cg, cap, ncg, pdir, pdn);
+		const int32_t poff = hao_al_walk_back<WT, KW>(col, stride, thre, tn, (low + 1) - (tn + low - pe - ptrim), pe, ez, cg, cap, ncg, pdir, pdn);
 		if (MODE == HAO_AL_SEMI) res.ps = poff;
 		else if (poff > 0) { if (pdir == 2) pdn += poff; else { if (pdn > 0) hao_al_push(cg, cap, ncg, pdir, pdn); pdir = 2; pdn = poff; } }
 		if (pdn > 0) hao_al_push(cg, cap, ncg, pdir, pdn);
@@ -352,7 +369,7 @@ struct hao_al_flagged { const uint8_t *f; __host__ __device__ bool operator()(co
 // The sweep of one wave's tile of 64 tasks (T: the lane's task, mine: the lane has a task of this launch's band word; codes: the wave's HAO_AL_CH bytes of LDS):
 // set-up of every lane's state, the tile's texts staged in LDS strip by strip, every lane stepped over its text.  hao_al_kernel and the delivery path's
 // kernel (hao_ed_deliver.cuh), which builds its tasks in the lane, share it.
-template<typename WT, int MODE, bool TRACE>
+template<typename WT, int MODE, bool TRACE, int KW = 5>
 __device__ __forceinline__ void hao_al_tile_sweep(const hao_ed_reads &R, const hao_ed_task_t &T, bool mine, hao_al_state<WT> &S, uint8_t *codes, int lane, uint64_t *col, uint64_t stride)
 {
 	// the tile's text windows: a lane starts a segment when its text differs from its left neighbour's (neighbour fields through DPP moves)
@@ -399,7 +416,7 @@ __device__ __forceinline__ void hao_al_tile_sweep(const hao_ed_reads &R, const h
 			__builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup"); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
 		}
 		if (mine && S.alive && !S.dead)
-			for (int32_t i = k0; i < k0 + chs && i < S.tn && !S.dead; ++i) hao_al_column<WT, MODE, TRACE>(S, strip[i - k0], i, col, stride);
+			for (int32_t i = k0; i < k0 + chs && i < S.tn && !S.dead; ++i) hao_al_column<WT, MODE, TRACE, KW>(S, strip[i - k0], i, col, stride);
 	}
 	(void)live;
 }

@@ -29,7 +29,8 @@ struct hao_ctx::Batch {
 		DevBuf<hao_chain_hdr_t> hdr; DevBuf<uint64_t> bits; DevBuf<uint32_t> rank, rank4; DevBuf<uint8_t> codes; DevBuf<hao_exc_t> exc; DevBuf<hao_qmz_t> qmz; DevBuf<uint16_t> qmz_pos, qmz_cnt; bool qmz16 = false;   // cl->list in the wire format (hao_deliver.cuh)
 		DevBuf<uint8_t> exact;                                                                        // exact-overlap flags of ol_out
 		DevBuf<uint64_t> ed_off; DevBuf<uint8_t> ed_err; DevBuf<uint16_t> ed_pe;                      // HAO_DELIVER_ED: pairs per read, error byte and pattern end per pair (hao_ed_deliver.cuh)
-		void release() { ed_off.release(); ed_err.release(); ed_pe.release(); fcw_off.release(); fcw.release(); ol_out.release(); ol_wire.release(); fin_off.release(); fc_out.release(); fc_out_off.release(); ch_off.release(); cl_off.release(); qm_off.release(); hdr.release(); bits.release(); rank.release(); rank4.release(); codes.release(); exc.release(); qmz.release(); qmz_pos.release(); qmz_cnt.release(); exact.release(); }
+		DevBuf<uint64_t> tr_off; DevBuf<uint16_t> tr_ps, tr_ncig, tr_cig;                            // HAO_DELIVER_TRACE: cigar entries per read, ps and entry count per pair, the entries (hao_trace_grid.cuh)
+		void release() { tr_off.release(); tr_ps.release(); tr_ncig.release(); tr_cig.release(); ed_off.release(); ed_err.release(); ed_pe.release(); fcw_off.release(); fcw.release(); ol_out.release(); ol_wire.release(); fin_off.release(); fc_out.release(); fc_out_off.release(); ch_off.release(); cl_off.release(); qm_off.release(); hdr.release(); bits.release(); rank.release(); rank4.release(); codes.release(); exc.release(); qmz.release(); qmz_pos.release(); qmz_cnt.release(); exact.release(); }
 	} out[2];
 	int cur = 0;
 	OutSet &O() { return out[cur]; }
@@ -40,6 +41,7 @@ struct hao_ctx::Batch {
 	double t_evsync = 0, t_enq = 0, t_alloc = 0, t_s1 = 0, t_s2 = 0, t_s3 = 0, t_run = 0, t_pre = 0; uint64_t t_n = 0, t_nrun = 0;      // host-side time spent in the delivery plumbing (HAO_DBG_PRINT=dl)
 	DevBuf<uint64_t> ed_nwin, ed_wbase, ed_wcnt, ed_woff; DevBuf<hao_ed_pair> ed_pairs; uint64_t ed_n = 0;      // HAO_DELIVER_ED scratch (compute stream only: not per output set); ed_n = pairs of the batch
 	hao_ed_delivery_t ed_dl[2] = {};      // the ED view of each slot (window 0: the slot's batch did not ask for HAO_DELIVER_ED)
+	uint64_t tr_n = 0, tr_ncig = 0; hao_trace_delivery_t tr_dl[2] = {}; bool tr_on[2] = { false, false };      // HAO_DELIVER_TRACE: traced pairs and cigar entries of the batch; the view of each slot (tr_on: the slot's batch asked for it)
 	hao_delivery_t dl[2]; uint64_t dl_seq = 0, n_exc = 0; uint32_t dl_parts = 0; bool exact_valid = false; std::vector<uint8_t> h_exact;
 	// host copies for fetch
 	std::vector<uint64_t> h_seg, h_fin_off, h_cl_off, h_fc_out_off; std::vector<hao_hit_t> h_hits, h_cl; std::vector<hao_ovlp_t> h_ol; std::vector<uint64_t> h_fc;
@@ -247,12 +249,70 @@ static int hao_ed_deliver_run(hao_ctx *c)
 	return HAO_OK;
 }
 
+// f3 with traceback on the grid (hao_trace_grid.cuh, hao_f3.hip)
+int hao_al_trace_grid(hao_ctx *c, const hao_ovlp_t *ol, const hao_ed_pair *pairs, uint64_t n, uint32_t wl, uint32_t thre, const uint8_t *err,
+		uint16_t *ps16, uint16_t *ncig16, DevBuf<uint16_t> &cig, uint64_t *n_traced, uint64_t *n_cigar, uint64_t *n_untraced);
+int hao_al_trace_grid_off(hao_ctx *c, const uint64_t *at, uint64_t n, uint64_t n_traced, uint64_t *out);
+int hao_al_trace_grid_expand(hao_ctx *c, const hao_ovlp_t *ol, uint64_t n, hao_ed_task_t *tasks, hao_trace_result_t *res);
+
+// HAO_DELIVER_TRACE: the traced grid stage over the pairs and error bytes HAO_DELIVER_ED has just written (same grid, nothing swept twice), into the output
+// set's records: ps and entry count per pair, the compact cigars, and the entries' offsets per read (pairs of read r start at ed_off[r])
+static int hao_trace_deliver_run(hao_ctx *c)
+{
+	hao_ctx::Batch &B = *c->batch; hao_ctx::Batch::OutSet &O = B.O(); const uint64_t n = B.n, T = B.ed_n;
+	B.tr_n = 0; B.tr_ncig = 0;
+	HIP_TRY(O.tr_ps.reserve(T + 64)); HIP_TRY(O.tr_ncig.reserve(T + 64)); HIP_TRY(O.tr_off.reserve(n + 2));
+	uint64_t nt = 0, nc = 0, nu = 0;
+	if (int rc = hao_al_trace_grid(c, O.ol_out.p, B.ed_pairs.p, T, c->ded_window, c->ded_thre, O.ed_err.p, O.tr_ps.p, O.tr_ncig.p, O.tr_cig, &nt, &nc, &nu)) return rc;
+	if (int rc = hao_al_trace_grid_off(c, O.ed_off.p, n, nt, O.tr_off.p)) return rc;
+	B.tr_n = nt; B.tr_ncig = nc;
+	return HAO_OK;
+}
+
+// hao_window_trace_grid: the grid pairs of the current batch (hao_window_ed_grid's), their distance-only alignment (the delivery path's kernel, into the
+// context's own buffers) and the traced stage; everything stays resident for hao_fetch_trace_grid.  out: pairs, traced pairs, cigar entries, aligned but untraced pairs.
+static int hao_trace_grid_run(hao_ctx *c, uint32_t wl, uint32_t thre, uint64_t out[4])
+{
+	hao_ctx::Batch &B = *c->batch; hao_ctx::Batch::OutSet &O = B.O(); const uint64_t n = B.n;
+	c->tg_valid = false; out[0] = out[1] = out[2] = out[3] = 0;
+	if (hao_is_sharded(c)) { hao_set_err(c, "hao_window_trace_grid needs the bases of both reads: single-device mode only"); return HAO_EUNSUPP; }
+	if (wl == 0 || thre > HAO_ED_MAX_THRE || (uint64_t)wl + 2 * (uint64_t)thre >= 0xffff) { hao_set_err(c, "hao_window_trace_grid: window length 0, threshold beyond the widest band, or window + 2 thre beyond 16 bits"); return HAO_EINVAL; }
+	const uint32_t nword = (2 * thre + 1 + 63) / 64;
+	c->tg_wl = wl; c->tg_thre = thre; c->tg_n = c->tg_nsel = c->tg_ncig = c->tg_nuntr = 0;
+	if (n == 0 || B.n_ol == 0) { c->tg_valid = true; return HAO_OK; }
+	if (B.n_ol >= (1ULL << 32)) { hao_set_err(c, "hao_window_trace_grid: more than 2^32 overlaps in one batch"); return HAO_EUNSUPP; }
+	// the pair list as the delivery path forms it (B.ed_* scratch: compute stream only), into the context's own list
+	uint64_t W = 0;
+	for (uint64_t r = 0; r < n; ++r) W += (c->h_len[B.lo + r] + wl - 1) / wl;
+	HIP_TRY(B.ed_nwin.reserve(n + 2)); HIP_TRY(B.ed_wbase.reserve(n + 2)); HIP_TRY(B.ed_wcnt.reserve(W + 2)); HIP_TRY(B.ed_woff.reserve(W + 2));
+	hipLaunchKernelGGL(ed_grid_nwin_kernel, dim3((unsigned)((n + 256) / 256)), dim3(256), 0, c->stream, c->d_len.p, B.lo, n, wl, B.ed_nwin.p); HAO_CHECK_LAUNCH();
+	if (int rc = hao_excl_scan_u64(c, B.ed_nwin.p, B.ed_wbase.p, n + 1)) return rc;
+	HIP_TRY(hipMemsetAsync(B.ed_wcnt.p + W, 0, 8, c->stream));
+	const dim3 g_((unsigned)((n + 3) / 4)), b_(256);
+	hipLaunchKernelGGL((ed_grid_kernel<ED_GRID_COUNT>), g_, b_, 0, c->stream, O.ol_out.p, O.fin_off.p, c->d_len.p, B.lo, n, wl, thre, nword, B.ed_wbase.p, B.ed_wcnt.p, (hao_ed_task_t*)nullptr, (hao_ed_pair*)nullptr); HAO_CHECK_LAUNCH();
+	if (int rc = hao_excl_scan_u64(c, B.ed_wcnt.p, B.ed_woff.p, W + 1)) return rc;
+	hipLaunchKernelGGL(hao_peek_kernel, dim3(1), dim3(64), 0, c->stream, (const unsigned long long*)(B.ed_woff.p + W), 1, c->peek_d + 32); HAO_CHECK_LAUNCH();
+	HIP_TRY(hipStreamSynchronize(c->stream));
+	const uint64_t T = c->peek_h[32];
+	if (T >= (1ULL << 32)) { hao_set_err(c, "hao_window_trace_grid: more than 2^32 pairs in one batch"); return HAO_EUNSUPP; }
+	HIP_TRY(c->tg_pairs.reserve(T + 1)); HIP_TRY(c->tg_err.reserve(T + 64)); HIP_TRY(c->tg_pe.reserve(T + 64)); HIP_TRY(c->tg_ps.reserve(T + 64)); HIP_TRY(c->tg_ncig16.reserve(T + 64));
+	if (T) { hipLaunchKernelGGL((ed_grid_kernel<ED_GRID_PAIRS>), g_, b_, 0, c->stream, O.ol_out.p, O.fin_off.p, c->d_len.p, B.lo, n, wl, thre, nword, B.ed_wbase.p, B.ed_woff.p, (hao_ed_task_t*)nullptr, c->tg_pairs.p); HAO_CHECK_LAUNCH(); }
+	c->timer.mark("ed_grid");
+	if (T) { if (int rc = hao_al_ed_deliver(c, O.ol_out.p, c->tg_pairs.p, T, wl, thre, c->tg_err.p, c->tg_pe.p)) return rc; }
+	c->timer.mark("ed_align");
+	uint64_t nt = 0, nc = 0, nu = 0;
+	if (int rc = hao_al_trace_grid(c, O.ol_out.p, c->tg_pairs.p, T, wl, thre, c->tg_err.p, c->tg_ps.p, c->tg_ncig16.p, c->tg_cig, &nt, &nc, &nu)) return rc;
+	c->tg_n = T; c->tg_nsel = nt; c->tg_ncig = nc; c->tg_nuntr = nu; c->tg_valid = true;
+	out[0] = T; out[1] = nt; out[2] = nc; out[3] = nu;
+	return HAO_OK;
+}
+
 // Queue the copy of the current batch's results into the slot's pinned arena (copy stream, after everything on the compute stream so far).
 static int hao_deliver_enqueue(hao_ctx *c)
 {
 	hao_ctx::Batch &B = *c->batch; const int s = B.cur; hao_ctx::Batch::OutSet &O = B.O(); const uint64_t n = B.n; const uint32_t parts = B.dl_parts;
 	auto al = [](size_t v) { return (v + 63) & ~(size_t)63; };
-	const bool ol = parts & HAO_DELIVER_OL, cl = parts & HAO_DELIVER_CL, ex = parts & HAO_DELIVER_EXACT, ed = parts & HAO_DELIVER_ED;
+	const bool ol = parts & HAO_DELIVER_OL, cl = parts & HAO_DELIVER_CL, ex = parts & HAO_DELIVER_EXACT, ed = parts & HAO_DELIVER_ED, tr = parts & HAO_DELIVER_TRACE;
 	size_t o_oloff = 0, o_ol = o_oloff + (ol ? al((n + 1) * 8) : 0), o_fcoff = o_ol + (ol ? al(B.n_ol * sizeof(hao_ovlp_wire_t)) : 0), o_fc = o_fcoff + (ol ? al((B.n_ol + 1) * 8) : 0);
 	size_t o_choff = o_fc + (ol ? al(B.n_fcw * 4) : 0), o_cloff = o_choff + (cl ? al((n + 1) * 8) : 0), o_qmoff = o_cloff + (cl ? al((n + 1) * 8) : 0), o_hdr = o_qmoff + (cl ? al((n + 1) * 8) : 0);
 	const bool q16 = O.qmz16;      // the minimizer tables in 2 + 2 bytes per minimizer (hao_qtab16_kernel) instead of 8
@@ -261,7 +321,8 @@ static int hao_deliver_enqueue(hao_ctx *c)
 	const uint64_t nr4_ = cl ? nw_ / 4 + 1 : 0;      // rank directory entries on the wire: one per 256 positions
 	size_t o_rank = o_bits + (cl ? al(nw_ * 8) : 0), o_codes = o_rank + (cl ? al(nr4_ * 4) : 0), o_exc = o_codes + (cl ? al(B.n_codes) : 0);
 	size_t o_ex = o_exc + (cl ? al(B.n_exc * sizeof(hao_exc_t)) : 0), o_edoff = o_ex + (ex ? al(B.n_ol) : 0);
-	size_t o_ederr = o_edoff + (ed ? al((n + 1) * 8) : 0), o_edpe = o_ederr + (ed ? al(B.ed_n) : 0), total = o_edpe + (ed ? al(B.ed_n * 2) : 0);      // (without HAO_DELIVER_ED: total = o_edoff, the layout of before)
+	size_t o_ederr = o_edoff + (ed ? al((n + 1) * 8) : 0), o_edpe = o_ederr + (ed ? al(B.ed_n) : 0), o_troff = o_edpe + (ed ? al(B.ed_n * 2) : 0);      // (without HAO_DELIVER_ED: o_troff = o_edoff, the layout of before)
+	size_t o_trps = o_troff + (tr ? al((n + 1) * 8) : 0), o_trnc = o_trps + (tr ? al(B.ed_n * 2) : 0), o_trcig = o_trnc + (tr ? al(B.ed_n * 2) : 0), total = o_trcig + (tr ? al(B.tr_ncig * 2) : 0);      // (without HAO_DELIVER_TRACE: total = o_troff)
 	if (total > B.arena_cap[s] || B.arena_bad[s]) {
 		const bool redo_ = B.arena_bad[s]; B.arena_bad[s] = false;      // (hao_deliver_wait saw this slot's last batch copied at less than 40 GB/s: the probe below tries every NUMA node)
 		B.arena_free(s);
@@ -352,6 +413,13 @@ static int hao_deliver_enqueue(hao_ctx *c)
 		e.n_pairs = B.ed_n; e.ed_off = (const uint64_t*)(a + o_edoff); e.err = a + o_ederr; e.pe = (const uint16_t*)(a + o_edpe);
 		d.bytes += (n + 1) * 8 + B.ed_n * 3;
 	}
+	if (tr && n) {
+		HIP_TRY(cp(o_troff, O.tr_off.p, (n + 1) * 8)); HIP_TRY(cp(o_trps, O.tr_ps.p, B.ed_n * 2)); HIP_TRY(cp(o_trnc, O.tr_ncig.p, B.ed_n * 2));
+		if (B.tr_ncig) HIP_TRY(cp(o_trcig, O.tr_cig.p, B.tr_ncig * 2));
+		hao_trace_delivery_t &t = B.tr_dl[s];
+		t.n_traced = B.tr_n; t.n_cigar = B.tr_ncig; t.cg_off = (const uint64_t*)(a + o_troff); t.ps = (const uint16_t*)(a + o_trps); t.n_cig = (const uint16_t*)(a + o_trnc); t.cigar = (const uint16_t*)(a + o_trcig);
+		d.bytes += (n + 1) * 8 + B.ed_n * 4 + B.tr_ncig * 2;
+	}
 	HIP_TRY(hipEventRecord(B.ev_done[s], B.copy_stream));
 	B.dl_pending[s] = true;
 	return HAO_OK;
@@ -376,7 +444,7 @@ static int hao_overlap_run(hao_ctx *c, uint64_t lo, uint64_t hi, const hao_pass_
 	if (!c->has_pt) { hao_set_err(c, "hao_pt_gen must run before hao_overlap_batch"); return HAO_EINVAL; }
 	if (!c->batch) c->batch = new hao_ctx::Batch();
 	hao_ctx::Batch &B = *c->batch; const double t_run0 = hao_now();
-	c->al_grid_n = 0;      // (the window-alignment grid of the previous batch's overlaps is stale)
+	c->al_grid_n = 0; c->tg_valid = false;      // (the window-alignment grid of the previous batch's overlaps is stale)
 	B.valid = false; B.host_valid = false; B.cl_valid = false; B.exact_valid = false; B.h_exact.clear(); B.lo = lo; B.n = hi - lo; B.dl_parts = parts; B.n_exc = 0;
 	const uint64_t n = B.n;
 	if (parts) {
@@ -387,7 +455,8 @@ static int hao_overlap_run(hao_ctx *c, uint64_t lo, uint64_t hi, const hao_pass_
 	// the output set about to be written may still be feeding a copy (its previous async batch): wait for that copy, never for the other slot's
 	if (B.dl_ready && B.dl_pending[B.cur]) { const double t0_ = hao_now(); HIP_TRY(hipEventSynchronize(B.ev_done[B.cur])); B.dl_pending[B.cur] = false; B.t_evsync += hao_now() - t0_; }
 	if (parts) { memset(&B.dl[B.cur], 0, sizeof(hao_delivery_t)); B.dl[B.cur].rid_lo = lo; B.dl[B.cur].n_reads = n;
-		memset(&B.ed_dl[B.cur], 0, sizeof(hao_ed_delivery_t)); if (parts & HAO_DELIVER_ED) { B.ed_dl[B.cur].window = c->ded_window; B.ed_dl[B.cur].thre = c->ded_thre; } }
+		memset(&B.ed_dl[B.cur], 0, sizeof(hao_ed_delivery_t)); if (parts & HAO_DELIVER_ED) { B.ed_dl[B.cur].window = c->ded_window; B.ed_dl[B.cur].thre = c->ded_thre; }
+		memset(&B.tr_dl[B.cur], 0, sizeof(hao_trace_delivery_t)); B.tr_on[B.cur] = (parts & HAO_DELIVER_TRACE) != 0; }
 	if (n == 0) { B.n_anchor = B.n_groups = B.n_chains = B.n_cl = B.n_ol = B.n_fc = B.n_fcw = B.n_mz = 0; B.valid = true; return HAO_OK; }      // (an empty delivery: nothing to copy, the view stays zeroed)
 	// minimizer range of the batch (host knows the per-read offsets? keep a host copy once)
 	if (c->h_ix_mz_off.size() != c->n_reads + 1) {
@@ -748,6 +817,7 @@ static int hao_overlap_run(hao_ctx *c, uint64_t lo, uint64_t hi, const hao_pass_
 	B.valid = true;
 	if (parts & HAO_DELIVER_EXACT) { if (int rc = hao_exact_run(c)) return rc; }
 	if (parts & HAO_DELIVER_ED) { if (int rc = hao_ed_deliver_run(c)) return rc; }
+	if (parts & HAO_DELIVER_TRACE) { if (int rc = hao_trace_deliver_run(c)) return rc; }
 	if (parts) { const double t0_ = hao_now(); const int rc_ = hao_deliver_enqueue(c); B.t_enq += hao_now() - t0_; ++B.t_n; if (c->sw.dltime && (B.t_n & 15) == 0) fprintf(stderr, "[deliver] %llu batches: slot wait %.1f ms, enqueue %.1f ms (arena alloc %.1f ms)\n", (unsigned long long)B.t_n, B.t_evsync * 1e3, B.t_enq * 1e3, B.t_alloc * 1e3); return rc_; }
 	return HAO_OK;
 }

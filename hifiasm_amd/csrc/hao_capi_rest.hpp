@@ -15,6 +15,7 @@ static void hao_release_all(hao_ctx *c)
 	c->w_lkv2.release(); c->w_s40_list.release(); c->w_s40_o.release(); c->w_s40_x.release(); c->w_s40_cnt.release(); c->d_ix_lk.release(); c->w_runid.release(); c->d_ix_mz_x.release(); c->d_ix_mz_info.release(); c->d_ix_mz_off.release(); c->d_ix_sx.release(); c->d_ix_sinfo.release();
 	c->d_ix_keys.release(); c->d_ix_start.release(); c->d_ix_cnt.release(); c->d_ix_bucket.release();
 	c->al_task.release(); c->al_k1.release(); c->al_k2.release(); c->al_path.release(); c->al_i1.release(); c->al_order.release(); c->al_sel.release(); c->al_res.release(); c->al_tres.release(); c->al_want.release(); c->al_cig.release();
+	c->tg.release(); c->tg_pairs.release(); c->tg_err.release(); c->tg_pe.release(); c->tg_ps.release(); c->tg_ncig16.release(); c->tg_cig.release(); c->tg_valid = false;
 }
 
 #include <atomic>
@@ -136,6 +137,7 @@ int hao_overlap_batch_async(hao_ctx *c, uint64_t rid_lo, uint64_t rid_hi, const 
 		if (!(parts & HAO_DELIVER_OL)) { hao_set_err(c, "HAO_DELIVER_ED needs HAO_DELIVER_OL: the decoder rebuilds the pairs from the delivered overlaps"); return HAO_EINVAL; }
 		if (!c->ded_window) { hao_set_err(c, "HAO_DELIVER_ED before hao_deliver_ed_config"); return HAO_EINVAL; }
 	}
+	if ((parts & HAO_DELIVER_TRACE) && !(parts & HAO_DELIVER_ED)) { hao_set_err(c, "HAO_DELIVER_TRACE needs HAO_DELIVER_ED: it traces the pairs the ED stage aligned"); return HAO_EINVAL; }
 	hao_pass_t ps;
 	if (!pass) { if (int rc = hao_pass_default(c, &ps)) return rc; pass = &ps; }
 	HIP_TRY(hipSetDevice(c->device));
@@ -335,6 +337,78 @@ int hao_fetch_ed_grid(hao_ctx *c, hao_ed_task_t *tasks, hao_ed_result_t *res, ui
 	if (n && res) HIP_TRY(hipMemcpyAsync(res, c->al_res.p, n * sizeof(hao_ed_result_t), hipMemcpyDeviceToHost, c->stream));
 	HIP_TRY(hipStreamSynchronize(c->stream));
 	return HAO_OK;
+}
+
+int hao_window_trace_grid(hao_ctx *c, uint32_t window, uint32_t thre, uint64_t out[4])
+{
+	if (!c || !out || !c->batch || !c->batch->valid) return HAO_EINVAL;
+	if (int rc = hao_view_refresh(c)) return rc;
+	HIP_TRY(hipSetDevice(c->device));
+	c->timer.begin(c->stream);
+	if (int rc = hao_trace_grid_run(c, window, thre, out)) return rc;
+	HIP_TRY(hipStreamSynchronize(c->stream));
+	c->timer.collect(c->stage_ms);      // (hao_stage_times: ed_grid, ed_align, trace_sel, trace_align)
+	if (c->tg.path.cap > (1ULL << 27)) c->tg.path.release();      // (more than 1 GB of column scratch is not kept between blocking calls)
+	return HAO_OK;
+}
+
+int hao_fetch_trace_grid(hao_ctx *c, hao_ed_task_t *tasks, hao_trace_result_t *res, uint64_t *cig_off, uint16_t *cigars, uint64_t cap_pairs, uint64_t cap_cigars)
+{
+	if (!c) return HAO_EINVAL;
+	if (!c->batch || !c->batch->valid || !c->tg_valid) { hao_set_err(c, "hao_fetch_trace_grid: no results of hao_window_trace_grid are resident (a new batch or another window-alignment call has reused the scratch)"); return HAO_EINVAL; }
+	if (c->tg_n == 0) { if (cig_off) cig_off[0] = 0; return HAO_OK; }      // (an empty grid: nothing resident to read)
+	HIP_TRY(hipSetDevice(c->device));
+	const uint64_t n = std::min<uint64_t>(cap_pairs, c->tg_n);
+	DevBuf<hao_ed_task_t> dt; DevBuf<hao_trace_result_t> dr; DevBuf<uint64_t> doff;
+	auto done = [&](int rc) { HIP_TRY(hipStreamSynchronize(c->stream)); dt.release(); dr.release(); doff.release(); return rc; };
+	if (n && (tasks || res)) {
+		HIP_TRY(dt.reserve(n)); HIP_TRY(dr.reserve(n));
+		if (int rc = hao_al_trace_grid_expand(c, c->batch->O().ol_out.p, n, dt.p, dr.p)) return done(rc);
+		if (tasks) HIP_TRY(hipMemcpyAsync(tasks, dt.p, n * sizeof(hao_ed_task_t), hipMemcpyDeviceToHost, c->stream));
+		if (res) HIP_TRY(hipMemcpyAsync(res, dr.p, n * sizeof(hao_trace_result_t), hipMemcpyDeviceToHost, c->stream));
+	}
+	uint64_t end = 0;      // cigar entries of the first n pairs
+	HIP_TRY(doff.reserve(n + 2));
+	if (int rc = hao_al_trace_grid_off(c, nullptr, n, c->tg_nsel, doff.p)) return done(rc);
+	HIP_TRY(hipMemcpyAsync(&end, doff.p + n, 8, hipMemcpyDeviceToHost, c->stream));
+	if (cig_off) HIP_TRY(hipMemcpyAsync(cig_off, doff.p, (n + 1) * 8, hipMemcpyDeviceToHost, c->stream));
+	HIP_TRY(hipStreamSynchronize(c->stream));
+	const uint64_t nc = std::min<uint64_t>(end, cap_cigars);
+	if (cigars && nc) HIP_TRY(hipMemcpyAsync(cigars, c->tg_cig.p, nc * 2, hipMemcpyDeviceToHost, c->stream));
+	return done(HAO_OK);
+}
+
+int hao_deliver_trace(hao_ctx *c, int slot, hao_trace_delivery_t *out)
+{
+	if (!c || !out || slot < 0 || slot > 1 || !c->batch || !c->batch->dl_ready) return HAO_EINVAL;
+	hao_ctx::Batch &B = *c->batch;
+	if (!B.tr_on[slot]) { hao_set_err(c, "hao_deliver_trace: the slot's batch did not ask for HAO_DELIVER_TRACE"); return HAO_EINVAL; }
+	if (B.dl_pending[slot]) { hao_set_err(c, "hao_deliver_trace: hao_deliver_wait has not been called on the slot"); return HAO_EINVAL; }
+	*out = B.tr_dl[slot];
+	return HAO_OK;
+}
+
+// pure function of the three views of a delivered batch: read rid's pairs and distance-only results as hao_unpack_ed gives them, with the traced part added
+uint64_t hao_unpack_trace(const hao_trace_delivery_t *t, const hao_ed_delivery_t *e, const hao_delivery_t *d, const uint32_t *len, uint64_t rid,
+		hao_ed_task_t *tasks, hao_trace_result_t *res, uint64_t *cig_off, uint16_t *cigars, uint64_t cap_pairs, uint64_t cap_cigars)
+{
+	if (!t || !e || !d || !len || !t->cg_off || !e->window || !e->ed_off || rid < d->rid_lo || rid >= d->rid_lo + d->n_reads) return 0;
+	const uint64_t r = rid - d->rid_lo, p0 = e->ed_off[r], np = e->ed_off[r + 1] - p0, c0 = t->cg_off[r], nc = t->cg_off[r + 1] - c0;
+	if (np > cap_pairs || nc > cap_cigars || !tasks || !res || !cig_off || !cigars) return np;
+	std::vector<hao_ed_result_t> er(np);
+	const uint64_t k = hao_unpack_ed(e, d, len, rid, tasks, er.data(), np);
+	if (k != np) return UINT64_MAX;
+	uint64_t o = 0;
+	for (uint64_t i = 0; i < np; ++i) {
+		const uint16_t ps = t->ps[p0 + i], m = t->n_cig[p0 + i];
+		hao_trace_result_t &x = res[i];
+		x.err = er[i].err; x.pe = er[i].pe; x.ps = ps == 0xffff ? -1 : (int32_t)ps; x.ts = 0; x.te = (int32_t)tasks[i].t_len - 1; x.n_cigar = m;
+		cig_off[i] = o; o += m;
+	}
+	cig_off[np] = o;
+	if (o != nc) return UINT64_MAX;
+	if (nc) memcpy(cigars, t->cigar + c0, nc * 2);
+	return np;
 }
 
 int hao_deliver_ed_config(hao_ctx *c, uint32_t window, uint32_t thre)

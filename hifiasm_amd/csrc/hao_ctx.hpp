@@ -7,6 +7,7 @@
 #include <cstdlib>
 #include <cstring>
 #include "hao_common.cuh"
+#include "hao_grid_pair.cuh"      // (hao_ed_pair)
 
 struct hao_ctx;
 static void hao_set_err(hao_ctx *c, const std::string &m);
@@ -162,6 +163,16 @@ struct hao_ctx {
 	DevBuf<hao_ed_task_t> al_task; DevBuf<uint64_t> al_k1, al_k2, al_path; DevBuf<uint32_t> al_i1, al_order, al_sel; DevBuf<hao_ed_result_t> al_res; DevBuf<hao_trace_result_t> al_tres;
 	DevBuf<uint8_t> al_want; DevBuf<uint16_t> al_cig;
 	uint32_t ded_window = 0, ded_thre = 0;      // hao_deliver_ed_config: the grid of HAO_DELIVER_ED (window 0: not configured); per context, a view has its own
+	// f3 with traceback on the grid (hao_trace_grid.cuh): the stage's scratch, compute stream only (hao_window_trace_grid and HAO_DELIVER_TRACE share it) -
+	// flags and selected pairs, entry counts and their scans, the compact array's offsets, the column scratch, the rows of one slice, two counters
+	struct TraceGrid {
+		DevBuf<uint8_t> want; DevBuf<uint32_t> sel; DevBuf<uint64_t> cnt, loc, off, path; DevBuf<uint16_t> rows; DevBuf<unsigned long long> ctr;
+		void release() { want.release(); sel.release(); cnt.release(); loc.release(); off.release(); path.release(); rows.release(); ctr.release(); }
+	} tg;
+	// hao_window_trace_grid's results, kept for hao_fetch_trace_grid (tg_valid: they belong to the current batch and no window-alignment batch has run since):
+	// the pair list, the distance-only err / pe, ps and entry count per pair, the compact cigars; pairs, traced pairs, entries, aligned but untraced pairs
+	bool tg_valid = false; uint32_t tg_wl = 0, tg_thre = 0; uint64_t tg_n = 0, tg_nsel = 0, tg_ncig = 0, tg_nuntr = 0;
+	DevBuf<hao_ed_pair> tg_pairs; DevBuf<uint8_t> tg_err; DevBuf<uint16_t> tg_pe, tg_ps, tg_ncig16, tg_cig;
 	struct Batch;
 	Batch *batch = nullptr;
 	StageTimer timer; std::vector<std::pair<std::string, float> > stage_ms;

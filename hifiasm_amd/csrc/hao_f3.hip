@@ -1,6 +1,7 @@
 // libhao.so, second translation unit: f3, the window-alignment batches (hao_align.cuh) - 36 instantiations of hao_al_kernel (five modes, with and without
-// traceback, bands of one to four words) and the four of the delivery path's kernel (hao_ed_deliver.cuh) that the rest of the library reaches through
-// hao_al_ed_resident / hao_al_ed_deliver only; compiled beside hao_capi.hip (hifiasm_amd/build.py).
+// traceback, bands of one to four words), the four of the delivery path's kernel (hao_ed_deliver.cuh) and the four of the traced grid stage's
+// (hao_trace_grid.cuh) that the rest of the library reaches through hao_al_ed_resident / hao_al_ed_deliver / hao_al_trace_grid only; compiled beside
+// hao_capi.hip (hifiasm_amd/build.py).
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -8,6 +9,7 @@
 #include "hao_comm.hpp"
 #include "hao_align.cuh"
 #include "hao_ed_deliver.cuh"
+#include "hao_trace_grid.cuh"
 
 // ---- f3 (hao_align.cuh): host side of the window-alignment batches ----
 // tasks -> device, and their order by text window (hao_align.cuh: a wave takes 64 neighbours of that order, which mostly share one text)
@@ -92,6 +94,75 @@ int hao_al_ed_deliver(hao_ctx *c, const hao_ovlp_t *ol, const hao_ed_pair *pairs
 	return HAO_OK;
 }
 
+// the traced grid stage (hao_trace_grid.cuh; hao_window_trace_grid and HAO_DELIVER_TRACE, hao_batch.hpp): n pairs (overlap, window) of the batch's ol->list in
+// text order and their distance-only error bytes -> ps16[n] / ncig16[n] (0xffff / 0 for the pairs without a cigar), the cigars of the traced pairs in pair
+// order in cig, and c->tg.sel / c->tg.off (the traced pairs and their offsets into cig: hao_tg_off_kernel's input).  Two peeks at totals on the way.
+int hao_al_trace_grid(hao_ctx *c, const hao_ovlp_t *ol, const hao_ed_pair *pairs, uint64_t n, uint32_t wl, uint32_t thre, const uint8_t *err,
+		uint16_t *ps16, uint16_t *ncig16, DevBuf<uint16_t> &cig, uint64_t *n_traced, uint64_t *n_cigar, uint64_t *n_untraced)
+{
+	hao_ctx::TraceGrid &G = c->tg;
+	*n_traced = 0; *n_cigar = 0; *n_untraced = 0;
+	if (n == 0) { HIP_TRY(cig.reserve(1)); HIP_TRY(G.off.reserve(2)); HIP_TRY(hipMemsetAsync(G.off.p, 0, 8, c->stream)); c->timer.mark("trace_sel"); c->timer.mark("trace_align"); return HAO_OK; }
+	const hao_ed_reads R = hao_al_reads_of(c);
+	const uint32_t nword = hao_al_nword(thre), cap = 2 * thre + 3;
+	HIP_TRY(G.want.reserve(n + 1)); HIP_TRY(G.sel.reserve(n + 1)); HIP_TRY(G.ctr.reserve(2)); HIP_TRY(c->d_cursor.reserve(2));
+	HIP_TRY(hipMemsetAsync(ps16, 0xff, n * 2, c->stream)); HIP_TRY(hipMemsetAsync(ncig16, 0, n * 2, c->stream)); HIP_TRY(hipMemsetAsync(G.ctr.p, 0, 16, c->stream));
+	hipLaunchKernelGGL(hao_tg_flag_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, c->d_len.p, ol, pairs, n, wl, thre, err, G.want.p, G.ctr.p); HAO_CHECK_LAUNCH();
+	size_t tb = 0;
+	const auto idx = rocprim::make_counting_iterator<uint32_t>(0);
+	HIP_TRY(rocprim::select(nullptr, tb, idx, G.want.p, G.sel.p, (uint64_t*)c->d_cursor.p, n, c->stream)); HIP_TRY(hao_tmp(c, tb));
+	HIP_TRY(rocprim::select(c->d_tmp.p, tb, idx, G.want.p, G.sel.p, (uint64_t*)c->d_cursor.p, n, c->stream));
+	hipLaunchKernelGGL(hao_peek_kernel, dim3(1), dim3(64), 0, c->stream, (const unsigned long long*)c->d_cursor.p, 1, c->peek_d + 33); HAO_CHECK_LAUNCH();
+	hipLaunchKernelGGL(hao_peek_kernel, dim3(1), dim3(64), 0, c->stream, G.ctr.p, 2, c->peek_d + 34); HAO_CHECK_LAUNCH();
+	HIP_TRY(hipStreamSynchronize(c->stream));
+	const uint64_t T = c->peek_h[33], bound = c->peek_h[34];
+	*n_untraced = c->peek_h[35];
+	c->timer.mark("trace_sel");
+	HIP_TRY(cig.reserve(bound + 1)); HIP_TRY(G.off.reserve(T + 2)); HIP_TRY(hipMemsetAsync(G.off.p, 0, 8, c->stream));      // (off[0] = 0: no traced pair, every offset is 0)
+	if (T) {
+		// column scratch: 24 bytes per band word, text column (t_len <= wl, + slot 0) and selected pair, in slices whose columns fit ~4 GB; rows of 2 thre + 3 entries per slice
+		const uint64_t cw = 3 * (uint64_t)nword, ncol = (uint64_t)wl + 1;
+		const uint64_t slice = std::max<uint64_t>(256, std::min<uint64_t>((T + 255) & ~255ULL, ((4ULL << 30) / (8 * cw * ncol)) & ~255ULL));
+		HIP_TRY(G.path.reserve(cw * ncol * slice + 1)); HIP_TRY(G.rows.reserve(slice * cap + 1)); HIP_TRY(G.cnt.reserve(slice + 2)); HIP_TRY(G.loc.reserve(slice + 2));
+		const dim3 b_(256);
+		for (uint64_t lo = 0; lo < T; lo += slice) {
+			const uint64_t m = std::min<uint64_t>(slice, T - lo);
+			const dim3 g2((unsigned)((m + 255) / 256));
+			HIP_TRY(hipMemsetAsync(G.cnt.p + m, 0, 8, c->stream));
+			if (nword == 1) hipLaunchKernelGGL((hao_trace_grid_kernel<uint64_t>), g2, b_, 0, c->stream, R, ol, pairs, G.sel.p + lo, m, wl, thre, G.path.p, slice, G.rows.p, cap, G.cnt.p, ps16, ncig16);
+			else if (nword == 2) hipLaunchKernelGGL((hao_trace_grid_kernel<hao_u128>), g2, b_, 0, c->stream, R, ol, pairs, G.sel.p + lo, m, wl, thre, G.path.p, slice, G.rows.p, cap, G.cnt.p, ps16, ncig16);
+			else if (nword == 3) hipLaunchKernelGGL((hao_trace_grid_kernel<hao_wide<3> >), g2, b_, 0, c->stream, R, ol, pairs, G.sel.p + lo, m, wl, thre, G.path.p, slice, G.rows.p, cap, G.cnt.p, ps16, ncig16);
+			else hipLaunchKernelGGL((hao_trace_grid_kernel<hao_wide<4> >), g2, b_, 0, c->stream, R, ol, pairs, G.sel.p + lo, m, wl, thre, G.path.p, slice, G.rows.p, cap, G.cnt.p, ps16, ncig16);
+			HAO_CHECK_LAUNCH();
+			if (int rc = hao_excl_scan_u64(c, G.cnt.p, G.loc.p, m + 1)) return rc;
+			hipLaunchKernelGGL(hao_tg_compact_kernel, g2, b_, 0, c->stream, G.rows.p, cap, G.loc.p, m, G.off.p + lo, cig.p, (uint64_t)cig.cap); HAO_CHECK_LAUNCH();
+		}
+		hipLaunchKernelGGL(hao_peek_kernel, dim3(1), dim3(64), 0, c->stream, (const unsigned long long*)(G.off.p + T), 1, c->peek_d + 36); HAO_CHECK_LAUNCH();
+		HIP_TRY(hipStreamSynchronize(c->stream));
+		*n_cigar = c->peek_h[36];
+		if (*n_cigar > bound) { hao_set_err(c, "traced grid stage: more cigar entries than their bound"); return HAO_EUNSUPP; }      // (hao_tg_bound rules it out)
+	}
+	c->timer.mark("trace_align");
+	*n_traced = T;
+	return HAO_OK;
+}
+
+// out[r] = offset into the traced grid stage's cigars of pair at[r] (at = NULL: of pair r), r = 0 .. n (hao_tg_off_kernel over c->tg.sel / c->tg.off)
+int hao_al_trace_grid_off(hao_ctx *c, const uint64_t *at, uint64_t n, uint64_t n_traced, uint64_t *out)
+{
+	hipLaunchKernelGGL(hao_tg_off_kernel, dim3((unsigned)((n + 256) / 256)), dim3(256), 0, c->stream, at, n, c->tg.sel.p, n_traced, c->tg.off.p, out); HAO_CHECK_LAUNCH();
+	return HAO_OK;
+}
+
+// hao_fetch_trace_grid's expansion: the first n pairs of hao_window_trace_grid's list as tasks and widened results (device buffers of n entries each)
+int hao_al_trace_grid_expand(hao_ctx *c, const hao_ovlp_t *ol, uint64_t n, hao_ed_task_t *tasks, hao_trace_result_t *res)
+{
+	if (n == 0) return HAO_OK;
+	hipLaunchKernelGGL(hao_tg_expand_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, c->d_len.p, ol, c->tg_pairs.p, n, c->tg_wl, c->tg_thre,
+		c->tg_err.p, c->tg_pe.p, c->tg_ps.p, c->tg_ncig16.p, tasks, res); HAO_CHECK_LAUNCH();
+	return HAO_OK;
+}
+
 extern "C" {
 
 int hao_window_ed_batch(hao_ctx *c, const hao_ed_task_t *tasks, uint64_t n_tasks, hao_ed_result_t *out)
@@ -100,6 +171,7 @@ int hao_window_ed_batch(hao_ctx *c, const hao_ed_task_t *tasks, uint64_t n_tasks
 	if (int rc = hao_view_refresh(c)) return rc;
 	if (hao_is_sharded(c)) { hao_set_err(c, "hao_window_ed_batch needs the bases of both reads: single-device mode only"); return HAO_EUNSUPP; }
 	c->al_grid_n = 0;      // (the task / result scratch is shared with hao_window_ed_grid: what that call left is gone)
+	c->tg_valid = false;      // (and hao_window_trace_grid's results follow the same rule)
 	if (n_tasks == 0) return HAO_OK;
 	if (n_tasks >= (1ULL << 32)) { hao_set_err(c, "hao_window_ed_batch: more than 2^32 tasks in one call"); return HAO_EUNSUPP; }
 	uint32_t words = 0;      // bit (nword - 1): some band needs nword 64-bit words (the reference's cal_exz_infi picks nword = ceil((2 thre + 1) / 64), Correct.cpp:14508-14565)
@@ -132,7 +204,7 @@ int hao_window_trace_batch(hao_ctx *c, int mode, const hao_ed_task_t *tasks, uin
 	if (!c || (mode < HAO_ALIGN_GLOBAL || mode > HAO_ALIGN_SEMI) || (!tasks && n_tasks) || (!out && n_tasks) || (!cigars && n_tasks && cigar_cap)) return HAO_EINVAL;
 	if (int rc = hao_view_refresh(c)) return rc;
 	if (hao_is_sharded(c)) { hao_set_err(c, "hao_window_trace_batch needs the bases of both reads: single-device mode only"); return HAO_EUNSUPP; }
-	c->al_grid_n = 0;
+	c->al_grid_n = 0; c->tg_valid = false;
 	if (n_tasks == 0) return HAO_OK;
 	if (n_tasks >= (1ULL << 32)) { hao_set_err(c, "hao_window_trace_batch: more than 2^32 tasks in one call"); return HAO_EUNSUPP; }
 	uint64_t tn_max = 1; uint32_t words = 0;      // bit (nword - 1): some band needs nword 64-bit words

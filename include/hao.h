@@ -260,7 +260,8 @@ int hao_fetch_ed_grid(hao_ctx *c, hao_ed_task_t *tasks, hao_ed_result_t *res, ui
  * the same (err, pe) - and the results cross PCIe in the batch's arena: 3 bytes per pair (an error byte, 0xff = no alignment within thre, and a 16-bit pattern
  * end, 0xffff = -1) plus the pairs' offsets per read.  Tasks do not travel: hao_unpack_ed rebuilds them from the delivered overlaps.  The blocking path's
  * task / result scratch (hao_window_ed_grid / hao_fetch_ed_grid) is not touched; batches without HAO_DELIVER_ED keep their arena layout and byte count.
- * Not covered: the fake-cigar shift of the window's target start (Correct.cpp:3897), traced modes, the sharded path.
+ * Not covered: the fake-cigar shift of the window's target start (Correct.cpp:3897), the sharded path.  The semi-global traced mode rides along as HAO_DELIVER_TRACE
+ * (below); the other traced modes stay host-fed.
  *   hao_deliver_ed_config: the grid of this context's HAO_DELIVER_ED batches (an attached view has its own).  window == 0, thre > HAO_ED_MAX_THRE or
  *                          window + 2 thre >= 65535 (pe travels in 16 bits): HAO_EINVAL.  Bands of two or more words leave out the pairs hao_window_ed_grid leaves out.
  *   hao_deliver_ed:        the ED view of a slot whose batch asked for HAO_DELIVER_ED, valid after hao_deliver_wait on that slot; its pointers live in the slot's
@@ -300,6 +301,43 @@ typedef struct { int32_t err, ps, pe, ts, te, n_cigar; } hao_trace_result_t;
                                  * The band must cover the pattern: 0 <= p_len - t_len + abs_diag <= 2 thre and t_len > abs_diag (else HAO_EINVAL: the reference's
                                  * traceback would index its column words out of range).  (Numbering: the modes of Correct.cpp:14536-14545.) */
 int hao_window_trace_batch(hao_ctx *c, int mode, const hao_ed_task_t *tasks, uint64_t n_tasks, hao_trace_result_t *out, uint16_t *cigars, uint32_t cigar_cap);
+
+/* f3 with traceback on the device grid: the semi-global traced alignment (HAO_ALIGN_SEMI: ed_band_cal_semi_64_w_absent_diag_trace + gen_trace, the call
+ * Correct.cpp:3897-3911 makes right after the distance-only one) of the grid pairs hao_window_ed_grid(window, thre) forms, in the same text order.  A pair is
+ * TRACED iff its distance-only result aligned (err <= thre) and its band covers the pattern (0 <= p_len - t_len + abs_diag <= 2 thre, t_len > abs_diag: the
+ * domain hao_window_trace_batch accepts for HAO_ALIGN_SEMI).  A traced pair's (err, pe) is the distance-only result and (ps, ts = 0, te = t_len - 1, cigar)
+ * is what hao_window_trace_batch(HAO_ALIGN_SEMI) gives for the same task; an aligned pair outside the domain (clipped at a read end) keeps its distance-only
+ * (err, pe) with ps = -1 and no cigar (ALIGNED BUT UNTRACED); a pair without an alignment reads err = INT32_MAX, pe = ps = -1.  ts = 0 and te = t_len - 1 for
+ * every pair.  A cigar has at most 2 thre + 3 entries (push_trace's encoding, op << 14 | len).  Not covered: the fake-cigar shift (Correct.cpp:3897), the other
+ * traced modes (host-fed: hao_window_trace_batch), the sharded path (HAO_EUNSUPP).  On the device, the traced sweep keeps three words per band word and text
+ * column (D0, VP, VN; the walk derives HP / HN) in slices of ~4 GB, and the cigars are compacted into one array.
+ *   hao_window_trace_grid: over the last batch (hao_overlap_batch[_ex]; results resident).  out[0] = grid pairs, out[1] = traced pairs, out[2] = cigar entries,
+ *                          out[3] = aligned but untraced pairs.  thre > HAO_ED_MAX_THRE, window == 0 or window + 2 thre >= 65535: HAO_EINVAL.  Its results stay
+ *                          resident until the next batch or hao_window_ed_batch / hao_window_trace_batch call.
+ *   hao_fetch_trace_grid:  the first min(cap_pairs, out[0]) pairs: tasks (rebuilt from the pair list), results, cig_off[0 .. m] (offsets into cigars; untraced
+ *                          pairs have empty ranges) and the cigar entries of those pairs, the first cap_cigars of them.  Any pointer may be NULL.
+ * HAO_DELIVER_TRACE in the parts of hao_overlap_batch_async (only with HAO_DELIVER_ED, else HAO_EINVAL) runs the same stage on the pairs and error bytes of
+ * the ED stage (hao_deliver_ed_config's window and threshold) and delivers, after the ED records: per read a uint64 offset of its first cigar entry, per pair a
+ * uint16 ps (0xffff: none) and a uint16 entry count, and the entries in pair order.  Batches without the part keep their arena layout and byte count.
+ *   hao_deliver_trace:     the view of a slot whose batch asked for HAO_DELIVER_TRACE, valid after hao_deliver_wait on that slot (HAO_EINVAL otherwise); its
+ *                          pointers live in the slot's pinned arena.
+ *   hao_unpack_trace:      read rid's pairs as hao_unpack_ed rebuilds them, their results (hao_fetch_trace_grid's values), per-pair offsets cig_off[0 .. n]
+ *                          into the read's cigar entries and those entries.  Returns the pair count; nothing is written when it exceeds cap_pairs, the read's
+ *                          entries exceed cap_cigars, or tasks / res / cig_off / cigars is NULL; 0 for a read outside the batch; UINT64_MAX when the rebuilt
+ *                          pairs or the entry counts do not match the delivered ones (len is not the batch's).  A pure function of the three views. */
+int hao_window_trace_grid(hao_ctx *c, uint32_t window, uint32_t thre, uint64_t out[4]);
+int hao_fetch_trace_grid(hao_ctx *c, hao_ed_task_t *tasks, hao_trace_result_t *res, uint64_t *cig_off, uint16_t *cigars, uint64_t cap_pairs, uint64_t cap_cigars);
+#define HAO_DELIVER_TRACE 16u      /* traceback of the batch's aligned grid pairs (with HAO_DELIVER_ED; hao_deliver_trace, hao_unpack_trace) */
+typedef struct {
+	uint64_t n_traced, n_cigar;  /* traced pairs and cigar entries of the batch */
+	const uint64_t *cg_off;      /* [n_reads + 1]: cigar entries of read r = [cg_off[r], cg_off[r + 1]) */
+	const uint16_t *ps;          /* [n_pairs] (the ED view's pairs): start of the alignment on the pattern, 0xffff = no cigar */
+	const uint16_t *n_cig;       /* [n_pairs]: cigar entries of the pair */
+	const uint16_t *cigar;       /* [n_cigar]: the entries, pair after pair */
+} hao_trace_delivery_t;
+int hao_deliver_trace(hao_ctx *c, int slot, hao_trace_delivery_t *out);
+uint64_t hao_unpack_trace(const hao_trace_delivery_t *t, const hao_ed_delivery_t *e, const hao_delivery_t *d, const uint32_t *len, uint64_t rid,
+                          hao_ed_task_t *tasks, hao_trace_result_t *res, uint64_t *cig_off, uint16_t *cigars, uint64_t cap_pairs, uint64_t cap_cigars);
 
 /* On-disk formats: the filter table, the position index and the read store in the reference's own resume format, so a GPU-built
  * index can be handed to a stock hifiasm (load_pt_index, htab.cpp:1432-1550, called from Assembly.cpp:2078):
