@@ -52,7 +52,8 @@ class Delivery(C.Structure):
 
 class EdDelivery(C.Structure):
     """hao_ed_delivery_t: the window-alignment results of a batch delivered with HAO_DELIVER_ED (pointers into the same pinned arena as its Delivery)"""
-    _fields_ = [("n_pairs", C.c_uint64), ("window", C.c_uint32), ("thre", C.c_uint32), ("ed_off", C.c_void_p), ("err", C.c_void_p), ("pe", C.c_void_p)]
+    _fields_ = [("n_pairs", C.c_uint64), ("window", C.c_uint32), ("thre", C.c_uint32), ("ed_off", C.c_void_p), ("err", C.c_void_p), ("pe", C.c_void_p),
+                ("placement", C.c_uint32), ("pad", C.c_uint32), ("e_rate", C.c_double), ("unresolved", C.c_uint64), ("ovlp", C.c_void_p)]
 
 
 class TraceDelivery(C.Structure):
@@ -61,6 +62,7 @@ class TraceDelivery(C.Structure):
 
 
 DELIVER_OL, DELIVER_CL, DELIVER_EXACT, DELIVER_ED, DELIVER_TRACE = 1, 2, 4, 8, 16
+PLACE_DIAG, PLACE_REF = 0, 1      # hao_ed_delivery_t::placement
 
 ABI_SYMBOLS = [
     "hao_opt_default", "hao_create", "hao_destroy", "hao_last_error", "hao_set_reads", "hao_ft_gen", "hao_pt_gen",
@@ -70,6 +72,7 @@ ABI_SYMBOLS = [
     "hao_loop_create", "hao_loop_destroy", "hao_dist_init_loopback", "hao_batch_digest", "hao_selftest_rocprim", "hao_selftest_big", "hao_selftest_sortbits", "hao_unpack_cigar", "hao_unpack_overlaps", "hao_overlap_batch_async", "hao_deliver_wait", "hao_unpack_hits", "hao_exact_check", "hao_fetch_exact", "hao_window_ed_batch", "hao_index_save", "hao_index_load", "hao_next_slot", "hao_attach", "hao_window_trace_batch", "hao_delivery_digest", "hao_ft_passes", "hao_ovlp_bin_read", "hao_ovlp_bin_write", "hao_window_ed_grid", "hao_fetch_ed_grid",
     "hao_deliver_ed_config", "hao_deliver_ed", "hao_unpack_ed",
     "hao_window_trace_grid", "hao_fetch_trace_grid", "hao_deliver_trace", "hao_unpack_trace",
+    "hao_window_ed_ref", "hao_fetch_ed_ovlp", "hao_deliver_ed_config_ref", "hao_ref_thresholds",
 ]
 
 
@@ -127,6 +130,10 @@ def lib():
         L.hao_deliver_ed.argtypes = [vp, C.c_int, C.POINTER(EdDelivery)]
         L.hao_unpack_ed.argtypes = [C.POINTER(EdDelivery), C.POINTER(Delivery), u32p, C.c_uint64, vp, vp, C.c_uint64]; L.hao_unpack_ed.restype = C.c_uint64
         L.hao_window_trace_grid.argtypes = [vp, C.c_uint32, C.c_uint32, u64p]
+        L.hao_window_ed_ref.argtypes = [vp, C.c_uint32, C.c_double, u64p, u64p]
+        L.hao_fetch_ed_ovlp.argtypes = [vp, C.c_uint64, C.POINTER(vp), u64p]
+        L.hao_deliver_ed_config_ref.argtypes = [vp, C.c_uint32, C.c_double]
+        L.hao_ref_thresholds.argtypes = [C.c_uint32, C.c_double, u8p]; L.hao_ref_thresholds.restype = None
         L.hao_fetch_trace_grid.argtypes = [vp, vp, vp, u64p, vp, C.c_uint64, C.c_uint64]
         L.hao_deliver_trace.argtypes = [vp, C.c_int, C.POINTER(TraceDelivery)]
         L.hao_unpack_trace.argtypes = [C.POINTER(TraceDelivery), C.POINTER(EdDelivery), C.POINTER(Delivery), u32p, C.c_uint64, vp, vp, u64p, vp, C.c_uint64, C.c_uint64]
@@ -341,6 +348,19 @@ class Engine:
         """the window grid of this context's DELIVER_ED batches (hao_deliver_ed_config: windows of `window` query bases, threshold thre)"""
         self._ck(self.L.hao_deliver_ed_config(self.h, C.c_uint32(window), C.c_uint32(thre)), "hao_deliver_ed_config")
 
+    def deliver_ed_config_ref(self, window=775, e_rate=0.04):
+        """this context's following DELIVER_ED batches in REFERENCE placement (hao_deliver_ed_config_ref): the fake-cigar shift of the window's target start, one
+        threshold per window from its length and e_rate, init_waln's admission and clipping; deliver_ed_config switches back"""
+        self._ck(self.L.hao_deliver_ed_config_ref(self.h, C.c_uint32(window), C.c_double(e_rate)), "hao_deliver_ed_config_ref")
+
+    def delivered_ed_ovlp(self, d, rid):
+        """uint32 [n_ol, 4] (windows covered, windows aligned, aligned bases, error sum) of read rid's overlaps out of a reference-placed DELIVER_ED batch"""
+        e = getattr(d, "ed", None)
+        if e is None or not e.ovlp:
+            raise HaoError("delivered_ed_ovlp: the batch was not delivered with DELIVER_ED in reference placement")
+        oo = _arr(d.ol_off + 8 * (rid - d.rid_lo), 2, np.uint64)
+        return _arr(e.ovlp + 16 * int(oo[0]), 4 * int(oo[1] - oo[0]), np.uint32).reshape(-1, 4)
+
     def deliver_ed(self, slot):
         """the EdDelivery view of a waited-for slot whose batch asked for DELIVER_ED"""
         e = EdDelivery()
@@ -460,6 +480,19 @@ class Engine:
         self._ck(self.L.hao_fetch_ed_grid(self.h, t.ctypes.data_as(C.c_void_p), r.ctypes.data_as(C.c_void_p), C.c_uint64(n)), "hao_fetch_ed_grid")
         return t, r
 
+    def window_ed_ref(self, window=775, e_rate=0.04):
+        """hao_window_ed_ref: the last batch's window / candidate pairs in REFERENCE placement, generated and aligned on the device; fetch_ed_grid serves tasks
+        and results, fetch_ed_ovlp the per-overlap summaries.  Returns (pairs, unresolved windows)"""
+        n, u = C.c_uint64(), C.c_uint64()
+        self._ck(self.L.hao_window_ed_ref(self.h, C.c_uint32(window), C.c_double(e_rate), C.byref(n), C.byref(u)), "hao_window_ed_ref")
+        return int(n.value), int(u.value)
+
+    def fetch_ed_ovlp(self, rid):
+        """uint32 [n_ol, 4] (windows covered, windows aligned, aligned bases, error sum) per overlap of read rid after window_ed_ref, aligned with h_ec_lchain(rid)[0]"""
+        p, n = C.c_void_p(), C.c_uint64()
+        self._ck(self.L.hao_fetch_ed_ovlp(self.h, rid, C.byref(p), C.byref(n)), "hao_fetch_ed_ovlp")
+        return _arr(p.value, 4 * n.value, np.uint32).reshape(-1, 4)
+
     def window_trace_grid(self, window=375, thre=15):
         """hao_window_trace_grid: the last batch's grid pairs aligned with traceback where they align inside the semi-global domain;
         returns (grid pairs, traced pairs, cigar entries, aligned but untraced pairs)"""
@@ -522,3 +555,10 @@ class Engine:
         ms = (C.c_float * 64)()
         n = self.L.hao_stage_times(self.h, names, ms, 64)
         return [(names[i].decode(), float(ms[i])) for i in range(n)]
+
+
+def ref_thresholds(window, e_rate):
+    """uint8 [window + 1]: the threshold of a window of q_l bases in reference placement (hao_ref_thresholds)"""
+    out = np.zeros(int(window) + 1, dtype=np.uint8)
+    lib().hao_ref_thresholds(C.c_uint32(window), C.c_double(e_rate), out.ctypes.data_as(C.POINTER(C.c_uint8)))
+    return out

@@ -29,8 +29,9 @@ struct hao_ctx::Batch {
 		DevBuf<hao_chain_hdr_t> hdr; DevBuf<uint64_t> bits; DevBuf<uint32_t> rank, rank4; DevBuf<uint8_t> codes; DevBuf<hao_exc_t> exc; DevBuf<hao_qmz_t> qmz; DevBuf<uint16_t> qmz_pos, qmz_cnt; bool qmz16 = false;   // cl->list in the wire format (hao_deliver.cuh)
 		DevBuf<uint8_t> exact;                                                                        // exact-overlap flags of ol_out
 		DevBuf<uint64_t> ed_off; DevBuf<uint8_t> ed_err; DevBuf<uint16_t> ed_pe;                      // HAO_DELIVER_ED: pairs per read, error byte and pattern end per pair (hao_ed_deliver.cuh)
+		DevBuf<hao_ed_ovlp_sum> ed_sum;                                                               // HAO_DELIVER_ED in reference placement: the per-overlap summaries (ed_ref_summary_kernel)
 		DevBuf<uint64_t> tr_off; DevBuf<uint16_t> tr_ps, tr_ncig, tr_cig;                            // HAO_DELIVER_TRACE: cigar entries per read, ps and entry count per pair, the entries (hao_trace_grid.cuh)
-		void release() { tr_off.release(); tr_ps.release(); tr_ncig.release(); tr_cig.release(); ed_off.release(); ed_err.release(); ed_pe.release(); fcw_off.release(); fcw.release(); ol_out.release(); ol_wire.release(); fin_off.release(); fc_out.release(); fc_out_off.release(); ch_off.release(); cl_off.release(); qm_off.release(); hdr.release(); bits.release(); rank.release(); rank4.release(); codes.release(); exc.release(); qmz.release(); qmz_pos.release(); qmz_cnt.release(); exact.release(); }
+		void release() { ed_sum.release(); tr_off.release(); tr_ps.release(); tr_ncig.release(); tr_cig.release(); ed_off.release(); ed_err.release(); ed_pe.release(); fcw_off.release(); fcw.release(); ol_out.release(); ol_wire.release(); fin_off.release(); fc_out.release(); fc_out_off.release(); ch_off.release(); cl_off.release(); qm_off.release(); hdr.release(); bits.release(); rank.release(); rank4.release(); codes.release(); exc.release(); qmz.release(); qmz_pos.release(); qmz_cnt.release(); exact.release(); }
 	} out[2];
 	int cur = 0;
 	OutSet &O() { return out[cur]; }
@@ -39,6 +40,7 @@ struct hao_ctx::Batch {
 	void arena_free(int x) { if (!arena[x]) return; if (arena_reg[x]) { (void)hipHostUnregister(arena[x]); (void)munmap(arena[x], arena_cap[x]); } else (void)hipHostFree(arena[x]); arena[x] = nullptr; arena_cap[x] = 0; arena_reg[x] = false; } hipStream_t copy_stream = nullptr; hipEvent_t ev_ready[2], ev_done[2], ev_cstart[2]; bool arena_bad[2] = { false, false }; int arena_retry[2] = { 0, 0 }, arena_node = -1;      /* arena_node: the NUMA node a probe found best (a box of round 6 reported the GPU on node 0 and copied at 30 GB/s into node 0, 56 into node 1) */ bool dl_ready = false, dl_pending[2] = { false, false };
 	uint32_t wgt_hi = 0xffffffffu, wgt_lo = 0xffffffffu, wgt_max = 0xffffffffu;      // (wgt_max: the largest k_mer_hit::cnt the pass's weight table can give)
 	double t_evsync = 0, t_enq = 0, t_alloc = 0, t_s1 = 0, t_s2 = 0, t_s3 = 0, t_run = 0, t_pre = 0; uint64_t t_n = 0, t_nrun = 0;      // host-side time spent in the delivery plumbing (HAO_DBG_PRINT=dl)
+	uint64_t ed_unres = 0;      // HAO_DELIVER_ED in reference placement: windows of the batch whose start resolved to no cigar entry
 	DevBuf<uint64_t> ed_nwin, ed_wbase, ed_wcnt, ed_woff; DevBuf<hao_ed_pair> ed_pairs; uint64_t ed_n = 0;      // HAO_DELIVER_ED scratch (compute stream only: not per output set); ed_n = pairs of the batch
 	hao_ed_delivery_t ed_dl[2] = {};      // the ED view of each slot (window 0: the slot's batch did not ask for HAO_DELIVER_ED)
 	uint64_t tr_n = 0, tr_ncig = 0; hao_trace_delivery_t tr_dl[2] = {}; bool tr_on[2] = { false, false };      // HAO_DELIVER_TRACE: traced pairs and cigar entries of the batch; the view of each slot (tr_on: the slot's batch asked for it)
@@ -201,28 +203,108 @@ static int hao_ed_grid_run(hao_ctx *c, uint32_t wl, uint32_t thre, uint64_t *n_t
 	DevBuf<uint64_t> &cnt = c->al_path, off; HIP_TRY(cnt.reserve(W + 2)); HIP_TRY(off.reserve(W + 2));
 	HIP_TRY(hipMemsetAsync(cnt.p + W, 0, 8, c->stream));
 	const dim3 g_((unsigned)((n + 3) / 4)), b_(256);
-	hipLaunchKernelGGL((ed_grid_kernel<ED_GRID_COUNT>), g_, b_, 0, c->stream, B.O().ol_out.p, B.O().fin_off.p, c->d_len.p, B.lo, n, wl, thre, nword, wbase.p, cnt.p, (hao_ed_task_t*)nullptr, (hao_ed_pair*)nullptr); HAO_CHECK_LAUNCH();
+	hipLaunchKernelGGL((ed_grid_kernel<ED_GRID_COUNT>), g_, b_, 0, c->stream, B.O().ol_out.p, B.O().fin_off.p, c->d_len.p, B.lo, n, wl, thre, nword, wbase.p, cnt.p, (hao_ed_task_t*)nullptr, (hao_ed_pair*)nullptr, hao_ref_args{nullptr, nullptr, nullptr}); HAO_CHECK_LAUNCH();
 	if (int rc = hao_excl_scan_u64(c, cnt.p, off.p, W + 1)) return rc;
 	uint64_t T = 0; HIP_TRY(hipMemcpyAsync(&T, off.p + W, 8, hipMemcpyDeviceToHost, c->stream)); HIP_TRY(hipStreamSynchronize(c->stream));
 	if (T >= (1ULL << 32)) { hao_set_err(c, "hao_window_ed_grid: more than 2^32 pairs in one batch"); return HAO_EUNSUPP; }
 	HIP_TRY(c->al_task.reserve(T + 1));
-	if (T) { hipLaunchKernelGGL((ed_grid_kernel<ED_GRID_TASKS>), g_, b_, 0, c->stream, B.O().ol_out.p, B.O().fin_off.p, c->d_len.p, B.lo, n, wl, thre, nword, wbase.p, off.p, c->al_task.p, (hao_ed_pair*)nullptr); HAO_CHECK_LAUNCH(); }
+	if (T) { hipLaunchKernelGGL((ed_grid_kernel<ED_GRID_TASKS>), g_, b_, 0, c->stream, B.O().ol_out.p, B.O().fin_off.p, c->d_len.p, B.lo, n, wl, thre, nword, wbase.p, off.p, c->al_task.p, (hao_ed_pair*)nullptr, hao_ref_args{nullptr, nullptr, nullptr}); HAO_CHECK_LAUNCH(); }
 	HIP_TRY(hipStreamSynchronize(c->stream));      // (off is a local buffer)
 	off.release();
 	*n_tasks = T; c->al_grid_n = T;
 	return T ? hao_al_ed_resident(c, T, nword) : HAO_OK;
 }
 
+// ---- reference placement (hao_grid_pair.cuh: hao_ref_pair; hao_grid.cuh: the kernels) ----
+// the front of a reference-placed stage over the current batch's final ol->list: covered windows per overlap and their scan (the CSR of the shifts), one peek
+// at their total, the shifts (ed_ref_shift_kernel), the CSR slots' error bytes preset to "none".  tab = the threshold table on the device.
+static int hao_ed_ref_front(hao_ctx *c, uint32_t wl, const uint8_t *tab, hao_ref_args *A, uint64_t *n_slots)
+{
+	hao_ctx::Batch &B = *c->batch; hao_ctx::Batch::OutSet &O = B.O(); hao_ctx::RefGrid &G = c->rf; const uint64_t m = B.n_ol;
+	HIP_TRY(G.cnt.reserve(m + 2)); HIP_TRY(G.woff.reserve(m + 2)); HIP_TRY(G.ctr.reserve(2));
+	HIP_TRY(hipMemsetAsync(G.ctr.p, 0, 8, c->stream));
+	hipLaunchKernelGGL(ed_ref_nwin_kernel, dim3((unsigned)((m + 256) / 256)), dim3(256), 0, c->stream, O.ol_out.p, m, wl, G.cnt.p); HAO_CHECK_LAUNCH();
+	if (int rc = hao_excl_scan_u64(c, G.cnt.p, G.woff.p, m + 1)) return rc;
+	hipLaunchKernelGGL(hao_peek_kernel, dim3(1), dim3(64), 0, c->stream, (const unsigned long long*)(G.woff.p + m), 1, c->peek_d + 37); HAO_CHECK_LAUNCH();
+	HIP_TRY(hipStreamSynchronize(c->stream));
+	const uint64_t Wc = c->peek_h[37];
+	HIP_TRY(G.shift.reserve(Wc + 1)); HIP_TRY(G.werr.reserve(Wc + 1));
+	if (Wc) HIP_TRY(hipMemsetAsync(G.werr.p, 0xff, Wc, c->stream));
+	hipLaunchKernelGGL(ed_ref_shift_kernel, dim3((unsigned)((m * 16 + 255) / 256)), dim3(256), 0, c->stream, O.ol_out.p, m, O.fc_out.p, O.fc_out_off.p, wl, G.woff.p, G.shift.p, G.ctr.p); HAO_CHECK_LAUNCH();
+	A->win_off = G.woff.p; A->shift = G.shift.p; A->tab = tab; *n_slots = Wc;
+	return HAO_OK;
+}
+static bool hao_ed_ref_args_ok(uint32_t wl, double e_rate) { return wl != 0 && (uint64_t)wl + 62 < 65535 && e_rate > 0 && e_rate < 1; }
+static int hao_ed_ref_upload(hao_ctx *c, uint32_t wl, double e_rate, DevBuf<uint8_t> &tab)
+{
+	std::vector<uint8_t> h((size_t)wl + 1); hao_ref_thre_table(wl, e_rate, h.data());
+	HIP_TRY(tab.reserve((size_t)wl + 1));
+	HIP_TRY(hipMemcpy(tab.p, h.data(), (size_t)wl + 1, hipMemcpyHostToDevice));
+	return HAO_OK;
+}
+
+// hao_window_ed_ref: hao_ed_grid_run in reference placement - tasks into c->al_task, results into c->al_res (hao_fetch_ed_grid serves them), plus the pair list,
+// the per-overlap summaries (c->rf_sum) and the count of unresolved windows
+static int hao_ed_ref_run(hao_ctx *c, uint32_t wl, double e_rate, uint64_t *n_tasks, uint64_t *unresolved)
+{
+	hao_ctx::Batch &B = *c->batch; *n_tasks = 0; if (unresolved) *unresolved = 0; c->al_grid_n = 0; c->rf_valid = false; c->rf_hvalid = false; c->rf_unres = 0;
+	if (hao_is_sharded(c)) { hao_set_err(c, "hao_window_ed_ref needs the bases of both reads: single-device mode only"); return HAO_EUNSUPP; }
+	if (!hao_ed_ref_args_ok(wl, e_rate)) { hao_set_err(c, "hao_window_ed_ref: window length 0, window + 62 beyond 16 bits, or e_rate outside (0, 1)"); return HAO_EINVAL; }
+	const uint64_t n = B.n;
+	if (n == 0 || B.n_ol == 0) { c->rf_valid = true; return HAO_OK; }
+	if (B.n_ol >= (1ULL << 32)) { hao_set_err(c, "hao_window_ed_ref: more than 2^32 overlaps in one batch"); return HAO_EUNSUPP; }
+	if (c->rf_tab_wl != wl || c->rf_tab_erate != e_rate) { c->rf_tab_wl = 0; if (int rc = hao_ed_ref_upload(c, wl, e_rate, c->rf_tab)) return rc; c->rf_tab_wl = wl; c->rf_tab_erate = e_rate; }
+	hao_ctx::Batch::OutSet &O = B.O();
+	hao_ref_args A; uint64_t Wc = 0;
+	if (int rc = hao_ed_ref_front(c, wl, c->rf_tab.p, &A, &Wc)) return rc;
+	DevBuf<uint64_t> &nwin = c->al_k1, &wbase = c->al_k2;
+	HIP_TRY(nwin.reserve(n + 2)); HIP_TRY(wbase.reserve(n + 2));
+	hipLaunchKernelGGL(ed_grid_nwin_kernel, dim3((unsigned)((n + 256) / 256)), dim3(256), 0, c->stream, c->d_len.p, B.lo, n, wl, nwin.p); HAO_CHECK_LAUNCH();
+	if (int rc = hao_excl_scan_u64(c, nwin.p, wbase.p, n + 1)) return rc;
+	uint64_t W = 0; HIP_TRY(hipMemcpyAsync(&W, wbase.p + n, 8, hipMemcpyDeviceToHost, c->stream)); HIP_TRY(hipStreamSynchronize(c->stream));
+	DevBuf<uint64_t> &cnt = c->al_path, off; HIP_TRY(cnt.reserve(W + 2)); HIP_TRY(off.reserve(W + 2));
+	HIP_TRY(hipMemsetAsync(cnt.p + W, 0, 8, c->stream));
+	const dim3 g_((unsigned)((n + 3) / 4)), b_(256);
+	hipLaunchKernelGGL((ed_grid_kernel<ED_GRID_COUNT, HAO_PLACE_REF>), g_, b_, 0, c->stream, O.ol_out.p, O.fin_off.p, c->d_len.p, B.lo, n, wl, 0u, 1u, wbase.p, cnt.p, (hao_ed_task_t*)nullptr, (hao_ed_pair*)nullptr, A); HAO_CHECK_LAUNCH();
+	if (int rc = hao_excl_scan_u64(c, cnt.p, off.p, W + 1)) { off.release(); return rc; }
+	uint64_t T = 0, UR = 0;
+	hipError_t e1 = hipMemcpyAsync(&T, off.p + W, 8, hipMemcpyDeviceToHost, c->stream), e2 = hipMemcpyAsync(&UR, c->rf.ctr.p, 8, hipMemcpyDeviceToHost, c->stream), e3 = hipStreamSynchronize(c->stream);
+	if (e1 != hipSuccess || e2 != hipSuccess || e3 != hipSuccess) { off.release(); HIP_TRY(e1); HIP_TRY(e2); HIP_TRY(e3); }
+	if (T >= (1ULL << 32)) { off.release(); hao_set_err(c, "hao_window_ed_ref: more than 2^32 pairs in one batch"); return HAO_EUNSUPP; }
+	hipError_t e4 = c->al_task.reserve(T + 1), e5 = c->rf.pairs.reserve(T + 1), e6 = c->rf_sum.reserve(B.n_ol + 1);
+	if (e4 != hipSuccess || e5 != hipSuccess || e6 != hipSuccess) { off.release(); HIP_TRY(e4); HIP_TRY(e5); HIP_TRY(e6); }
+	if (T) {
+		hipLaunchKernelGGL((ed_grid_kernel<ED_GRID_TASKS, HAO_PLACE_REF>), g_, b_, 0, c->stream, O.ol_out.p, O.fin_off.p, c->d_len.p, B.lo, n, wl, 0u, 1u, wbase.p, off.p, c->al_task.p, c->rf.pairs.p, A);      // (tasks and pair list in one pass)
+	}
+	// (not HAO_CHECK_LAUNCH as elsewhere: `off` is a local buffer the fill kernel reads, so launch error and synchronisation are collected first, `off` is
+	// released, and only then does an error return)
+	const hipError_t e7 = hipGetLastError(), e8 = hipStreamSynchronize(c->stream);
+	off.release();
+	HIP_TRY(e7); HIP_TRY(e8);
+	*n_tasks = T; c->al_grid_n = T; c->rf_unres = UR; if (unresolved) *unresolved = UR;
+	if (T) {
+		if (int rc = hao_al_ed_resident(c, T, 1)) return rc;
+		hipLaunchKernelGGL(ed_ref_scatter_kernel, dim3((unsigned)((T + 255) / 256)), dim3(256), 0, c->stream, O.ol_out.p, c->rf.pairs.p, c->al_res.p, T, wl, A.win_off, c->rf.werr.p); HAO_CHECK_LAUNCH();
+	}
+	hipLaunchKernelGGL(ed_ref_summary_kernel, dim3((unsigned)((B.n_ol + 255) / 256)), dim3(256), 0, c->stream, O.ol_out.p, B.n_ol, wl, A.win_off, c->rf.werr.p, c->rf_sum.p); HAO_CHECK_LAUNCH();
+	c->rf_valid = true;
+	return HAO_OK;
+}
+
 // HAO_DELIVER_ED (hao_overlap_batch_async): the grid pairs of the current batch's final ol->list (hao_deliver_ed_config's window and threshold) aligned on the
 // compute stream into the output set's compact records (hao_ed_deliver.cuh), so that they travel with the batch.  Scratch and results are the batch's own: the
 // blocking path's task / result buffers (c->al_*) are not touched.  Windows per read (from the host's copy of the lengths: no device round trip), pairs per
 // window (ed_grid_kernel), a scan, the per-read offsets, one peek at the total, the pair list (8 bytes a pair), one alignment launch.
-int hao_al_ed_deliver(hao_ctx *c, const hao_ovlp_t *ol, const hao_ed_pair *pairs, uint64_t n, uint32_t wl, uint32_t thre, uint8_t *err, uint16_t *pe);      // (hao_f3.hip)
+int hao_al_ed_deliver(hao_ctx *c, const hao_ovlp_t *ol, const hao_ed_pair *pairs, uint64_t n, uint32_t wl, uint32_t thre, uint8_t *err, uint16_t *pe,
+		int place = HAO_PLACE_DIAG, hao_ref_args A = hao_ref_args{nullptr, nullptr, nullptr}, uint8_t *werr = nullptr);      // (hao_f3.hip)
 static int hao_ed_deliver_run(hao_ctx *c)
 {
 	hao_ctx::Batch &B = *c->batch; hao_ctx::Batch::OutSet &O = B.O(); const uint64_t n = B.n;
 	const uint32_t wl = c->ded_window, thre = c->ded_thre, nword = (2 * thre + 1 + 63) / 64;
-	B.ed_n = 0;
+	B.ed_n = 0; B.ed_unres = 0;
+	// reference placement (hao_deliver_ed_config_ref): the shifts first (their own pass), then the same counting / scan / fill with hao_ref_pair, the alignment
+	// kernel's reference instance, and the per-overlap summaries into the output set.  A batch in diagonal placement runs none of it.
+	const bool ref = c->ded_place == HAO_PLACE_REF; hao_ref_args A{nullptr, nullptr, nullptr};
 	c->timer.mark("q_totals");      // (labels what ran since q_final - the totals' read-back and, with HAO_DELIVER_EXACT, the exact check - so that ed_grid / ed_align time the ED stage alone)
 	if (B.n_ol >= (1ULL << 32)) { hao_set_err(c, "HAO_DELIVER_ED: more than 2^32 overlaps in one batch"); return HAO_EUNSUPP; }
 	uint64_t W = 0;
@@ -232,7 +314,14 @@ static int hao_ed_deliver_run(hao_ctx *c)
 	if (int rc = hao_excl_scan_u64(c, B.ed_nwin.p, B.ed_wbase.p, n + 1)) return rc;
 	HIP_TRY(hipMemsetAsync(B.ed_wcnt.p + W, 0, 8, c->stream));
 	const dim3 g_((unsigned)((n + 3) / 4)), b_(256);
-	hipLaunchKernelGGL((ed_grid_kernel<ED_GRID_COUNT>), g_, b_, 0, c->stream, O.ol_out.p, O.fin_off.p, c->d_len.p, B.lo, n, wl, thre, nword, B.ed_wbase.p, B.ed_wcnt.p, (hao_ed_task_t*)nullptr, (hao_ed_pair*)nullptr); HAO_CHECK_LAUNCH();
+	if (ref) {
+		uint64_t Wc = 0; HIP_TRY(O.ed_sum.reserve(B.n_ol + 1));
+		if (B.n_ol) { if (int rc = hao_ed_ref_front(c, wl, c->ded_tab.p, &A, &Wc)) return rc; }
+		hipLaunchKernelGGL((ed_grid_kernel<ED_GRID_COUNT, HAO_PLACE_REF>), g_, b_, 0, c->stream, O.ol_out.p, O.fin_off.p, c->d_len.p, B.lo, n, wl, thre, nword, B.ed_wbase.p, B.ed_wcnt.p, (hao_ed_task_t*)nullptr, (hao_ed_pair*)nullptr, A); HAO_CHECK_LAUNCH();
+		if (B.n_ol) { hipLaunchKernelGGL(hao_peek_kernel, dim3(1), dim3(64), 0, c->stream, (const unsigned long long*)c->rf.ctr.p, 1, c->peek_d + 38); HAO_CHECK_LAUNCH(); } else c->peek_h[38] = 0;
+	} else {
+	hipLaunchKernelGGL((ed_grid_kernel<ED_GRID_COUNT>), g_, b_, 0, c->stream, O.ol_out.p, O.fin_off.p, c->d_len.p, B.lo, n, wl, thre, nword, B.ed_wbase.p, B.ed_wcnt.p, (hao_ed_task_t*)nullptr, (hao_ed_pair*)nullptr, hao_ref_args{nullptr, nullptr, nullptr}); HAO_CHECK_LAUNCH();
+	}
 	if (int rc = hao_excl_scan_u64(c, B.ed_wcnt.p, B.ed_woff.p, W + 1)) return rc;
 	hipLaunchKernelGGL(ed_read_off_kernel, dim3((unsigned)((n + 256) / 256)), dim3(256), 0, c->stream, B.ed_wbase.p, B.ed_woff.p, n, O.ed_off.p); HAO_CHECK_LAUNCH();
 	// the total through mapped host memory, not a copy: a device-to-host copy would queue behind the previous batch's delivery on the DMA engine (hao_peek_kernel)
@@ -241,7 +330,17 @@ static int hao_ed_deliver_run(hao_ctx *c)
 	const uint64_t T = c->peek_h[32];
 	if (T >= (1ULL << 32)) { hao_set_err(c, "HAO_DELIVER_ED: more than 2^32 pairs in one batch"); return HAO_EUNSUPP; }
 	HIP_TRY(B.ed_pairs.reserve(T + 1)); HIP_TRY(O.ed_err.reserve(T + 64)); HIP_TRY(O.ed_pe.reserve(T + 64));
-	if (T) { hipLaunchKernelGGL((ed_grid_kernel<ED_GRID_PAIRS>), g_, b_, 0, c->stream, O.ol_out.p, O.fin_off.p, c->d_len.p, B.lo, n, wl, thre, nword, B.ed_wbase.p, B.ed_woff.p, (hao_ed_task_t*)nullptr, B.ed_pairs.p); HAO_CHECK_LAUNCH(); }
+	if (ref) {
+		B.ed_unres = c->peek_h[38];
+		if (T) { hipLaunchKernelGGL((ed_grid_kernel<ED_GRID_PAIRS, HAO_PLACE_REF>), g_, b_, 0, c->stream, O.ol_out.p, O.fin_off.p, c->d_len.p, B.lo, n, wl, thre, nword, B.ed_wbase.p, B.ed_woff.p, (hao_ed_task_t*)nullptr, B.ed_pairs.p, A); HAO_CHECK_LAUNCH(); }
+		c->timer.mark("ed_grid");
+		if (T) { if (int rc = hao_al_ed_deliver(c, O.ol_out.p, B.ed_pairs.p, T, wl, thre, O.ed_err.p, O.ed_pe.p, HAO_PLACE_REF, A, c->rf.werr.p)) return rc; }
+		if (B.n_ol) { hipLaunchKernelGGL(ed_ref_summary_kernel, dim3((unsigned)((B.n_ol + 255) / 256)), dim3(256), 0, c->stream, O.ol_out.p, B.n_ol, wl, A.win_off, c->rf.werr.p, O.ed_sum.p); HAO_CHECK_LAUNCH(); }
+		c->timer.mark("ed_align");
+		B.ed_n = T;
+		return HAO_OK;
+	}
+	if (T) { hipLaunchKernelGGL((ed_grid_kernel<ED_GRID_PAIRS>), g_, b_, 0, c->stream, O.ol_out.p, O.fin_off.p, c->d_len.p, B.lo, n, wl, thre, nword, B.ed_wbase.p, B.ed_woff.p, (hao_ed_task_t*)nullptr, B.ed_pairs.p, hao_ref_args{nullptr, nullptr, nullptr}); HAO_CHECK_LAUNCH(); }
 	c->timer.mark("ed_grid");
 	if (T) { if (int rc = hao_al_ed_deliver(c, O.ol_out.p, B.ed_pairs.p, T, wl, thre, O.ed_err.p, O.ed_pe.p)) return rc; }
 	c->timer.mark("ed_align");
@@ -289,14 +388,14 @@ static int hao_trace_grid_run(hao_ctx *c, uint32_t wl, uint32_t thre, uint64_t o
 	if (int rc = hao_excl_scan_u64(c, B.ed_nwin.p, B.ed_wbase.p, n + 1)) return rc;
 	HIP_TRY(hipMemsetAsync(B.ed_wcnt.p + W, 0, 8, c->stream));
 	const dim3 g_((unsigned)((n + 3) / 4)), b_(256);
-	hipLaunchKernelGGL((ed_grid_kernel<ED_GRID_COUNT>), g_, b_, 0, c->stream, O.ol_out.p, O.fin_off.p, c->d_len.p, B.lo, n, wl, thre, nword, B.ed_wbase.p, B.ed_wcnt.p, (hao_ed_task_t*)nullptr, (hao_ed_pair*)nullptr); HAO_CHECK_LAUNCH();
+	hipLaunchKernelGGL((ed_grid_kernel<ED_GRID_COUNT>), g_, b_, 0, c->stream, O.ol_out.p, O.fin_off.p, c->d_len.p, B.lo, n, wl, thre, nword, B.ed_wbase.p, B.ed_wcnt.p, (hao_ed_task_t*)nullptr, (hao_ed_pair*)nullptr, hao_ref_args{nullptr, nullptr, nullptr}); HAO_CHECK_LAUNCH();
 	if (int rc = hao_excl_scan_u64(c, B.ed_wcnt.p, B.ed_woff.p, W + 1)) return rc;
 	hipLaunchKernelGGL(hao_peek_kernel, dim3(1), dim3(64), 0, c->stream, (const unsigned long long*)(B.ed_woff.p + W), 1, c->peek_d + 32); HAO_CHECK_LAUNCH();
 	HIP_TRY(hipStreamSynchronize(c->stream));
 	const uint64_t T = c->peek_h[32];
 	if (T >= (1ULL << 32)) { hao_set_err(c, "hao_window_trace_grid: more than 2^32 pairs in one batch"); return HAO_EUNSUPP; }
 	HIP_TRY(c->tg_pairs.reserve(T + 1)); HIP_TRY(c->tg_err.reserve(T + 64)); HIP_TRY(c->tg_pe.reserve(T + 64)); HIP_TRY(c->tg_ps.reserve(T + 64)); HIP_TRY(c->tg_ncig16.reserve(T + 64));
-	if (T) { hipLaunchKernelGGL((ed_grid_kernel<ED_GRID_PAIRS>), g_, b_, 0, c->stream, O.ol_out.p, O.fin_off.p, c->d_len.p, B.lo, n, wl, thre, nword, B.ed_wbase.p, B.ed_woff.p, (hao_ed_task_t*)nullptr, c->tg_pairs.p); HAO_CHECK_LAUNCH(); }
+	if (T) { hipLaunchKernelGGL((ed_grid_kernel<ED_GRID_PAIRS>), g_, b_, 0, c->stream, O.ol_out.p, O.fin_off.p, c->d_len.p, B.lo, n, wl, thre, nword, B.ed_wbase.p, B.ed_woff.p, (hao_ed_task_t*)nullptr, c->tg_pairs.p, hao_ref_args{nullptr, nullptr, nullptr}); HAO_CHECK_LAUNCH(); }
 	c->timer.mark("ed_grid");
 	if (T) { if (int rc = hao_al_ed_deliver(c, O.ol_out.p, c->tg_pairs.p, T, wl, thre, c->tg_err.p, c->tg_pe.p)) return rc; }
 	c->timer.mark("ed_align");
@@ -321,7 +420,8 @@ static int hao_deliver_enqueue(hao_ctx *c)
 	const uint64_t nr4_ = cl ? nw_ / 4 + 1 : 0;      // rank directory entries on the wire: one per 256 positions
 	size_t o_rank = o_bits + (cl ? al(nw_ * 8) : 0), o_codes = o_rank + (cl ? al(nr4_ * 4) : 0), o_exc = o_codes + (cl ? al(B.n_codes) : 0);
 	size_t o_ex = o_exc + (cl ? al(B.n_exc * sizeof(hao_exc_t)) : 0), o_edoff = o_ex + (ex ? al(B.n_ol) : 0);
-	size_t o_ederr = o_edoff + (ed ? al((n + 1) * 8) : 0), o_edpe = o_ederr + (ed ? al(B.ed_n) : 0), o_troff = o_edpe + (ed ? al(B.ed_n * 2) : 0);      // (without HAO_DELIVER_ED: o_troff = o_edoff, the layout of before)
+	const bool edref = ed && B.ed_dl[s].placement == HAO_PLACE_REF;      // (reference placement: the per-overlap summaries travel after the pairs' records)
+	size_t o_ederr = o_edoff + (ed ? al((n + 1) * 8) : 0), o_edpe = o_ederr + (ed ? al(B.ed_n) : 0), o_edsum = o_edpe + (ed ? al(B.ed_n * 2) : 0), o_troff = o_edsum + (edref ? al(B.n_ol * sizeof(hao_ed_ovlp_sum)) : 0);      // (without HAO_DELIVER_ED: o_troff = o_edoff, the layout of before; in diagonal placement o_troff = o_edsum)
 	size_t o_trps = o_troff + (tr ? al((n + 1) * 8) : 0), o_trnc = o_trps + (tr ? al(B.ed_n * 2) : 0), o_trcig = o_trnc + (tr ? al(B.ed_n * 2) : 0), total = o_trcig + (tr ? al(B.tr_ncig * 2) : 0);      // (without HAO_DELIVER_TRACE: total = o_troff)
 	if (total > B.arena_cap[s] || B.arena_bad[s]) {
 		const bool redo_ = B.arena_bad[s]; B.arena_bad[s] = false;      // (hao_deliver_wait saw this slot's last batch copied at less than 40 GB/s: the probe below tries every NUMA node)
@@ -412,6 +512,7 @@ static int hao_deliver_enqueue(hao_ctx *c)
 		hao_ed_delivery_t &e = B.ed_dl[s];
 		e.n_pairs = B.ed_n; e.ed_off = (const uint64_t*)(a + o_edoff); e.err = a + o_ederr; e.pe = (const uint16_t*)(a + o_edpe);
 		d.bytes += (n + 1) * 8 + B.ed_n * 3;
+		if (edref) { HIP_TRY(cp(o_edsum, O.ed_sum.p, B.n_ol * sizeof(hao_ed_ovlp_sum))); e.ovlp = (const hao_ed_ovlp_t*)(a + o_edsum); e.unresolved = B.ed_unres; d.bytes += B.n_ol * sizeof(hao_ed_ovlp_sum); }
 	}
 	if (tr && n) {
 		HIP_TRY(cp(o_troff, O.tr_off.p, (n + 1) * 8)); HIP_TRY(cp(o_trps, O.tr_ps.p, B.ed_n * 2)); HIP_TRY(cp(o_trnc, O.tr_ncig.p, B.ed_n * 2));
@@ -444,7 +545,7 @@ static int hao_overlap_run(hao_ctx *c, uint64_t lo, uint64_t hi, const hao_pass_
 	if (!c->has_pt) { hao_set_err(c, "hao_pt_gen must run before hao_overlap_batch"); return HAO_EINVAL; }
 	if (!c->batch) c->batch = new hao_ctx::Batch();
 	hao_ctx::Batch &B = *c->batch; const double t_run0 = hao_now();
-	c->al_grid_n = 0; c->tg_valid = false;      // (the window-alignment grid of the previous batch's overlaps is stale)
+	c->al_grid_n = 0; c->tg_valid = false; c->rf_valid = false;      // (the window-alignment grid of the previous batch's overlaps is stale)
 	B.valid = false; B.host_valid = false; B.cl_valid = false; B.exact_valid = false; B.h_exact.clear(); B.lo = lo; B.n = hi - lo; B.dl_parts = parts; B.n_exc = 0;
 	const uint64_t n = B.n;
 	if (parts) {
@@ -455,7 +556,7 @@ static int hao_overlap_run(hao_ctx *c, uint64_t lo, uint64_t hi, const hao_pass_
 	// the output set about to be written may still be feeding a copy (its previous async batch): wait for that copy, never for the other slot's
 	if (B.dl_ready && B.dl_pending[B.cur]) { const double t0_ = hao_now(); HIP_TRY(hipEventSynchronize(B.ev_done[B.cur])); B.dl_pending[B.cur] = false; B.t_evsync += hao_now() - t0_; }
 	if (parts) { memset(&B.dl[B.cur], 0, sizeof(hao_delivery_t)); B.dl[B.cur].rid_lo = lo; B.dl[B.cur].n_reads = n;
-		memset(&B.ed_dl[B.cur], 0, sizeof(hao_ed_delivery_t)); if (parts & HAO_DELIVER_ED) { B.ed_dl[B.cur].window = c->ded_window; B.ed_dl[B.cur].thre = c->ded_thre; }
+		memset(&B.ed_dl[B.cur], 0, sizeof(hao_ed_delivery_t)); if (parts & HAO_DELIVER_ED) { B.ed_dl[B.cur].window = c->ded_window; B.ed_dl[B.cur].thre = c->ded_thre; B.ed_dl[B.cur].placement = c->ded_place; B.ed_dl[B.cur].e_rate = c->ded_place == HAO_PLACE_REF ? c->ded_erate : 0; }
 		memset(&B.tr_dl[B.cur], 0, sizeof(hao_trace_delivery_t)); B.tr_on[B.cur] = (parts & HAO_DELIVER_TRACE) != 0; }
 	if (n == 0) { B.n_anchor = B.n_groups = B.n_chains = B.n_cl = B.n_ol = B.n_fc = B.n_fcw = B.n_mz = 0; B.valid = true; return HAO_OK; }      // (an empty delivery: nothing to copy, the view stays zeroed)
 	// minimizer range of the batch (host knows the per-read offsets? keep a host copy once)

@@ -15,6 +15,7 @@ static void hao_release_all(hao_ctx *c)
 	c->w_lkv2.release(); c->w_s40_list.release(); c->w_s40_o.release(); c->w_s40_x.release(); c->w_s40_cnt.release(); c->d_ix_lk.release(); c->w_runid.release(); c->d_ix_mz_x.release(); c->d_ix_mz_info.release(); c->d_ix_mz_off.release(); c->d_ix_sx.release(); c->d_ix_sinfo.release();
 	c->d_ix_keys.release(); c->d_ix_start.release(); c->d_ix_cnt.release(); c->d_ix_bucket.release();
 	c->al_task.release(); c->al_k1.release(); c->al_k2.release(); c->al_path.release(); c->al_i1.release(); c->al_order.release(); c->al_sel.release(); c->al_res.release(); c->al_tres.release(); c->al_want.release(); c->al_cig.release();
+	c->rf.release(); c->ded_tab.release(); c->rf_tab.release(); c->rf_sum.release(); c->rf_valid = false;
 	c->tg.release(); c->tg_pairs.release(); c->tg_err.release(); c->tg_pe.release(); c->tg_ps.release(); c->tg_ncig16.release(); c->tg_cig.release(); c->tg_valid = false;
 }
 
@@ -137,6 +138,7 @@ int hao_overlap_batch_async(hao_ctx *c, uint64_t rid_lo, uint64_t rid_hi, const 
 		if (!(parts & HAO_DELIVER_OL)) { hao_set_err(c, "HAO_DELIVER_ED needs HAO_DELIVER_OL: the decoder rebuilds the pairs from the delivered overlaps"); return HAO_EINVAL; }
 		if (!c->ded_window) { hao_set_err(c, "HAO_DELIVER_ED before hao_deliver_ed_config"); return HAO_EINVAL; }
 	}
+	if ((parts & HAO_DELIVER_TRACE) && (parts & HAO_DELIVER_ED) && c->ded_place == HAO_PLACE_REF) { hao_set_err(c, "HAO_DELIVER_TRACE: the traced grid stage is not built in reference placement (hao_deliver_ed_config_ref)"); return HAO_EUNSUPP; }
 	if ((parts & HAO_DELIVER_TRACE) && !(parts & HAO_DELIVER_ED)) { hao_set_err(c, "HAO_DELIVER_TRACE needs HAO_DELIVER_ED: it traces the pairs the ED stage aligned"); return HAO_EINVAL; }
 	hao_pass_t ps;
 	if (!pass) { if (int rc = hao_pass_default(c, &ps)) return rc; pass = &ps; }
@@ -392,7 +394,7 @@ int hao_deliver_trace(hao_ctx *c, int slot, hao_trace_delivery_t *out)
 uint64_t hao_unpack_trace(const hao_trace_delivery_t *t, const hao_ed_delivery_t *e, const hao_delivery_t *d, const uint32_t *len, uint64_t rid,
 		hao_ed_task_t *tasks, hao_trace_result_t *res, uint64_t *cig_off, uint16_t *cigars, uint64_t cap_pairs, uint64_t cap_cigars)
 {
-	if (!t || !e || !d || !len || !t->cg_off || !e->window || !e->ed_off || rid < d->rid_lo || rid >= d->rid_lo + d->n_reads) return 0;
+	if (!t || !e || !d || !len || !t->cg_off || !e->window || e->placement != HAO_PLACE_DIAG || !e->ed_off || rid < d->rid_lo || rid >= d->rid_lo + d->n_reads) return 0;
 	const uint64_t r = rid - d->rid_lo, p0 = e->ed_off[r], np = e->ed_off[r + 1] - p0, c0 = t->cg_off[r], nc = t->cg_off[r + 1] - c0;
 	if (np > cap_pairs || nc > cap_cigars || !tasks || !res || !cig_off || !cigars) return np;
 	std::vector<hao_ed_result_t> er(np);
@@ -415,7 +417,51 @@ int hao_deliver_ed_config(hao_ctx *c, uint32_t window, uint32_t thre)
 {
 	if (!c) return HAO_EINVAL;
 	if (window == 0 || thre > HAO_ED_MAX_THRE || (uint64_t)window + 2 * (uint64_t)thre >= 0xffff) { hao_set_err(c, "hao_deliver_ed_config: window length 0, threshold beyond the widest band, or window + 2 thre beyond 16 bits"); return HAO_EINVAL; }
-	c->ded_window = window; c->ded_thre = thre;
+	c->ded_window = window; c->ded_thre = thre; c->ded_place = HAO_PLACE_DIAG; c->ded_erate = 0;
+	return HAO_OK;
+}
+
+int hao_deliver_ed_config_ref(hao_ctx *c, uint32_t window, double e_rate)
+{
+	if (!c) return HAO_EINVAL;
+	if (!hao_ed_ref_args_ok(window, e_rate)) { hao_set_err(c, "hao_deliver_ed_config_ref: window length 0, window + 62 beyond 16 bits, or e_rate outside (0, 1)"); return HAO_EINVAL; }
+	HIP_TRY(hipSetDevice(c->device));
+	HIP_TRY(hipStreamSynchronize(c->stream));      // (a batch of this context may still read the previous table)
+	if (int rc = hao_ed_ref_upload(c, window, e_rate, c->ded_tab)) return rc;
+	uint8_t full = 0; { std::vector<uint8_t> h((size_t)window + 1); hao_ref_thre_table(window, e_rate, h.data()); full = h[window]; }
+	c->ded_window = window; c->ded_thre = full; c->ded_place = HAO_PLACE_REF; c->ded_erate = e_rate;
+	return HAO_OK;
+}
+
+void hao_ref_thresholds(uint32_t window, double e_rate, uint8_t *out) { if (out) hao_ref_thre_table(window, e_rate, out); }
+
+int hao_window_ed_ref(hao_ctx *c, uint32_t window, double e_rate, uint64_t *n_tasks, uint64_t *unresolved)
+{
+	if (!c || !n_tasks || !c->batch || !c->batch->valid) return HAO_EINVAL;
+	if (int rc = hao_view_refresh(c)) return rc;
+	HIP_TRY(hipSetDevice(c->device));
+	c->timer.begin(c->stream);
+	if (int rc = hao_ed_ref_run(c, window, e_rate, n_tasks, unresolved)) return rc;
+	HIP_TRY(hipStreamSynchronize(c->stream));
+	c->timer.mark("ed_ref"); c->timer.collect(c->stage_ms);
+	return HAO_OK;
+}
+
+int hao_fetch_ed_ovlp(hao_ctx *c, uint64_t rid, const hao_ed_ovlp_t **summary, uint64_t *n)
+{
+	if (!c || !summary || !n) return HAO_EINVAL;
+	if (!c->batch || !c->batch->valid || !c->rf_valid) { hao_set_err(c, "hao_fetch_ed_ovlp: no summaries of hao_window_ed_ref are resident (a new batch has run since)"); return HAO_EINVAL; }
+	hao_ctx::Batch &B = *c->batch;
+	if (rid < B.lo || rid >= B.lo + B.n) return HAO_EINVAL;
+	HIP_TRY(hipSetDevice(c->device));
+	if (int rc = hao_batch_download(c)) return rc;
+	if (!c->rf_hvalid) {
+		c->rf_hsum.assign(B.n_ol + 1, hao_ed_ovlp_sum{0, 0, 0, 0});
+		if (B.n_ol) HIP_TRY(hipMemcpy(c->rf_hsum.data(), c->rf_sum.p, B.n_ol * sizeof(hao_ed_ovlp_sum), hipMemcpyDeviceToHost));
+		c->rf_hvalid = true;
+	}
+	const uint64_t r = rid - B.lo, s_ = B.h_fin_off[r], e_ = B.h_fin_off[r + 1];
+	*summary = (const hao_ed_ovlp_t*)(c->rf_hsum.data() + s_); *n = e_ - s_;
 	return HAO_OK;
 }
 
@@ -439,6 +485,32 @@ uint64_t hao_unpack_ed(const hao_ed_delivery_t *e, const hao_delivery_t *d, cons
 	const uint32_t wl = e->window, thre = e->thre, nword = (2 * thre + 1 + 63) / 64, nw = (uint32_t)(((uint64_t)len[rid] + wl - 1) / wl);
 	const uint64_t o0 = d->ol_off[r], o1 = d->ol_off[r + 1];
 	uint64_t k = 0;
+	if (e->placement == HAO_PLACE_REF) {
+		// reference placement: the shift of every (overlap, covered window) from the DELIVERED fake cigars (hao_unpack_cigar), then hao_ref_pair in the device's order
+		if (!d->fc_off || !d->fc || !hao_ed_ref_args_ok(wl, e->e_rate)) return UINT64_MAX;
+		std::vector<uint8_t> tab((size_t)wl + 1); hao_ref_thre_table(wl, e->e_rate, tab.data());
+		std::vector<hao_ovlp_t> zs(o1 - o0); std::vector<uint64_t> so(o1 - o0 + 1, 0); std::vector<int32_t> sh; std::vector<uint64_t> fc;
+		if (hao_unpack_overlaps(d, rid, zs.data(), zs.size()) != zs.size()) return UINT64_MAX;
+		for (uint64_t i = 0; i < zs.size(); ++i) {
+			const hao_ovlp_t &z = zs[i]; const uint32_t w0 = z.x_pos_s / wl, w1 = z.x_pos_e / wl;
+			fc.resize((size_t)z.fc_len + 1);
+			if (w1 < w0 || hao_unpack_cigar(d, o0 + i, fc.data(), z.fc_len) != z.fc_len) return UINT64_MAX;
+			for (uint32_t w = w0; w <= w1; ++w) { const int64_t g0 = (int64_t)w * wl; sh.push_back(hao_ref_shift(fc.data(), z.fc_len, g0 > (int64_t)z.x_pos_s ? g0 : (int64_t)z.x_pos_s)); }
+			so[i + 1] = sh.size();
+		}
+		for (uint32_t w = 0; w < nw; ++w)
+			for (uint64_t i = 0; i < zs.size(); ++i) {
+				const hao_ovlp_t &z = zs[i]; const uint32_t w0 = z.x_pos_s / wl;
+				hao_ed_task_t t;
+				if (w0 > w || z.x_pos_e / wl < w || !hao_ref_pair(z, w, wl, sh[so[i] + (w - w0)], tab.data(), len[z.y_id], &t)) continue;
+				if (k == np) return UINT64_MAX;
+				tasks[k] = t;
+				const uint8_t er = e->err[p0 + k]; const uint16_t pe = e->pe[p0 + k];
+				res[k].err = er == 0xff ? INT32_MAX : (int32_t)er; res[k].pe = pe == 0xffff ? -1 : (int32_t)pe;
+				++k;
+			}
+		return k == np ? np : UINT64_MAX;
+	}
 	for (uint32_t w = 0; w < nw; ++w)
 		for (uint64_t i = o0; i < o1; ++i) {
 			const hao_ovlp_wire_t &x = d->ol[i]; hao_ovlp_t z;      // (hao_unpack_overlaps' record)

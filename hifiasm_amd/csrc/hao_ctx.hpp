@@ -163,6 +163,16 @@ struct hao_ctx {
 	DevBuf<hao_ed_task_t> al_task; DevBuf<uint64_t> al_k1, al_k2, al_path; DevBuf<uint32_t> al_i1, al_order, al_sel; DevBuf<hao_ed_result_t> al_res; DevBuf<hao_trace_result_t> al_tres;
 	DevBuf<uint8_t> al_want; DevBuf<uint16_t> al_cig;
 	uint32_t ded_window = 0, ded_thre = 0;      // hao_deliver_ed_config: the grid of HAO_DELIVER_ED (window 0: not configured); per context, a view has its own
+	// reference placement (hao_grid_pair.cuh: hao_ref_pair).  ded_place / ded_erate / ded_tab: hao_deliver_ed_config_ref (the table is uploaded at configuration
+	// time: no host-to-device copy inside a batch).  rf: the stage's scratch, compute stream only (the blocking call and HAO_DELIVER_ED share it) - covered windows
+	// per overlap and their scan, the shifts, the error byte per CSR slot, the pair list, the unresolved counter; rf_tab / rf_sum / rf_*: what hao_window_ed_ref
+	// leaves for hao_fetch_ed_ovlp (rf_valid: it belongs to the current batch)
+	uint32_t ded_place = 0; double ded_erate = 0; DevBuf<uint8_t> ded_tab;
+	struct RefGrid {
+		DevBuf<uint64_t> cnt, woff; DevBuf<int16_t> shift; DevBuf<uint8_t> werr; DevBuf<hao_ed_pair> pairs; DevBuf<unsigned long long> ctr;
+		void release() { cnt.release(); woff.release(); shift.release(); werr.release(); pairs.release(); ctr.release(); }
+	} rf;
+	DevBuf<uint8_t> rf_tab; uint32_t rf_tab_wl = 0; double rf_tab_erate = 0; DevBuf<hao_ed_ovlp_sum> rf_sum; std::vector<hao_ed_ovlp_sum> rf_hsum; bool rf_valid = false, rf_hvalid = false; uint64_t rf_unres = 0;
 	// f3 with traceback on the grid (hao_trace_grid.cuh): the stage's scratch, compute stream only (hao_window_trace_grid and HAO_DELIVER_TRACE share it) -
 	// flags and selected pairs, entry counts and their scans, the compact array's offsets, the column scratch, the rows of one slice, two counters
 	struct TraceGrid {

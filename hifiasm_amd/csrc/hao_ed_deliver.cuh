@@ -8,16 +8,22 @@
 #include "hao_align.cuh"
 #include "hao_grid_pair.cuh"
 
-template<typename WT>
+// PLACE = HAO_PLACE_REF (hao_deliver_ed_config_ref): the lane rebuilds its task with hao_ref_pair from the shifts and the threshold table (A), and an
+// aligned pair also leaves its error byte in its overlap's CSR slot (werr, preset to 0xff) for the per-overlap summary (ed_ref_summary_kernel, hao_grid.cuh)
+template<typename WT, int PLACE = HAO_PLACE_DIAG>
 __global__ __launch_bounds__(256) void hao_ed_deliver_kernel(hao_ed_reads R, const hao_ovlp_t *ol, const hao_ed_pair *pairs, uint64_t n, uint32_t wl, uint32_t thre,
-		uint8_t *err, uint16_t *pe)
+		uint8_t *err, uint16_t *pe, hao_ref_args A = hao_ref_args{nullptr, nullptr, nullptr}, uint8_t *werr = nullptr)
 {
 	__shared__ uint8_t s_text[4][HAO_AL_CH];
 	const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
 	const uint64_t slot = ((uint64_t)blockIdx.x * 4 + wv) * 64 + lane;
 	hao_ed_task_t T; T.p_rid = T.p_pos = T.p_len = T.p_rev = T.t_rid = T.t_pos = T.t_len = T.t_rev = T.thre = T.abs_diag = 0;
-	bool mine = false;
-	if (slot < n) { const hao_ed_pair q = pairs[slot]; mine = hao_grid_pair(ol[q.ol], q.w, wl, thre, hao_al_nword(thre), R.len, &T); }      // (always true: the generator kept exactly these pairs)
+	bool mine = false; uint64_t ws = 0;
+	if (slot < n) {      // (always true: the generator kept exactly these pairs)
+		const hao_ed_pair q = pairs[slot];
+		if (PLACE == HAO_PLACE_DIAG) mine = hao_grid_pair(ol[q.ol], q.w, wl, thre, hao_al_nword(thre), R.len, &T);
+		else { const hao_ovlp_t z = ol[q.ol]; ws = A.win_off[q.ol] + (q.w - z.x_pos_s / wl); mine = hao_ref_pair(z, q.w, wl, A.shift[ws], A.tab, R.len[z.y_id], &T); }
+	}
 	hao_al_state<WT> S;
 	hao_al_tile_sweep<WT, HAO_AL_ED, false>(R, T, mine, S, s_text[wv], lane, (uint64_t*)nullptr, 0);
 	if (slot < n) {
@@ -26,5 +32,6 @@ __global__ __launch_bounds__(256) void hao_ed_deliver_kernel(hao_ed_reads R, con
 		// err <= thre <= 127 when there is an alignment; pe < p_len <= window + 2 thre < 65535 (hao_deliver_ed_config)
 		err[slot] = res.err == HAO_AL_NONE ? (uint8_t)0xff : (uint8_t)res.err;
 		pe[slot] = res.pe < 0 ? (uint16_t)0xffff : (uint16_t)res.pe;
+		if (PLACE == HAO_PLACE_REF && mine && res.err != HAO_AL_NONE) werr[ws] = (uint8_t)res.err;
 	}
 }

@@ -81,15 +81,17 @@ int hao_al_ed_resident(hao_ctx *c, uint64_t n, uint32_t nword)
 }
 
 // the delivery path's alignment (HAO_DELIVER_ED, hao_batch.hpp): n pairs (overlap, window) of the batch's ol->list in text order -> err[n] / pe[n] of the output set
-int hao_al_ed_deliver(hao_ctx *c, const hao_ovlp_t *ol, const hao_ed_pair *pairs, uint64_t n, uint32_t wl, uint32_t thre, uint8_t *err, uint16_t *pe)
+// (place = HAO_PLACE_REF: the pairs of reference placement - thresholds <= 31, the one-word band - with the shifts and the threshold table in A and the CSR slots' error bytes in werr)
+int hao_al_ed_deliver(hao_ctx *c, const hao_ovlp_t *ol, const hao_ed_pair *pairs, uint64_t n, uint32_t wl, uint32_t thre, uint8_t *err, uint16_t *pe, int place, hao_ref_args A, uint8_t *werr)
 {
 	const hao_ed_reads R = hao_al_reads_of(c);
 	const dim3 g_((unsigned)((n + 255) / 256)), b_(256);
 	const uint32_t nword = hao_al_nword(thre);
-	if (nword == 1) hipLaunchKernelGGL((hao_ed_deliver_kernel<uint64_t>), g_, b_, 0, c->stream, R, ol, pairs, n, wl, thre, err, pe);
-	else if (nword == 2) hipLaunchKernelGGL((hao_ed_deliver_kernel<hao_u128>), g_, b_, 0, c->stream, R, ol, pairs, n, wl, thre, err, pe);
-	else if (nword == 3) hipLaunchKernelGGL((hao_ed_deliver_kernel<hao_wide<3> >), g_, b_, 0, c->stream, R, ol, pairs, n, wl, thre, err, pe);
-	else hipLaunchKernelGGL((hao_ed_deliver_kernel<hao_wide<4> >), g_, b_, 0, c->stream, R, ol, pairs, n, wl, thre, err, pe);
+	if (place == HAO_PLACE_REF) hipLaunchKernelGGL((hao_ed_deliver_kernel<uint64_t, HAO_PLACE_REF>), g_, b_, 0, c->stream, R, ol, pairs, n, wl, thre, err, pe, A, werr);
+	else if (nword == 1) hipLaunchKernelGGL((hao_ed_deliver_kernel<uint64_t>), g_, b_, 0, c->stream, R, ol, pairs, n, wl, thre, err, pe, hao_ref_args{nullptr, nullptr, nullptr}, (uint8_t*)nullptr);
+	else if (nword == 2) hipLaunchKernelGGL((hao_ed_deliver_kernel<hao_u128>), g_, b_, 0, c->stream, R, ol, pairs, n, wl, thre, err, pe, hao_ref_args{nullptr, nullptr, nullptr}, (uint8_t*)nullptr);
+	else if (nword == 3) hipLaunchKernelGGL((hao_ed_deliver_kernel<hao_wide<3> >), g_, b_, 0, c->stream, R, ol, pairs, n, wl, thre, err, pe, hao_ref_args{nullptr, nullptr, nullptr}, (uint8_t*)nullptr);
+	else hipLaunchKernelGGL((hao_ed_deliver_kernel<hao_wide<4> >), g_, b_, 0, c->stream, R, ol, pairs, n, wl, thre, err, pe, hao_ref_args{nullptr, nullptr, nullptr}, (uint8_t*)nullptr);
 	HAO_CHECK_LAUNCH();
 	return HAO_OK;
 }

@@ -248,7 +248,7 @@ int hao_window_ed_batch(hao_ctx *c, const hao_ed_task_t *tasks, uint64_t n_tasks
  * batch's final ol->list on the reference's fixed window grid - windows of `window` query bases (WINDOW = 375, Hash_Table.h:9; Correct.cpp:5645, 5993) starting at
  * multiples of `window`, one pair per overlap and grid window it covers, the window clipped to the overlap at its ends, the pattern = the target interval on the
  * overlap's diagonal padded by thre on both sides and clipped at the read ends with abs_diag = the bases clipped at its start (the operands Correct.cpp:3897 hands to
- * ed_band_cal_semi_64_w_absent_diag, without the fake-cigar shift) - in text order (query read, grid window, position in ol->list), and the distance-only window
+ * ed_band_cal_semi_64_w_absent_diag, without the fake-cigar shift: DIAGONAL placement; hao_window_ed_ref below places them as the reference does) - in text order (query read, grid window, position in ol->list), and the distance-only window
  * alignment (hao_window_ed_batch's kernels) runs over them where they lie.  Tasks and results stay in device memory; *n_tasks = their number.
  * hao_fetch_ed_grid copies the first `cap` of them out (either pointer may be NULL).  One threshold per call (thre <= HAO_ED_MAX_THRE); single-device mode. */
 int hao_window_ed_grid(hao_ctx *c, uint32_t window, uint32_t thre, uint64_t *n_tasks);
@@ -260,8 +260,9 @@ int hao_fetch_ed_grid(hao_ctx *c, hao_ed_task_t *tasks, hao_ed_result_t *res, ui
  * the same (err, pe) - and the results cross PCIe in the batch's arena: 3 bytes per pair (an error byte, 0xff = no alignment within thre, and a 16-bit pattern
  * end, 0xffff = -1) plus the pairs' offsets per read.  Tasks do not travel: hao_unpack_ed rebuilds them from the delivered overlaps.  The blocking path's
  * task / result scratch (hao_window_ed_grid / hao_fetch_ed_grid) is not touched; batches without HAO_DELIVER_ED keep their arena layout and byte count.
- * Not covered: the fake-cigar shift of the window's target start (Correct.cpp:3897), the sharded path.  The semi-global traced mode rides along as HAO_DELIVER_TRACE
- * (below); the other traced modes stay host-fed.
+ * The pairs above are DIAGONAL placement (target start on the overlap's first diagonal, one threshold per call); hao_deliver_ed_config_ref switches the context
+ * to REFERENCE placement (below: the fake-cigar shift, per-window thresholds, init_waln).  Not covered: the sharded path.  The semi-global traced mode rides
+ * along as HAO_DELIVER_TRACE (below; diagonal placement only); the other traced modes stay host-fed.
  *   hao_deliver_ed_config: the grid of this context's HAO_DELIVER_ED batches (an attached view has its own).  window == 0, thre > HAO_ED_MAX_THRE or
  *                          window + 2 thre >= 65535 (pe travels in 16 bits): HAO_EINVAL.  Bands of two or more words leave out the pairs hao_window_ed_grid leaves out.
  *   hao_deliver_ed:        the ED view of a slot whose batch asked for HAO_DELIVER_ED, valid after hao_deliver_wait on that slot; its pointers live in the slot's
@@ -270,6 +271,31 @@ int hao_fetch_ed_grid(hao_ctx *c, hao_ed_task_t *tasks, hao_ed_result_t *res, ui
  *                          ALL reads, as given to hao_set_reads) and their results widened to hao_ed_result_t (err INT32_MAX / pe -1 without an alignment).
  *                          Returns the pair count; nothing is written when it exceeds cap (or tasks / res is NULL); 0 for a read outside the batch;
  *                          UINT64_MAX when the rebuilt pairs do not match the delivered count (len is not the batch's).  A pure function of the two views. */
+/* REFERENCE PLACEMENT of the grid pairs: the window / candidate pairs as the reference's correction pass forms them (align_hc_ed_post_extz,
+ * Correct.cpp:12951-13006, per overlap from gen_hc_r_alin :25637; the same loop in align_ul_ed_post_extz :12900 and verify_window :382-559).  The grid windows
+ * and the text order of the pairs are those of hao_window_ed_grid; what differs is
+ *   - the target start: (q_s - x_pos_s) + y_pos_s + y_start_offset(q_s, fake cigar) (Hash_Table.h:165-189) - the diagonal of the nearest chained seed before
+ *     the window, read from the overlap's own fake cigar.  A window whose start resolves to no cigar entry (the reference would exit) forms no pair and is
+ *     counted as unresolved, as is one whose shift does not fit 16 bits (0 for every cigar h_ec_lchain produces with apend_be = 1);
+ *   - the threshold: one per window from its length q_l, (int64_t)(q_l * e_rate), 0 -> 1 when q_l >= 4 (Adjust_Threshold, Correct.h:46), at most 31
+ *     (THRESHOLD_MAX_SIZE, Hash_Table.h:24): computed on the host in double as a table of window + 1 bytes (hao_ref_thresholds) that the kernels read;
+ *   - admission and clipping: init_waln (Correct.cpp:764-779).  p_pos / p_len = its r_s / r_l, abs_diag = its aux_beg.
+ * window = WINDOW_HC 775 (HiFi) / WINDOW_OHC 375 (ONT), e_rate = asm_opt.max_ov_diff_ec 0.04 / 0.07 in the reference.  window == 0, window + 62 >= 65535 or
+ * e_rate outside (0, 1): HAO_EINVAL; sharded mode: HAO_EUNSUPP.
+ *   hao_window_ed_ref:         blocking, over the last batch; tasks and results lie where hao_window_ed_grid leaves them, so hao_fetch_ed_grid serves them;
+ *                              *unresolved (may be NULL) = the batch's unresolved windows.
+ *   hao_fetch_ed_ovlp:         the per-overlap summaries of the last hao_window_ed_ref for read rid, aligned with hao_fetch_overlaps' ol: windows covered, windows
+ *                              aligned (err != INT32_MAX), the sum of their lengths - the align_length the reference's loop accumulates before its rescue step,
+ *                              what its OVERLAP_THRESHOLD_HIFI_FILTER test (simi_pass) starts from - and the sum of their errors.
+ *   hao_deliver_ed_config_ref: this context's following HAO_DELIVER_ED batches are reference-placed (hao_deliver_ed_config switches back).  The 3 bytes per pair
+ *                              and the per-read offsets travel as before, the summaries (16 bytes per overlap) after them; hao_deliver_ed's view names placement
+ *                              and e_rate, and hao_unpack_ed rebuilds a read's tasks from the delivered overlaps AND their delivered fake cigars.
+ * Not built: the traced stage in reference placement - HAO_DELIVER_TRACE on a reference-placed context returns HAO_EUNSUPP, hao_window_trace_grid has no
+ * reference-placed form, and hao_unpack_trace returns 0 for a reference-placed view (never diagonal cigars under a reference-placed configuration).  Out of scope: the reference's rescue of unaligned windows by extension from aligned neighbours and its early exit (push_hc_wlst_exz,
+ * Correct.cpp:12711-12771), which are sequential per overlap. */
+#define HAO_PLACE_DIAG 0u
+#define HAO_PLACE_REF 1u
+typedef struct { uint32_t n_win, n_aligned, aligned_bases, err_sum; } hao_ed_ovlp_t;
 #define HAO_DELIVER_ED 8u      /* window-alignment results of the batch's grid pairs (hao_deliver_ed_config, hao_deliver_ed, hao_unpack_ed) */
 typedef struct {
 	uint64_t n_pairs;           /* pairs of the batch */
@@ -277,10 +303,20 @@ typedef struct {
 	const uint64_t *ed_off;     /* [n_reads + 1]: pairs of read r = [ed_off[r], ed_off[r + 1]) */
 	const uint8_t *err;         /* [n_pairs]: edit distance, 0xff = no alignment within thre */
 	const uint16_t *pe;         /* [n_pairs]: end of the alignment on the pattern, 0xffff = -1 */
+	/* (the fields below were added with reference placement: hao_deliver_ed now writes 72 bytes, so callers built against the 40-byte struct must be rebuilt) */
+	uint32_t placement, pad;    /* HAO_PLACE_DIAG / HAO_PLACE_REF: how the batch's pairs were placed; in reference placement thre = the full window's threshold */
+	double e_rate;              /* reference placement: the e_rate of hao_deliver_ed_config_ref at the time of the batch (0 in diagonal placement) */
+	uint64_t unresolved;        /* reference placement: covered windows of the batch whose start resolved to no fake-cigar entry, or whose shift does not fit the
+	                             * 16 bits the device keeps per window (|shift| > 32767): they form no pair.  0 for every cigar h_ec_lchain produces */
+	const hao_ed_ovlp_t *ovlp;  /* reference placement: [n_ol] per-overlap summaries, aligned with the hao_delivery_t's ol; NULL in diagonal placement */
 } hao_ed_delivery_t;
 int hao_deliver_ed_config(hao_ctx *c, uint32_t window, uint32_t thre);
 int hao_deliver_ed(hao_ctx *c, int slot, hao_ed_delivery_t *out);
 uint64_t hao_unpack_ed(const hao_ed_delivery_t *e, const hao_delivery_t *d, const uint32_t *len, uint64_t rid, hao_ed_task_t *tasks, hao_ed_result_t *res, uint64_t cap);
+int hao_window_ed_ref(hao_ctx *c, uint32_t window, double e_rate, uint64_t *n_tasks, uint64_t *unresolved);
+int hao_fetch_ed_ovlp(hao_ctx *c, uint64_t rid, const hao_ed_ovlp_t **summary, uint64_t *n);
+int hao_deliver_ed_config_ref(hao_ctx *c, uint32_t window, double e_rate);
+void hao_ref_thresholds(uint32_t window, double e_rate, uint8_t *out /* [window + 1] */);     /* host code, no context */
 
 /* Second variant: global alignment inside the band WITH traceback - ed_band_cal_global_64_w_trace (Levenshtein_distance.h:3370-3442) on a
  * cleared bit_extz_t followed by gen_trace(ez, thre, 1) (:903-985), the call cal_exz_global / Correct.cpp:14537 make once a window's end points are fixed.
@@ -308,7 +344,7 @@ int hao_window_trace_batch(hao_ctx *c, int mode, const hao_ed_task_t *tasks, uin
  * domain hao_window_trace_batch accepts for HAO_ALIGN_SEMI).  A traced pair's (err, pe) is the distance-only result and (ps, ts = 0, te = t_len - 1, cigar)
  * is what hao_window_trace_batch(HAO_ALIGN_SEMI) gives for the same task; an aligned pair outside the domain (clipped at a read end) keeps its distance-only
  * (err, pe) with ps = -1 and no cigar (ALIGNED BUT UNTRACED); a pair without an alignment reads err = INT32_MAX, pe = ps = -1.  ts = 0 and te = t_len - 1 for
- * every pair.  A cigar has at most 2 thre + 3 entries (push_trace's encoding, op << 14 | len).  Not covered: the fake-cigar shift (Correct.cpp:3897), the other
+ * every pair.  A cigar has at most 2 thre + 3 entries (push_trace's encoding, op << 14 | len).  Not covered: reference placement (diagonal pairs only), the other
  * traced modes (host-fed: hao_window_trace_batch), the sharded path (HAO_EUNSUPP).  On the device, the traced sweep keeps three words per band word and text
  * column (D0, VP, VN; the walk derives HP / HN) in slices of ~4 GB, and the cigars are compacted into one array.
  *   hao_window_trace_grid: over the last batch (hao_overlap_batch[_ex]; results resident).  out[0] = grid pairs, out[1] = traced pairs, out[2] = cigar entries,

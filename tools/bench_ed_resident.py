@@ -3,7 +3,10 @@ one all-reads batch on the reference's window grid (WINDOW = 375), one threshold
 
 --deliver: the same alignment in the streaming pass (HAO_DELIVER_ED): passes of hao_overlap_batch_async batches (both slots in flight) with OL|CL and with OL|CL|ED,
 alternately; per batch the ED stage's device time (stage_times "ed_grid" + "ed_align"), its pairs/s and the arena bytes it adds; per pass the wall time of the
-delivered step.  usage: python tools/bench_ed_resident.py --deliver [--workload W] [--batch-reads N] [--max-batches K] [--thre T] [--reps R]"""
+delivered step.  usage: python tools/bench_ed_resident.py --deliver [--workload W] [--batch-reads N] [--max-batches K] [--thre T] [--reps R]
+
+--window W: the window of the diagonal grid (default 375).  --ref WINDOW,ERATE (blocking and --deliver): the same stage in REFERENCE placement (hao_window_ed_ref /
+hao_deliver_ed_config_ref: fake-cigar shift, per-window thresholds, init_waln), e.g. --ref 775,0.04 beside the diagonal stage at --window 775 and thre 31."""
 import argparse
 import json
 import os
@@ -17,18 +20,29 @@ sys.path.insert(0, ROOT)
 def main():
     from hifiasm_amd import workloads
     from hifiasm_amd.api import Engine
-    thre = int(sys.argv[1]) if len(sys.argv) > 1 else 15
-    reps = int(sys.argv[2]) if len(sys.argv) > 2 else 5
+    argv = [x for x in sys.argv[1:]]
+    ref, window = None, 375
+    for flag in ("--ref", "--window"):
+        if flag in argv:
+            i = argv.index(flag); val = argv[i + 1]; del argv[i:i + 2]
+            if flag == "--ref":
+                ref = (int(val.split(",")[0]), float(val.split(",")[1]))
+            else:
+                window = int(val)
+    thre = int(argv[0]) if len(argv) > 0 else 15
+    reps = int(argv[1]) if len(argv) > 1 else 5
     rs = workloads.workload_reads("bacterial5M_hifi30x")
     e = Engine(0); e.set_readset(rs); e.ha_ft_gen(); e.ha_pt_gen()
     e.overlap_batch(0, rs.n)
-    n = e.window_ed_grid(375, thre)      # warm-up (allocations)
+    run = (lambda: e.window_ed_ref(*ref)[0]) if ref else (lambda: e.window_ed_grid(window, thre))
+    n = run()      # warm-up (allocations)
     ts = []
     for _ in range(reps):
-        t0 = time.time(); n = e.window_ed_grid(375, thre); ts.append(time.time() - t0)
+        t0 = time.time(); n = run(); ts.append(time.time() - t0)
     t, r = e.fetch_ed_grid(min(n, 1_000_000))
     ok = int((r[:, 0] != 2**31 - 1).sum())
-    print(json.dumps({"workload": "bacterial5M_hifi30x", "reads": int(rs.n), "overlaps": e.batch_totals()["overlaps"], "window": 375, "thre": thre, "pairs": n,
+    print(json.dumps({"workload": "bacterial5M_hifi30x", "reads": int(rs.n), "overlaps": e.batch_totals()["overlaps"], "placement": "reference" if ref else "diagonal",
+                      "window": ref[0] if ref else window, "thre": None if ref else thre, "e_rate": ref[1] if ref else None, "pairs": n,
                       "ms_per_call_best": round(min(ts) * 1e3, 3), "ms_per_call_all": [round(x * 1e3, 3) for x in ts], "pairs_per_s": round(n / min(ts)),
                       "within_thre_of_first_million": ok, "what": "task generation on the device from ol->list + distance-only window alignment; nothing crosses the host but two totals"}))
     e.close()
@@ -40,7 +54,11 @@ def deliver(a):
     hi_all = workloads.n_reads_of(a.workload)
     rs = workloads.workload_reads(a.workload)
     e = Engine(0); e.set_readset(rs); e.ha_ft_gen(); e.ha_pt_gen()
-    e.deliver_ed_config(375, a.thre)
+    ref = (int(a.ref.split(",")[0]), float(a.ref.split(",")[1])) if a.ref else None
+    if ref:
+        e.deliver_ed_config_ref(*ref)
+    else:
+        e.deliver_ed_config(a.window, a.thre)
     br = a.batch_reads or (rs.n + 1) // 2
     ranges = [(lo, min(hi_all, lo + br)) for lo in range(0, rs.n, br)][:a.max_batches]
 
@@ -74,7 +92,8 @@ def deliver(a):
                             pairs_per_s_ed_stage=round(b1["pairs"] / max(1e-9, ed_ms * 1e-3)), pairs_per_s_align=round(b1["pairs"] / max(1e-9, b1["ed_align_ms"] * 1e-3)),
                             arena_bytes_ol_cl=b0["bytes"], arena_bytes_ol_cl_ed=b1["bytes"], extra_bytes=b1["bytes"] - b0["bytes"],
                             kernels_ms_ol_cl=round(b0["kernels_ms"], 3), kernels_ms_ol_cl_ed=round(b1["kernels_ms"], 3)))
-    print(json.dumps({"workload": a.workload, "reads_indexed": int(rs.n), "window": 375, "thre": a.thre, "batches": batches,
+    print(json.dumps({"workload": a.workload, "reads_indexed": int(rs.n), "placement": "reference" if ref else "diagonal", "window": ref[0] if ref else a.window,
+                      "thre": None if ref else a.thre, "e_rate": ref[1] if ref else None, "batches": batches,
                       "delivered_step_ms_ol_cl": walls["ol_cl"], "delivered_step_ms_ol_cl_ed": walls["ol_cl_ed"],
                       "delivered_step_ms_best": {k: min(v) for k, v in walls.items()},
                       "what": "passes over the listed batches with both slots in flight: host wall time per pass with OL|CL and with OL|CL|ED (alternating), the ED stage's device time per batch (stage_times), the bytes it adds to the arena"}))
@@ -90,6 +109,8 @@ if __name__ == "__main__":
         ap.add_argument("--max-batches", type=int, default=1 << 30)
         ap.add_argument("--thre", type=int, default=15)
         ap.add_argument("--reps", type=int, default=3)
+        ap.add_argument("--window", type=int, default=375)
+        ap.add_argument("--ref", default="", help="WINDOW,ERATE: reference placement")
         deliver(ap.parse_args())
     else:
         main()
