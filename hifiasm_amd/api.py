@@ -61,7 +61,12 @@ class TraceDelivery(C.Structure):
     _fields_ = [("n_traced", C.c_uint64), ("n_cigar", C.c_uint64), ("cg_off", C.c_void_p), ("ps", C.c_void_p), ("n_cig", C.c_void_p), ("cigar", C.c_void_p)]
 
 
-DELIVER_OL, DELIVER_CL, DELIVER_EXACT, DELIVER_ED, DELIVER_TRACE = 1, 2, 4, 8, 16
+class RescueDelivery(C.Structure):
+    """hao_rescue_delivery_t: the rescue stage's results of a batch delivered with HAO_DELIVER_RESCUE (pointers into the same pinned arena as its Delivery)"""
+    _fields_ = [("n_ol", C.c_uint64), ("n_wins", C.c_uint64), ("n_rescued", C.c_uint64), ("ovlp", C.c_void_p), ("win_off", C.c_void_p), ("wins", C.c_void_p)]
+
+
+DELIVER_OL, DELIVER_CL, DELIVER_EXACT, DELIVER_ED, DELIVER_TRACE, DELIVER_RESCUE = 1, 2, 4, 8, 16, 32
 PLACE_DIAG, PLACE_REF = 0, 1      # hao_ed_delivery_t::placement
 
 ABI_SYMBOLS = [
@@ -73,7 +78,51 @@ ABI_SYMBOLS = [
     "hao_deliver_ed_config", "hao_deliver_ed", "hao_unpack_ed",
     "hao_window_trace_grid", "hao_fetch_trace_grid", "hao_deliver_trace", "hao_unpack_trace",
     "hao_window_ed_ref", "hao_fetch_ed_ovlp", "hao_deliver_ed_config_ref", "hao_ref_thresholds",
+    "hao_window_rescue_ref", "hao_fetch_rescue", "hao_rescue_task", "hao_deliver_rescue", "hao_unpack_rescue",
 ]
+
+
+RESCUE_OVLP = np.dtype([("verdict", np.uint16), ("flags", np.uint16), ("exit_win", np.uint32), ("align_length", np.uint32), ("n_rescued", np.uint32)])
+RESCUE_FWD, RESCUE_BWD, RESCUE_ANCHOR, RESCUE_UNTRACED, RESCUE_NO_EXIT = 0, 1, 2, 1, 0xFFFFFFFF
+
+
+def rescue_records(raw):
+    """hao_rescue_win_t records (uint32 [m, 4]) -> int64 [m, 7]: grid window, y_start, y_end, err, thre, direction, re-placed"""
+    raw = np.asarray(raw, dtype=np.uint32).reshape(-1, 4)
+    out = np.zeros((raw.shape[0], 7), dtype=np.int64)
+    out[:, 0] = raw[:, 2]; out[:, 1] = raw[:, 0].view(np.int32) if raw.shape[0] else 0; out[:, 2] = raw[:, 1].view(np.int32) if raw.shape[0] else 0
+    info = raw[:, 3].astype(np.int64)
+    out[:, 3] = info & 0xFF; out[:, 4] = (info >> 8) & 0xFF; out[:, 5] = (info >> 16) & 3; out[:, 6] = (info >> 18) & 1
+    return out
+
+
+def unpack_rescue(d, e, r, lengths, rid):
+    """hao_unpack_rescue (host code) over the three views -> (ovlp structured array, list of int64 [m, 7] record arrays per overlap)"""
+    L = np.ascontiguousarray(lengths, dtype=np.uint32)
+    u32p, u64p = C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)
+    f = lib().hao_unpack_rescue
+    n = int(f(C.byref(d), C.byref(e), C.byref(r), L.ctypes.data_as(u32p), rid, None, None, None, 0, 0))
+    if n == 2**64 - 1:
+        raise HaoError(f"hao_unpack_rescue: read {rid}: the views do not belong together")
+    ov = np.zeros(n, dtype=RESCUE_OVLP); wo = np.zeros(n + 1, dtype=np.uint64)
+    m = 0
+    if n:
+        oo = _arr(d.ol_off + 8 * (rid - d.rid_lo), 2, np.uint64)
+        ww = _arr(r.win_off + 8 * int(oo[0]), n + 1, np.uint64)
+        m = int(ww[n] - ww[0])
+    raw = np.zeros((max(m, 1), 4), dtype=np.uint32)
+    got = int(f(C.byref(d), C.byref(e), C.byref(r), L.ctypes.data_as(u32p), rid, ov.ctypes.data_as(C.c_void_p), wo.ctypes.data_as(u64p), raw.ctypes.data_as(C.c_void_p), n, m))
+    if got != n:
+        raise HaoError(f"hao_unpack_rescue: read {rid}: {got} != {n}")
+    return ov, [rescue_records(raw[int(wo[i]):int(wo[i + 1])]) for i in range(n)]
+
+
+def rescue_task(z, win, window, toff, tab, target_len):
+    """hao_rescue_task (host code): the task (uint32 [10]) of the rescue alignment of grid window `win` of overlap z (uint32 [12]) from target offset toff, or None"""
+    z = np.ascontiguousarray(z, dtype=np.uint32); tab = np.ascontiguousarray(tab, dtype=np.uint8); out = np.zeros(10, dtype=np.uint32)
+    ok = lib().hao_rescue_task(z.ctypes.data_as(C.c_void_p), C.c_uint32(int(win)), C.c_uint32(int(window)), C.c_int64(int(toff)), tab.ctypes.data_as(C.POINTER(C.c_uint8)),
+                               C.c_uint32(int(target_len)), out.ctypes.data_as(C.c_void_p))
+    return out if ok else None
 
 
 def lib_path():
@@ -133,6 +182,12 @@ def lib():
         L.hao_window_ed_ref.argtypes = [vp, C.c_uint32, C.c_double, u64p, u64p]
         L.hao_fetch_ed_ovlp.argtypes = [vp, C.c_uint64, C.POINTER(vp), u64p]
         L.hao_deliver_ed_config_ref.argtypes = [vp, C.c_uint32, C.c_double]
+        L.hao_window_rescue_ref.argtypes = [vp, u64p]
+        L.hao_deliver_rescue.argtypes = [vp, C.c_int, C.POINTER(RescueDelivery)]
+        L.hao_unpack_rescue.argtypes = [C.POINTER(Delivery), C.POINTER(EdDelivery), C.POINTER(RescueDelivery), u32p, C.c_uint64, vp, u64p, vp, C.c_uint64, C.c_uint64]
+        L.hao_unpack_rescue.restype = C.c_uint64
+        L.hao_fetch_rescue.argtypes = [vp, C.c_uint64, C.POINTER(vp), u64p, C.POINTER(vp), C.POINTER(vp)]
+        L.hao_rescue_task.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_int64, u8p, C.c_uint32, vp]
         L.hao_ref_thresholds.argtypes = [C.c_uint32, C.c_double, u8p]; L.hao_ref_thresholds.restype = None
         L.hao_fetch_trace_grid.argtypes = [vp, vp, vp, u64p, vp, C.c_uint64, C.c_uint64]
         L.hao_deliver_trace.argtypes = [vp, C.c_int, C.POINTER(TraceDelivery)]
@@ -334,6 +389,9 @@ class Engine:
         if not hasattr(self, "_tr_slot"):
             self._tr_slot = {}
         self._tr_slot[slot.value] = bool(parts & DELIVER_TRACE)
+        if not hasattr(self, "_rs_slot"):
+            self._rs_slot = {}
+        self._rs_slot[slot.value] = bool(parts & DELIVER_RESCUE)
         return slot.value
 
     def deliver_wait(self, slot):
@@ -342,6 +400,7 @@ class Engine:
         self._ck(self.L.hao_deliver_wait(self.h, slot, C.byref(d)), "hao_deliver_wait")
         d.ed = self.deliver_ed(slot) if getattr(self, "_ed_slot", {}).get(slot) else None
         d.tr = self.deliver_trace(slot) if getattr(self, "_tr_slot", {}).get(slot) else None
+        d.rs = self.deliver_rescue(slot) if getattr(self, "_rs_slot", {}).get(slot) else None
         return d
 
     def deliver_ed_config(self, window=375, thre=15):
@@ -385,6 +444,23 @@ class Engine:
         if got != n:
             raise HaoError(f"hao_unpack_ed: read {rid}: the pairs rebuilt from the delivered overlaps do not match the delivered count (lengths of another read set?)")
         return t, r
+
+    def deliver_rescue(self, slot):
+        """the RescueDelivery view of a waited-for slot whose batch asked for DELIVER_RESCUE"""
+        r = RescueDelivery()
+        self._ck(self.L.hao_deliver_rescue(self.h, slot, C.byref(r)), "hao_deliver_rescue")
+        return r
+
+    def delivered_rescue(self, d, rid, lengths=None):
+        """(ovlp, wins) of read rid out of a Delivery with DELIVER_ED | DELIVER_RESCUE - fetch_rescue's shapes and values (hao_unpack_rescue)"""
+        r, e = getattr(d, "rs", None), getattr(d, "ed", None)
+        if r is None or e is None:
+            raise HaoError("delivered_rescue: the batch was not delivered with DELIVER_ED | DELIVER_RESCUE")
+        if lengths is None:
+            lengths = getattr(self, "lengths", None)
+        if lengths is None:
+            raise HaoError("delivered_rescue: the lengths of all reads are needed (pass lengths=)")
+        return unpack_rescue(d, e, r, lengths, rid)
 
     def deliver_trace(self, slot):
         """the TraceDelivery view of a waited-for slot whose batch asked for DELIVER_TRACE"""
@@ -492,6 +568,27 @@ class Engine:
         p, n = C.c_void_p(), C.c_uint64()
         self._ck(self.L.hao_fetch_ed_ovlp(self.h, rid, C.byref(p), C.byref(n)), "hao_fetch_ed_ovlp")
         return _arr(p.value, 4 * n.value, np.uint32).reshape(-1, 4)
+
+    def window_rescue_ref(self):
+        """hao_window_rescue_ref: the rescue of unaligned windows, the exit test and the verdict of align_hc_ed_post_extz over the batch window_ed_ref has
+        just aligned; returns the number of rescued windows.  fetch_rescue serves the per-overlap results and the window records"""
+        n = C.c_uint64()
+        self._ck(self.L.hao_window_rescue_ref(self.h, C.byref(n)), "hao_window_rescue_ref")
+        return int(n.value)
+
+    def fetch_rescue(self, rid):
+        """(ovlp, wins) of read rid after window_rescue_ref, aligned with h_ec_lchain(rid)[0]: ovlp = structured array (verdict, flags, exit_win, align_length,
+        n_rescued) per overlap; wins = one int64 [m, 7] array per overlap (grid window, y_start, y_end, err, thre, direction, re-placed) in window order"""
+        po, n, pw, pr = C.c_void_p(), C.c_uint64(), C.c_void_p(), C.c_void_p()
+        self._ck(self.L.hao_fetch_rescue(self.h, rid, C.byref(po), C.byref(n), C.byref(pw), C.byref(pr)), "hao_fetch_rescue")
+        m = int(n.value)
+        ov = _arr(po.value, m, RESCUE_OVLP)
+        wo = _arr(pw.value, m + 1, np.uint64)
+        wins = []
+        for i in range(m):
+            a, b = int(wo[i]), int(wo[i + 1])
+            wins.append(rescue_records(_arr(pr.value + 16 * a, 4 * (b - a), np.uint32).reshape(-1, 4)))
+        return ov, wins
 
     def window_trace_grid(self, window=375, thre=15):
         """hao_window_trace_grid: the last batch's grid pairs aligned with traceback where they align inside the semi-global domain;

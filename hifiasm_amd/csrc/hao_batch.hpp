@@ -30,6 +30,7 @@ struct hao_ctx::Batch {
 		DevBuf<uint8_t> exact;                                                                        // exact-overlap flags of ol_out
 		DevBuf<uint64_t> ed_off; DevBuf<uint8_t> ed_err; DevBuf<uint16_t> ed_pe;                      // HAO_DELIVER_ED: pairs per read, error byte and pattern end per pair (hao_ed_deliver.cuh)
 		DevBuf<hao_ed_ovlp_sum> ed_sum;                                                               // HAO_DELIVER_ED in reference placement: the per-overlap summaries (ed_ref_summary_kernel)
+		DevBuf<hao_rs_ovlp> rs_ovlp; DevBuf<uint64_t> rs_off; DevBuf<hao_rs_win> rs_wins;                // HAO_DELIVER_RESCUE: per-overlap results, record offsets per overlap, the records (hao_rescue.cuh)
 		DevBuf<uint64_t> tr_off; DevBuf<uint16_t> tr_ps, tr_ncig, tr_cig;                            // HAO_DELIVER_TRACE: cigar entries per read, ps and entry count per pair, the entries (hao_trace_grid.cuh)
 		void release() { ed_sum.release(); tr_off.release(); tr_ps.release(); tr_ncig.release(); tr_cig.release(); ed_off.release(); ed_err.release(); ed_pe.release(); fcw_off.release(); fcw.release(); ol_out.release(); ol_wire.release(); fin_off.release(); fc_out.release(); fc_out_off.release(); ch_off.release(); cl_off.release(); qm_off.release(); hdr.release(); bits.release(); rank.release(); rank4.release(); codes.release(); exc.release(); qmz.release(); qmz_pos.release(); qmz_cnt.release(); exact.release(); }
 	} out[2];
@@ -43,6 +44,7 @@ struct hao_ctx::Batch {
 	uint64_t ed_unres = 0;      // HAO_DELIVER_ED in reference placement: windows of the batch whose start resolved to no cigar entry
 	DevBuf<uint64_t> ed_nwin, ed_wbase, ed_wcnt, ed_woff; DevBuf<hao_ed_pair> ed_pairs; uint64_t ed_n = 0;      // HAO_DELIVER_ED scratch (compute stream only: not per output set); ed_n = pairs of the batch
 	hao_ed_delivery_t ed_dl[2] = {};      // the ED view of each slot (window 0: the slot's batch did not ask for HAO_DELIVER_ED)
+	uint64_t rs_nw = 0, rs_nres = 0, rs_wc = 0; hao_rescue_delivery_t rs_dl[2] = {}; bool rs_on[2] = { false, false };      // HAO_DELIVER_RESCUE: window records and rescued windows of the batch, its covered windows; the view of each slot
 	uint64_t tr_n = 0, tr_ncig = 0; hao_trace_delivery_t tr_dl[2] = {}; bool tr_on[2] = { false, false };      // HAO_DELIVER_TRACE: traced pairs and cigar entries of the batch; the view of each slot (tr_on: the slot's batch asked for it)
 	hao_delivery_t dl[2]; uint64_t dl_seq = 0, n_exc = 0; uint32_t dl_parts = 0; bool exact_valid = false; std::vector<uint8_t> h_exact;
 	// host copies for fetch
@@ -247,7 +249,7 @@ static int hao_ed_ref_upload(hao_ctx *c, uint32_t wl, double e_rate, DevBuf<uint
 // the per-overlap summaries (c->rf_sum) and the count of unresolved windows
 static int hao_ed_ref_run(hao_ctx *c, uint32_t wl, double e_rate, uint64_t *n_tasks, uint64_t *unresolved)
 {
-	hao_ctx::Batch &B = *c->batch; *n_tasks = 0; if (unresolved) *unresolved = 0; c->al_grid_n = 0; c->rf_valid = false; c->rf_hvalid = false; c->rf_unres = 0;
+	hao_ctx::Batch &B = *c->batch; *n_tasks = 0; if (unresolved) *unresolved = 0; c->al_grid_n = 0; c->rf_valid = false; c->rf_hvalid = false; c->rf_unres = 0; c->rs_valid = false; c->rf_T = 0;
 	if (hao_is_sharded(c)) { hao_set_err(c, "hao_window_ed_ref needs the bases of both reads: single-device mode only"); return HAO_EUNSUPP; }
 	if (!hao_ed_ref_args_ok(wl, e_rate)) { hao_set_err(c, "hao_window_ed_ref: window length 0, window + 62 beyond 16 bits, or e_rate outside (0, 1)"); return HAO_EINVAL; }
 	const uint64_t n = B.n;
@@ -281,13 +283,29 @@ static int hao_ed_ref_run(hao_ctx *c, uint32_t wl, double e_rate, uint64_t *n_ta
 	const hipError_t e7 = hipGetLastError(), e8 = hipStreamSynchronize(c->stream);
 	off.release();
 	HIP_TRY(e7); HIP_TRY(e8);
-	*n_tasks = T; c->al_grid_n = T; c->rf_unres = UR; if (unresolved) *unresolved = UR;
+	*n_tasks = T; c->al_grid_n = T; c->rf_T = T; c->rf_unres = UR; if (unresolved) *unresolved = UR;
 	if (T) {
 		if (int rc = hao_al_ed_resident(c, T, 1)) return rc;
 		hipLaunchKernelGGL(ed_ref_scatter_kernel, dim3((unsigned)((T + 255) / 256)), dim3(256), 0, c->stream, O.ol_out.p, c->rf.pairs.p, c->al_res.p, T, wl, A.win_off, c->rf.werr.p); HAO_CHECK_LAUNCH();
 	}
 	hipLaunchKernelGGL(ed_ref_summary_kernel, dim3((unsigned)((B.n_ol + 255) / 256)), dim3(256), 0, c->stream, O.ol_out.p, B.n_ol, wl, A.win_off, c->rf.werr.p, c->rf_sum.p); HAO_CHECK_LAUNCH();
 	c->rf_valid = true;
+	return HAO_OK;
+}
+
+// hao_window_rescue_ref: the rescue stage (hao_rescue.cuh) over what hao_ed_ref_run left - the CSR, shifts and error bytes in c->rf, the pair list and the
+// results per pair in c->al_res
+int hao_al_rescue(hao_ctx *c, const hao_ovlp_t *ol, uint64_t n_ol, uint32_t wl, hao_ref_args RA, const uint8_t *werr, const hao_ed_pair *pairs, const hao_ed_result_t *res, uint64_t n_pairs, uint64_t n_slots,
+		const uint8_t *err8 = nullptr, const uint16_t *pe16 = nullptr, hao_rs_ovlp *out = nullptr, DevBuf<uint64_t> *d_off = nullptr, DevBuf<hao_rs_win> *d_wins = nullptr, uint64_t *n_wins = nullptr);      // (hao_f3.hip)
+static int hao_rescue_ref_run(hao_ctx *c, uint64_t *n_rescued)
+{
+	hao_ctx::Batch &B = *c->batch; *n_rescued = 0; c->rs_valid = false; c->rs_hvalid = false;
+	if (!c->rf_valid || c->al_grid_n != c->rf_T) { hao_set_err(c, "hao_window_rescue_ref: hao_window_ed_ref has not run on this batch (or another window-alignment call has run since)"); return HAO_EINVAL; }
+	if (B.n == 0 || B.n_ol == 0) { c->rs_total = c->rs_rounds = c->rs_active = c->rs_slots = 0; c->rs_valid = true; return HAO_OK; }
+	hao_ref_args A; A.win_off = c->rf.woff.p; A.shift = c->rf.shift.p; A.tab = c->rf_tab.p;
+	uint64_t Wc = 0; HIP_TRY(hipMemcpyAsync(&Wc, c->rf.woff.p + B.n_ol, 8, hipMemcpyDeviceToHost, c->stream)); HIP_TRY(hipStreamSynchronize(c->stream));
+	if (int rc = hao_al_rescue(c, B.O().ol_out.p, B.n_ol, c->rf_tab_wl, A, c->rf.werr.p, c->rf.pairs.p, c->al_res.p, c->rf_T, Wc)) return rc;
+	*n_rescued = c->rs_total; c->rs_valid = true;
 	return HAO_OK;
 }
 
@@ -317,6 +335,7 @@ static int hao_ed_deliver_run(hao_ctx *c)
 	if (ref) {
 		uint64_t Wc = 0; HIP_TRY(O.ed_sum.reserve(B.n_ol + 1));
 		if (B.n_ol) { if (int rc = hao_ed_ref_front(c, wl, c->ded_tab.p, &A, &Wc)) return rc; }
+		B.rs_wc = Wc;
 		hipLaunchKernelGGL((ed_grid_kernel<ED_GRID_COUNT, HAO_PLACE_REF>), g_, b_, 0, c->stream, O.ol_out.p, O.fin_off.p, c->d_len.p, B.lo, n, wl, thre, nword, B.ed_wbase.p, B.ed_wcnt.p, (hao_ed_task_t*)nullptr, (hao_ed_pair*)nullptr, A); HAO_CHECK_LAUNCH();
 		if (B.n_ol) { hipLaunchKernelGGL(hao_peek_kernel, dim3(1), dim3(64), 0, c->stream, (const unsigned long long*)c->rf.ctr.p, 1, c->peek_d + 38); HAO_CHECK_LAUNCH(); } else c->peek_h[38] = 0;
 	} else {
@@ -368,6 +387,22 @@ static int hao_trace_deliver_run(hao_ctx *c)
 	return HAO_OK;
 }
 
+// HAO_DELIVER_RESCUE: the rescue stage over the slots, pairs and records HAO_DELIVER_ED has just written in reference placement (c->rf: CSR, shifts, error
+// bytes; the output set's err / pe per pair), into the output set's own buffers - the copy of this batch runs under the next batch's compute, which reuses
+// the stage's scratch in c->rs
+static int hao_rescue_deliver_run(hao_ctx *c)
+{
+	hao_ctx::Batch &B = *c->batch; hao_ctx::Batch::OutSet &O = B.O();
+	B.rs_nw = 0; B.rs_nres = 0;
+	HIP_TRY(O.rs_ovlp.reserve(B.n_ol + 1)); HIP_TRY(O.rs_off.reserve(B.n_ol + 2)); HIP_TRY(O.rs_wins.reserve(1));
+	if (B.n_ol == 0) { HIP_TRY(hipMemsetAsync(O.rs_off.p, 0, 8, c->stream)); c->timer.mark("rescue"); return HAO_OK; }
+	hao_ref_args A; A.win_off = c->rf.woff.p; A.shift = c->rf.shift.p; A.tab = c->ded_tab.p;
+	if (int rc = hao_al_rescue(c, O.ol_out.p, B.n_ol, c->ded_window, A, c->rf.werr.p, B.ed_pairs.p, nullptr, B.ed_n, B.rs_wc, O.ed_err.p, O.ed_pe.p, O.rs_ovlp.p, &O.rs_off, &O.rs_wins, &B.rs_nw)) return rc;
+	B.rs_nres = c->rs_total;
+	c->timer.mark("rescue");
+	return HAO_OK;
+}
+
 // hao_window_trace_grid: the grid pairs of the current batch (hao_window_ed_grid's), their distance-only alignment (the delivery path's kernel, into the
 // context's own buffers) and the traced stage; everything stays resident for hao_fetch_trace_grid.  out: pairs, traced pairs, cigar entries, aligned but untraced pairs.
 static int hao_trace_grid_run(hao_ctx *c, uint32_t wl, uint32_t thre, uint64_t out[4])
@@ -411,7 +446,7 @@ static int hao_deliver_enqueue(hao_ctx *c)
 {
 	hao_ctx::Batch &B = *c->batch; const int s = B.cur; hao_ctx::Batch::OutSet &O = B.O(); const uint64_t n = B.n; const uint32_t parts = B.dl_parts;
 	auto al = [](size_t v) { return (v + 63) & ~(size_t)63; };
-	const bool ol = parts & HAO_DELIVER_OL, cl = parts & HAO_DELIVER_CL, ex = parts & HAO_DELIVER_EXACT, ed = parts & HAO_DELIVER_ED, tr = parts & HAO_DELIVER_TRACE;
+	const bool ol = parts & HAO_DELIVER_OL, cl = parts & HAO_DELIVER_CL, ex = parts & HAO_DELIVER_EXACT, ed = parts & HAO_DELIVER_ED, tr = parts & HAO_DELIVER_TRACE, rsq = parts & HAO_DELIVER_RESCUE;
 	size_t o_oloff = 0, o_ol = o_oloff + (ol ? al((n + 1) * 8) : 0), o_fcoff = o_ol + (ol ? al(B.n_ol * sizeof(hao_ovlp_wire_t)) : 0), o_fc = o_fcoff + (ol ? al((B.n_ol + 1) * 8) : 0);
 	size_t o_choff = o_fc + (ol ? al(B.n_fcw * 4) : 0), o_cloff = o_choff + (cl ? al((n + 1) * 8) : 0), o_qmoff = o_cloff + (cl ? al((n + 1) * 8) : 0), o_hdr = o_qmoff + (cl ? al((n + 1) * 8) : 0);
 	const bool q16 = O.qmz16;      // the minimizer tables in 2 + 2 bytes per minimizer (hao_qtab16_kernel) instead of 8
@@ -422,7 +457,8 @@ static int hao_deliver_enqueue(hao_ctx *c)
 	size_t o_ex = o_exc + (cl ? al(B.n_exc * sizeof(hao_exc_t)) : 0), o_edoff = o_ex + (ex ? al(B.n_ol) : 0);
 	const bool edref = ed && B.ed_dl[s].placement == HAO_PLACE_REF;      // (reference placement: the per-overlap summaries travel after the pairs' records)
 	size_t o_ederr = o_edoff + (ed ? al((n + 1) * 8) : 0), o_edpe = o_ederr + (ed ? al(B.ed_n) : 0), o_edsum = o_edpe + (ed ? al(B.ed_n * 2) : 0), o_troff = o_edsum + (edref ? al(B.n_ol * sizeof(hao_ed_ovlp_sum)) : 0);      // (without HAO_DELIVER_ED: o_troff = o_edoff, the layout of before; in diagonal placement o_troff = o_edsum)
-	size_t o_trps = o_troff + (tr ? al((n + 1) * 8) : 0), o_trnc = o_trps + (tr ? al(B.ed_n * 2) : 0), o_trcig = o_trnc + (tr ? al(B.ed_n * 2) : 0), total = o_trcig + (tr ? al(B.tr_ncig * 2) : 0);      // (without HAO_DELIVER_TRACE: total = o_troff)
+	size_t o_trps = o_troff + (tr ? al((n + 1) * 8) : 0), o_trnc = o_trps + (tr ? al(B.ed_n * 2) : 0), o_trcig = o_trnc + (tr ? al(B.ed_n * 2) : 0), o_rsov = o_trcig + (tr ? al(B.tr_ncig * 2) : 0);      // (without HAO_DELIVER_TRACE: o_rsov = o_troff)
+	size_t o_rsoff = o_rsov + (rsq ? al(B.n_ol * sizeof(hao_rs_ovlp)) : 0), o_rswin = o_rsoff + (rsq ? al((B.n_ol + 1) * 8) : 0), total = o_rswin + (rsq ? al(B.rs_nw * sizeof(hao_rs_win)) : 0);      // (without HAO_DELIVER_RESCUE: total = o_rsov, the layout of before)
 	if (total > B.arena_cap[s] || B.arena_bad[s]) {
 		const bool redo_ = B.arena_bad[s]; B.arena_bad[s] = false;      // (hao_deliver_wait saw this slot's last batch copied at less than 40 GB/s: the probe below tries every NUMA node)
 		B.arena_free(s);
@@ -521,6 +557,12 @@ static int hao_deliver_enqueue(hao_ctx *c)
 		t.n_traced = B.tr_n; t.n_cigar = B.tr_ncig; t.cg_off = (const uint64_t*)(a + o_troff); t.ps = (const uint16_t*)(a + o_trps); t.n_cig = (const uint16_t*)(a + o_trnc); t.cigar = (const uint16_t*)(a + o_trcig);
 		d.bytes += (n + 1) * 8 + B.ed_n * 4 + B.tr_ncig * 2;
 	}
+	if (rsq && n) {
+		HIP_TRY(cp(o_rsov, O.rs_ovlp.p, B.n_ol * sizeof(hao_rs_ovlp))); HIP_TRY(cp(o_rsoff, O.rs_off.p, (B.n_ol + 1) * 8)); HIP_TRY(cp(o_rswin, O.rs_wins.p, B.rs_nw * sizeof(hao_rs_win)));
+		hao_rescue_delivery_t &r = B.rs_dl[s];
+		r.n_ol = B.n_ol; r.n_wins = B.rs_nw; r.n_rescued = B.rs_nres; r.ovlp = (const hao_rescue_ovlp_t*)(a + o_rsov); r.win_off = (const uint64_t*)(a + o_rsoff); r.wins = (const hao_rescue_win_t*)(a + o_rswin);
+		d.bytes += B.n_ol * sizeof(hao_rs_ovlp) + (B.n_ol + 1) * 8 + B.rs_nw * sizeof(hao_rs_win);
+	}
 	HIP_TRY(hipEventRecord(B.ev_done[s], B.copy_stream));
 	B.dl_pending[s] = true;
 	return HAO_OK;
@@ -545,7 +587,7 @@ static int hao_overlap_run(hao_ctx *c, uint64_t lo, uint64_t hi, const hao_pass_
 	if (!c->has_pt) { hao_set_err(c, "hao_pt_gen must run before hao_overlap_batch"); return HAO_EINVAL; }
 	if (!c->batch) c->batch = new hao_ctx::Batch();
 	hao_ctx::Batch &B = *c->batch; const double t_run0 = hao_now();
-	c->al_grid_n = 0; c->tg_valid = false; c->rf_valid = false;      // (the window-alignment grid of the previous batch's overlaps is stale)
+	c->al_grid_n = 0; c->tg_valid = false; c->rf_valid = false; c->rs_valid = false;      // (the window-alignment grid of the previous batch's overlaps is stale)
 	B.valid = false; B.host_valid = false; B.cl_valid = false; B.exact_valid = false; B.h_exact.clear(); B.lo = lo; B.n = hi - lo; B.dl_parts = parts; B.n_exc = 0;
 	const uint64_t n = B.n;
 	if (parts) {
@@ -557,7 +599,8 @@ static int hao_overlap_run(hao_ctx *c, uint64_t lo, uint64_t hi, const hao_pass_
 	if (B.dl_ready && B.dl_pending[B.cur]) { const double t0_ = hao_now(); HIP_TRY(hipEventSynchronize(B.ev_done[B.cur])); B.dl_pending[B.cur] = false; B.t_evsync += hao_now() - t0_; }
 	if (parts) { memset(&B.dl[B.cur], 0, sizeof(hao_delivery_t)); B.dl[B.cur].rid_lo = lo; B.dl[B.cur].n_reads = n;
 		memset(&B.ed_dl[B.cur], 0, sizeof(hao_ed_delivery_t)); if (parts & HAO_DELIVER_ED) { B.ed_dl[B.cur].window = c->ded_window; B.ed_dl[B.cur].thre = c->ded_thre; B.ed_dl[B.cur].placement = c->ded_place; B.ed_dl[B.cur].e_rate = c->ded_place == HAO_PLACE_REF ? c->ded_erate : 0; }
-		memset(&B.tr_dl[B.cur], 0, sizeof(hao_trace_delivery_t)); B.tr_on[B.cur] = (parts & HAO_DELIVER_TRACE) != 0; }
+		memset(&B.tr_dl[B.cur], 0, sizeof(hao_trace_delivery_t)); B.tr_on[B.cur] = (parts & HAO_DELIVER_TRACE) != 0;
+		memset(&B.rs_dl[B.cur], 0, sizeof(hao_rescue_delivery_t)); B.rs_on[B.cur] = (parts & HAO_DELIVER_RESCUE) != 0; }
 	if (n == 0) { B.n_anchor = B.n_groups = B.n_chains = B.n_cl = B.n_ol = B.n_fc = B.n_fcw = B.n_mz = 0; B.valid = true; return HAO_OK; }      // (an empty delivery: nothing to copy, the view stays zeroed)
 	// minimizer range of the batch (host knows the per-read offsets? keep a host copy once)
 	if (c->h_ix_mz_off.size() != c->n_reads + 1) {
@@ -919,6 +962,7 @@ static int hao_overlap_run(hao_ctx *c, uint64_t lo, uint64_t hi, const hao_pass_
 	if (parts & HAO_DELIVER_EXACT) { if (int rc = hao_exact_run(c)) return rc; }
 	if (parts & HAO_DELIVER_ED) { if (int rc = hao_ed_deliver_run(c)) return rc; }
 	if (parts & HAO_DELIVER_TRACE) { if (int rc = hao_trace_deliver_run(c)) return rc; }
+	if (parts & HAO_DELIVER_RESCUE) { if (int rc = hao_rescue_deliver_run(c)) return rc; }
 	if (parts) { const double t0_ = hao_now(); const int rc_ = hao_deliver_enqueue(c); B.t_enq += hao_now() - t0_; ++B.t_n; if (c->sw.dltime && (B.t_n & 15) == 0) fprintf(stderr, "[deliver] %llu batches: slot wait %.1f ms, enqueue %.1f ms (arena alloc %.1f ms)\n", (unsigned long long)B.t_n, B.t_evsync * 1e3, B.t_enq * 1e3, B.t_alloc * 1e3); return rc_; }
 	return HAO_OK;
 }

@@ -15,7 +15,7 @@ static void hao_release_all(hao_ctx *c)
 	c->w_lkv2.release(); c->w_s40_list.release(); c->w_s40_o.release(); c->w_s40_x.release(); c->w_s40_cnt.release(); c->d_ix_lk.release(); c->w_runid.release(); c->d_ix_mz_x.release(); c->d_ix_mz_info.release(); c->d_ix_mz_off.release(); c->d_ix_sx.release(); c->d_ix_sinfo.release();
 	c->d_ix_keys.release(); c->d_ix_start.release(); c->d_ix_cnt.release(); c->d_ix_bucket.release();
 	c->al_task.release(); c->al_k1.release(); c->al_k2.release(); c->al_path.release(); c->al_i1.release(); c->al_order.release(); c->al_sel.release(); c->al_res.release(); c->al_tres.release(); c->al_want.release(); c->al_cig.release();
-	c->rf.release(); c->ded_tab.release(); c->rf_tab.release(); c->rf_sum.release(); c->rf_valid = false;
+	c->rf.release(); c->ded_tab.release(); c->rf_tab.release(); c->rf_sum.release(); c->rf_valid = false; c->rs.release(); c->rs_valid = false;
 	c->tg.release(); c->tg_pairs.release(); c->tg_err.release(); c->tg_pe.release(); c->tg_ps.release(); c->tg_ncig16.release(); c->tg_cig.release(); c->tg_valid = false;
 }
 
@@ -139,6 +139,11 @@ int hao_overlap_batch_async(hao_ctx *c, uint64_t rid_lo, uint64_t rid_hi, const 
 		if (!c->ded_window) { hao_set_err(c, "HAO_DELIVER_ED before hao_deliver_ed_config"); return HAO_EINVAL; }
 	}
 	if ((parts & HAO_DELIVER_TRACE) && (parts & HAO_DELIVER_ED) && c->ded_place == HAO_PLACE_REF) { hao_set_err(c, "HAO_DELIVER_TRACE: the traced grid stage is not built in reference placement (hao_deliver_ed_config_ref)"); return HAO_EUNSUPP; }
+	if (parts & HAO_DELIVER_RESCUE) {
+		if (hao_is_sharded(c)) { hao_set_err(c, "HAO_DELIVER_RESCUE needs the bases of both reads: single-device mode only"); return HAO_EUNSUPP; }
+		if (!(parts & HAO_DELIVER_ED)) { hao_set_err(c, "HAO_DELIVER_RESCUE needs HAO_DELIVER_ED: it rescues the windows the ED stage left open"); return HAO_EINVAL; }
+		if (c->ded_place != HAO_PLACE_REF) { hao_set_err(c, "HAO_DELIVER_RESCUE needs reference placement (hao_deliver_ed_config_ref)"); return HAO_EINVAL; }
+	}
 	if ((parts & HAO_DELIVER_TRACE) && !(parts & HAO_DELIVER_ED)) { hao_set_err(c, "HAO_DELIVER_TRACE needs HAO_DELIVER_ED: it traces the pairs the ED stage aligned"); return HAO_EINVAL; }
 	hao_pass_t ps;
 	if (!pass) { if (int rc = hao_pass_default(c, &ps)) return rc; pass = &ps; }
@@ -463,6 +468,102 @@ int hao_fetch_ed_ovlp(hao_ctx *c, uint64_t rid, const hao_ed_ovlp_t **summary, u
 	const uint64_t r = rid - B.lo, s_ = B.h_fin_off[r], e_ = B.h_fin_off[r + 1];
 	*summary = (const hao_ed_ovlp_t*)(c->rf_hsum.data() + s_); *n = e_ - s_;
 	return HAO_OK;
+}
+
+int hao_window_rescue_ref(hao_ctx *c, uint64_t *n_rescued)
+{
+	if (!c || !n_rescued || !c->batch || !c->batch->valid) return HAO_EINVAL;
+	if (int rc = hao_view_refresh(c)) return rc;
+	HIP_TRY(hipSetDevice(c->device));
+	c->timer.begin(c->stream);
+	if (int rc = hao_rescue_ref_run(c, n_rescued)) return rc;
+	HIP_TRY(hipStreamSynchronize(c->stream));
+	c->timer.mark("rescue_ref"); c->timer.collect(c->stage_ms);
+	return HAO_OK;
+}
+
+int hao_fetch_rescue(hao_ctx *c, uint64_t rid, const hao_rescue_ovlp_t **ovlp, uint64_t *n, const uint64_t **win_off, const hao_rescue_win_t **wins)
+{
+	if (!c || !ovlp || !n || !win_off || !wins) return HAO_EINVAL;
+	if (!c->batch || !c->batch->valid || !c->rs_valid) { hao_set_err(c, "hao_fetch_rescue: no results of hao_window_rescue_ref are resident (a new batch has run since)"); return HAO_EINVAL; }
+	hao_ctx::Batch &B = *c->batch;
+	if (rid < B.lo || rid >= B.lo + B.n) return HAO_EINVAL;
+	HIP_TRY(hipSetDevice(c->device));
+	if (int rc = hao_batch_download(c)) return rc;
+	hao_ctx::Rescue &G = c->rs;
+	if (!c->rs_hvalid) {      // the whole batch once: the per-overlap results, and the record regions compacted into a CSR by overlap (slots without a record dropped)
+		const uint64_t m = B.n_ol;
+		G.h_ovlp.assign(m + 1, hao_rs_ovlp{0, 0, 0, 0, 0}); G.h_win_off.assign(m + 1, 0); G.h_wins.clear();
+		if (m) {
+			std::vector<uint64_t> rb(m), wo(m + 1); std::vector<hao_rs_win> rec((size_t)c->rs_slots + 1);
+			HIP_TRY(hipMemcpy(G.h_ovlp.data(), G.ovlp.p, m * sizeof(hao_rs_ovlp), hipMemcpyDeviceToHost));
+			HIP_TRY(hipMemcpy(rb.data(), G.rbase.p, m * 8, hipMemcpyDeviceToHost));
+			HIP_TRY(hipMemcpy(wo.data(), c->rf.woff.p, (m + 1) * 8, hipMemcpyDeviceToHost));
+			if (c->rs_slots) HIP_TRY(hipMemcpy(rec.data(), G.rec.p, c->rs_slots * sizeof(hao_rs_win), hipMemcpyDeviceToHost));
+			for (uint64_t i = 0; i < m; ++i) {
+				G.h_win_off[i] = G.h_wins.size();
+				if (rb[i] == UINT64_MAX) continue;
+				for (uint64_t k = 0, nw = wo[i + 1] - wo[i]; k < nw && rb[i] + k < c->rs_slots; ++k) {
+					hao_rs_win r = rec[rb[i] + k];
+					if (r.info & HAO_RS_VALID) { r.info &= ~(HAO_RS_VALID | HAO_RS_UNTRACED_BIT); G.h_wins.push_back(r); }
+				}
+			}
+			G.h_win_off[m] = G.h_wins.size();
+		}
+		G.h_wins.push_back(hao_rs_win{0, 0, 0, 0});      // (never empty: the pointer handed out is valid)
+		c->rs_hvalid = true;
+	}
+	const uint64_t r = rid - B.lo, s_ = B.h_fin_off[r], e_ = B.h_fin_off[r + 1];
+	*ovlp = (const hao_rescue_ovlp_t*)(G.h_ovlp.data() + s_); *n = e_ - s_;
+	*win_off = G.h_win_off.data() + s_; *wins = (const hao_rescue_win_t*)G.h_wins.data();
+	return HAO_OK;
+}
+
+int hao_rescue_task(const hao_ovlp_t *z, uint32_t win, uint32_t window, int64_t toff, const uint8_t *tab, uint32_t target_len, hao_ed_task_t *out)
+{
+	if (!z || !tab || !out || window == 0) return 0;
+	return hao_rescue_pair(*z, win, window, toff, tab, target_len, out) ? 1 : 0;
+}
+
+int hao_deliver_rescue(hao_ctx *c, int slot, hao_rescue_delivery_t *out)
+{
+	if (!c || !out || slot < 0 || slot > 1 || !c->batch || !c->batch->dl_ready) return HAO_EINVAL;
+	hao_ctx::Batch &B = *c->batch;
+	if (!B.rs_on[slot]) { hao_set_err(c, "hao_deliver_rescue: the slot's batch did not ask for HAO_DELIVER_RESCUE"); return HAO_EINVAL; }
+	if (B.dl_pending[slot]) { hao_set_err(c, "hao_deliver_rescue: hao_deliver_wait has not been called on the slot"); return HAO_EINVAL; }
+	*out = B.rs_dl[slot];
+	return HAO_OK;
+}
+
+uint64_t hao_unpack_rescue(const hao_delivery_t *d, const hao_ed_delivery_t *e, const hao_rescue_delivery_t *r, const uint32_t *len, uint64_t rid,
+		hao_rescue_ovlp_t *ovlp, uint64_t *win_off, hao_rescue_win_t *wins, uint64_t cap_ovlp, uint64_t cap_wins)
+{
+	if (!d || !e || !r || !len) return UINT64_MAX;
+	if (rid < d->rid_lo || rid >= d->rid_lo + d->n_reads) return 0;
+	if (!e->window || e->placement != HAO_PLACE_REF || !d->ol_off || !d->ol || r->n_ol != d->n_ol || (r->n_ol && (!r->ovlp || !r->win_off)) || (r->n_wins && !r->wins)) return UINT64_MAX;
+	const uint64_t q = rid - d->rid_lo, o0 = d->ol_off[q], o1 = d->ol_off[q + 1];
+	if (o0 > o1 || o1 > r->n_ol) return UINT64_MAX;
+	const uint64_t n = o1 - o0;
+	if (n == 0) return 0;
+	const uint64_t w0 = r->win_off[o0], w1 = r->win_off[o1];
+	if (w0 > w1 || w1 > r->n_wins) return UINT64_MAX;
+	// every record in a window its overlap covers, in ascending window order, inside the read's grid
+	std::vector<hao_ovlp_t> zs(n);
+	if (hao_unpack_overlaps(d, rid, zs.data(), n) != n) return UINT64_MAX;
+	const uint32_t wl = e->window; const uint64_t nwin = ((uint64_t)len[rid] + wl - 1) / wl;
+	for (uint64_t i = 0; i < n; ++i) {
+		const uint64_t a = r->win_off[o0 + i], b = r->win_off[o0 + i + 1];
+		if (a > b || b > w1) return UINT64_MAX;
+		for (uint64_t k = a; k < b; ++k) {
+			const uint32_t w = r->wins[k].win;
+			if (w < zs[i].x_pos_s / wl || w > zs[i].x_pos_e / wl || w >= nwin || (k > a && r->wins[k - 1].win >= w)) return UINT64_MAX;
+		}
+	}
+	if (n > cap_ovlp || w1 - w0 > cap_wins || !ovlp || !win_off || !wins) return n;
+	for (uint64_t i = 0; i < n; ++i) { ovlp[i] = r->ovlp[o0 + i]; win_off[i] = r->win_off[o0 + i] - w0; }
+	win_off[n] = w1 - w0;
+	for (uint64_t k = w0; k < w1; ++k) wins[k - w0] = r->wins[k];
+	return n;
 }
 
 int hao_deliver_ed(hao_ctx *c, int slot, hao_ed_delivery_t *out)

@@ -173,6 +173,15 @@ struct hao_ctx {
 		void release() { cnt.release(); woff.release(); shift.release(); werr.release(); pairs.release(); ctr.release(); }
 	} rf;
 	DevBuf<uint8_t> rf_tab; uint32_t rf_tab_wl = 0; double rf_tab_erate = 0; DevBuf<hao_ed_ovlp_sum> rf_sum; std::vector<hao_ed_ovlp_sum> rf_hsum; bool rf_valid = false, rf_hvalid = false; uint64_t rf_unres = 0;
+	// the rescue stage (hao_rescue.cuh; hao_window_rescue_ref): pe per CSR slot, record region start per overlap, the states of the overlaps with an open
+	// window, their record regions, the per-overlap results, the column scratch, six counters; rs_valid: the results belong to the current batch (rf_T: the
+	// pairs hao_window_ed_ref left in al_res, which the stage reads); h_*: hao_fetch_rescue's host copies and the compacted records
+	struct Rescue {
+		DevBuf<uint16_t> wpe; DevBuf<uint64_t> rbase, path; DevBuf<hao_rs_state> st; DevBuf<hao_rs_win> rec; DevBuf<hao_rs_ovlp> ovlp; DevBuf<unsigned long long> ctr;
+		std::vector<hao_rs_ovlp> h_ovlp; std::vector<uint64_t> h_win_off; std::vector<hao_rs_win> h_wins;
+		void release() { wpe.release(); rbase.release(); path.release(); st.release(); rec.release(); ovlp.release(); ctr.release(); }
+	} rs;
+	bool rs_valid = false, rs_hvalid = false; uint64_t rf_T = 0, rs_slots = 0, rs_rounds = 0, rs_active = 0, rs_total = 0;
 	// f3 with traceback on the grid (hao_trace_grid.cuh): the stage's scratch, compute stream only (hao_window_trace_grid and HAO_DELIVER_TRACE share it) -
 	// flags and selected pairs, entry counts and their scans, the compact array's offsets, the column scratch, the rows of one slice, two counters
 	struct TraceGrid {

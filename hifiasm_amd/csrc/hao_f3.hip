@@ -10,6 +10,7 @@
 #include "hao_align.cuh"
 #include "hao_ed_deliver.cuh"
 #include "hao_trace_grid.cuh"
+#include "hao_rescue.cuh"
 
 // ---- f3 (hao_align.cuh): host side of the window-alignment batches ----
 // tasks -> device, and their order by text window (hao_align.cuh: a wave takes 64 neighbours of that order, which mostly share one text)
@@ -162,6 +163,69 @@ int hao_al_trace_grid_expand(hao_ctx *c, const hao_ovlp_t *ol, uint64_t n, hao_e
 	if (n == 0) return HAO_OK;
 	hipLaunchKernelGGL(hao_tg_expand_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, c->d_len.p, ol, c->tg_pairs.p, n, c->tg_wl, c->tg_thre,
 		c->tg_err.p, c->tg_pe.p, c->tg_ps.p, c->tg_ncig16.p, tasks, res); HAO_CHECK_LAUNCH();
+	return HAO_OK;
+}
+
+// the rescue stage (hao_rescue.cuh; hao_window_rescue_ref, hao_batch.hpp): over the n_ol overlaps of the batch whose reference-placed ED stage has just run -
+// RA = its CSR and shifts, werr / res = its error bytes per slot and results per pair (n_pairs, pair list `pairs`), n_slots = its covered windows.  Leaves the
+// per-overlap results in c->rs.ovlp, the record regions in c->rs.rec (c->rs.rbase[i]: overlap i's), and the counts in c->rs_*.  Host round trips: one for the
+// two sizes, one count per round, one for the total.
+// res == NULL: the delivery path's records err8 / pe16 per pair instead.  out: where the per-overlap results go (NULL: c->rs.ovlp).  d_off / d_wins / n_wins
+// (the delivery path, all three or none): the records compacted on the device - d_off[n_ol + 1] offsets, the records, their number (one more round trip).
+int hao_al_rescue(hao_ctx *c, const hao_ovlp_t *ol, uint64_t n_ol, uint32_t wl, hao_ref_args RA, const uint8_t *werr, const hao_ed_pair *pairs, const hao_ed_result_t *res, uint64_t n_pairs, uint64_t n_slots,
+		const uint8_t *err8, const uint16_t *pe16, hao_rs_ovlp *out, DevBuf<uint64_t> *d_off, DevBuf<hao_rs_win> *d_wins, uint64_t *n_wins)
+{
+	hao_ctx::Rescue &G = c->rs;
+	c->rs_rounds = c->rs_active = c->rs_total = 0; c->rs_slots = 0;
+	HIP_TRY(G.ovlp.reserve(n_ol + 1)); HIP_TRY(G.rbase.reserve(n_ol + 1)); HIP_TRY(G.wpe.reserve(n_slots + 1)); HIP_TRY(G.ctr.reserve(8));
+	if (n_wins) *n_wins = 0;
+	if (n_ol == 0) return HAO_OK;
+	HIP_TRY(hipMemsetAsync(G.ctr.p, 0, 64, c->stream));
+	const dim3 b_(256), go((unsigned)((n_ol + 255) / 256));
+	if (n_pairs && res) { hipLaunchKernelGGL(hao_rs_scatter_pe_kernel, dim3((unsigned)((n_pairs + 255) / 256)), b_, 0, c->stream, ol, pairs, res, n_pairs, wl, RA.win_off, G.wpe.p); HAO_CHECK_LAUNCH(); }
+	else if (n_pairs) { hipLaunchKernelGGL(hao_rs_scatter_pe16_kernel, dim3((unsigned)((n_pairs + 255) / 256)), b_, 0, c->stream, ol, pairs, err8, pe16, n_pairs, wl, RA.win_off, G.wpe.p); HAO_CHECK_LAUNCH(); }
+	hao_rs_args A; A.ol = ol; A.n_ol = n_ol; A.wl = wl; A.win_off = RA.win_off; A.shift = RA.shift; A.tab = RA.tab; A.werr = werr; A.wpe = G.wpe.p; A.len = c->d_len.p;
+	hipLaunchKernelGGL((hao_rs_gap_kernel<false>), go, b_, 0, c->stream, A, G.ctr.p, (uint64_t*)nullptr, (hao_rs_state*)nullptr, (hao_rs_win*)nullptr); HAO_CHECK_LAUNCH();
+	hipLaunchKernelGGL(hao_peek_kernel, dim3(1), dim3(64), 0, c->stream, (const unsigned long long*)G.ctr.p, 2, c->peek_d + 40); HAO_CHECK_LAUNCH();
+	HIP_TRY(hipStreamSynchronize(c->stream));
+	const uint64_t na = c->peek_h[40], ns = c->peek_h[41];
+	HIP_TRY(G.st.reserve(na + 1)); HIP_TRY(G.rec.reserve(ns + 1));
+	hipLaunchKernelGGL((hao_rs_gap_kernel<true>), go, b_, 0, c->stream, A, G.ctr.p, G.rbase.p, G.st.p, G.rec.p); HAO_CHECK_LAUNCH();
+	uint64_t rounds = 0;
+	if (na) {
+		// column scratch: 24 bytes per text column (t_len <= wl, + slot 0) and lane, in slices of the states whose columns fit ~4 GB; a slice runs its rounds to the end
+		const hao_ed_reads R = hao_al_reads_of(c);
+		const uint64_t ncol = (uint64_t)wl + 1;
+		const uint64_t slice = std::max<uint64_t>(256, std::min<uint64_t>((na + 255) & ~255ULL, ((4ULL << 30) / (24 * ncol)) & ~255ULL));
+		HIP_TRY(G.path.reserve(3 * ncol * slice + 1));
+		for (uint64_t lo = 0; lo < na; lo += slice) {
+			const uint64_t m = std::min<uint64_t>(slice, na - lo);
+			for (;;) {
+				HIP_TRY(hipMemsetAsync(G.ctr.p + 4, 0, 8, c->stream));
+				hipLaunchKernelGGL(hao_rs_round_kernel, dim3((unsigned)((m + 255) / 256)), b_, 0, c->stream, R, A, G.st.p + lo, m, G.rec.p, G.path.p, slice, G.ctr.p + 4); HAO_CHECK_LAUNCH();
+				hipLaunchKernelGGL(hao_peek_kernel, dim3(1), dim3(64), 0, c->stream, (const unsigned long long*)(G.ctr.p + 4), 1, c->peek_d + 42); HAO_CHECK_LAUNCH();
+				HIP_TRY(hipStreamSynchronize(c->stream));
+				++rounds;
+				if (c->peek_h[42] == 0) break;
+				if (rounds > 4 * n_slots + 16) { G.path.release(); hao_set_err(c, "rescue stage: more rounds than alignment steps exist"); return HAO_EUNSUPP; }      // (every round completes a step of every waiting lane)
+			}
+		}
+	}
+	hipLaunchKernelGGL(hao_rs_verdict_kernel, go, b_, 0, c->stream, A, G.rbase.p, G.rec.p, out ? out : G.ovlp.p, G.ctr.p + 5); HAO_CHECK_LAUNCH();
+	if (d_off) {
+		HIP_TRY(d_off->reserve(n_ol + 2)); HIP_TRY(c->al_k1.reserve(n_ol + 2));      // (al_k1: the upload path's key buffer, free here)
+		hipLaunchKernelGGL(hao_rs_count_kernel, dim3((unsigned)((n_ol + 256) / 256)), b_, 0, c->stream, n_ol, RA.win_off, G.rbase.p, G.rec.p, c->al_k1.p); HAO_CHECK_LAUNCH();
+		if (int rc = hao_excl_scan_u64(c, c->al_k1.p, d_off->p, n_ol + 1)) return rc;
+		hipLaunchKernelGGL(hao_peek_kernel, dim3(1), dim3(64), 0, c->stream, (const unsigned long long*)(d_off->p + n_ol), 1, c->peek_d + 44); HAO_CHECK_LAUNCH();
+		HIP_TRY(hipStreamSynchronize(c->stream));
+		*n_wins = c->peek_h[44];
+		HIP_TRY(d_wins->reserve(*n_wins + 1));
+		if (*n_wins) { hipLaunchKernelGGL(hao_rs_compact_kernel, go, b_, 0, c->stream, n_ol, RA.win_off, G.rbase.p, G.rec.p, d_off->p, d_wins->p); HAO_CHECK_LAUNCH(); }
+	}
+	hipLaunchKernelGGL(hao_peek_kernel, dim3(1), dim3(64), 0, c->stream, (const unsigned long long*)(G.ctr.p + 5), 1, c->peek_d + 43); HAO_CHECK_LAUNCH();
+	HIP_TRY(hipStreamSynchronize(c->stream));
+	c->rs_total = c->peek_h[43]; c->rs_rounds = rounds; c->rs_active = na; c->rs_slots = ns;
+	if (G.path.cap > (1ULL << 27)) G.path.release();      // (more than 1 GB of column scratch is not kept between calls)
 	return HAO_OK;
 }
 

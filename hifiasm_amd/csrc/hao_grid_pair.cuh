@@ -81,6 +81,54 @@ __host__ __device__ __forceinline__ bool hao_ref_pair(const hao_ovlp_t &z, uint3
 	return true;
 }
 
+// ---- rescue of unaligned windows (push_hc_wlst_exz, Correct.cpp:12776-12836, through aln_wlst_adv_exz :4057-4131; hao_rescue.cuh) ----
+// the threshold of a rescue alignment of a window of ql bases: double_error_threshold(get_init_err_thres(ql, e_rate, w_l, 31), ql) (:917, :1042) over the
+// table of hao_ref_thre_table (whose entries are get_init_err_thres' for ql < w_l)
+__host__ __device__ __forceinline__ uint32_t hao_rescue_thre(uint32_t ql, uint32_t wl, const uint8_t *tab)
+{
+	uint32_t t = ql >= wl ? 31u : tab[ql];
+	if (t == 0 && ql >= 4) t = 1;
+	t *= 2;
+	if (ql >= 300 && t < 31) t = 31;
+	return t > 31 ? 31 : t;
+}
+// grid window w of overlap z clipped to the overlap: its first base and its length (0: not covered)
+__host__ __device__ __forceinline__ void hao_ref_window(const hao_ovlp_t &z, uint32_t w, uint32_t wl, int64_t *qs, int64_t *ql)
+{
+	const int64_t xs = z.x_pos_s, xe = z.x_pos_e, g0 = (int64_t)w * wl;
+	*qs = g0 > xs ? g0 : xs; const int64_t qe = g0 + wl - 1 < xe ? g0 + wl - 1 : xe; *ql = qe + 1 - *qs;
+	if (*ql < 0) *ql = 0;
+}
+// the task of a rescue alignment: grid window w of overlap z against the target from toff on (aln_wlst_adv_exz's t_s: the end of the window before + 1 in a
+// forward run, the start of the window after - the window's length in a backward run), init_waln with the rescue threshold.  false: init_waln refuses it, or
+// the pattern is too short (t_pri_l + thres < ql).  p_pos = the r_s the window record's y_start / y_end are counted from.  Shared by the rescue kernel, the
+// host decoder and the tests.
+__host__ __device__ __forceinline__ bool hao_rescue_pair(const hao_ovlp_t &z, uint32_t w, uint32_t wl, int64_t toff, const uint8_t *tab, uint32_t tl, hao_ed_task_t *t)
+{
+	int64_t qs, ql; hao_ref_window(z, w, wl, &qs, &ql);
+	if (ql <= 0) return false;
+	const int64_t thre = hao_rescue_thre((uint32_t)ql, wl, tab), wln = ql + 2 * thre, s = toff, l = tl;
+	if (s < 0 || s >= l || l - s + 2 * thre + 31 < wln) return false;
+	int64_t rs = s - thre, rl = l - rs, ab = 0;
+	if (rl > wln) rl = wln;
+	if (rs < 0) { ab = -rs; rs = 0; rl -= ab; }
+	if (rl + thre < ql) return false;
+	t->p_rid = z.y_id; t->p_pos = (uint32_t)rs; t->p_len = (uint32_t)rl; t->p_rev = z.y_pos_strand;
+	t->t_rid = z.x_id; t->t_pos = (uint32_t)qs; t->t_len = (uint32_t)ql; t->t_rev = 0; t->thre = (uint32_t)thre; t->abs_diag = (uint32_t)ab;
+	return true;
+}
+// per-overlap result of the rescue stage and a window record (hao.h: hao_rescue_ovlp_t, hao_rescue_win_t)
+struct hao_rs_ovlp { uint16_t verdict, flags; uint32_t exit_win, align_length, n_rescued; };
+struct hao_rs_win { int32_t y_start, y_end; uint32_t win, info; };
+// the rescue stage's state of one overlap (hao_rescue.cuh runs it; here because the context holds a buffer of them).  k: the aligned window (slot) being pushed;
+// j: the window the pending alignment is for; last: slot of w_list's last entry (-1: empty); cs: first slot the backward run may reach; toff: target offset of
+// the pending alignment; a_*: window k's record (y_start is its r_s until it is traced)
+struct hao_rs_state { uint32_t ol; int32_t phase, k, j, last, cs; uint32_t aflags; int32_t a_ys, a_ye, a_err; int64_t toff; uint64_t base; };
+// device-only bits of a record's info word, stripped before a record leaves the library: the slot holds a record; on an anchor's record, a traced step of its
+// backward run fell outside the traced domain (becomes HAO_RESCUE_UNTRACED in the overlap's flags)
+#define HAO_RS_VALID 0x80000000u
+#define HAO_RS_UNTRACED_BIT (1u << 19)
+
 // what the reference-placed generators read beside the overlaps: the covered windows of overlap i are slots win_off[i] .. win_off[i + 1] of shift[] (slot
 // k = grid window x_pos_s / window + k), tab = the threshold table; all null in diagonal placement
 struct hao_ref_args { const uint64_t *win_off; const int16_t *shift; const uint8_t *tab; };

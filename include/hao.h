@@ -285,14 +285,14 @@ int hao_fetch_ed_grid(hao_ctx *c, hao_ed_task_t *tasks, hao_ed_result_t *res, ui
  *   hao_window_ed_ref:         blocking, over the last batch; tasks and results lie where hao_window_ed_grid leaves them, so hao_fetch_ed_grid serves them;
  *                              *unresolved (may be NULL) = the batch's unresolved windows.
  *   hao_fetch_ed_ovlp:         the per-overlap summaries of the last hao_window_ed_ref for read rid, aligned with hao_fetch_overlaps' ol: windows covered, windows
- *                              aligned (err != INT32_MAX), the sum of their lengths - the align_length the reference's loop accumulates before its rescue step,
+ *                              aligned (err != INT32_MAX), the sum of their lengths - the align_length the reference's loop accumulates before its rescue step (hao_rescue_ovlp_t has the final one),
  *                              what its OVERLAP_THRESHOLD_HIFI_FILTER test (simi_pass) starts from - and the sum of their errors.
  *   hao_deliver_ed_config_ref: this context's following HAO_DELIVER_ED batches are reference-placed (hao_deliver_ed_config switches back).  The 3 bytes per pair
  *                              and the per-read offsets travel as before, the summaries (16 bytes per overlap) after them; hao_deliver_ed's view names placement
  *                              and e_rate, and hao_unpack_ed rebuilds a read's tasks from the delivered overlaps AND their delivered fake cigars.
  * Not built: the traced stage in reference placement - HAO_DELIVER_TRACE on a reference-placed context returns HAO_EUNSUPP, hao_window_trace_grid has no
- * reference-placed form, and hao_unpack_trace returns 0 for a reference-placed view (never diagonal cigars under a reference-placed configuration).  Out of scope: the reference's rescue of unaligned windows by extension from aligned neighbours and its early exit (push_hc_wlst_exz,
- * Correct.cpp:12711-12771), which are sequential per overlap. */
+ * reference-placed form, and hao_unpack_trace returns 0 for a reference-placed view (never diagonal cigars under a reference-placed configuration).  The reference's rescue of unaligned windows from their aligned neighbours, its early exit and its
+ * return value: hao_window_rescue_ref below (blocking path). */
 #define HAO_PLACE_DIAG 0u
 #define HAO_PLACE_REF 1u
 typedef struct { uint32_t n_win, n_aligned, aligned_bases, err_sum; } hao_ed_ovlp_t;
@@ -317,6 +317,60 @@ int hao_window_ed_ref(hao_ctx *c, uint32_t window, double e_rate, uint64_t *n_ta
 int hao_fetch_ed_ovlp(hao_ctx *c, uint64_t rid, const hao_ed_ovlp_t **summary, uint64_t *n);
 int hao_deliver_ed_config_ref(hao_ctx *c, uint32_t window, double e_rate);
 void hao_ref_thresholds(uint32_t window, double e_rate, uint8_t *out /* [window + 1] */);     /* host code, no context */
+
+/* The second half of align_hc_ed_post_extz (Correct.cpp:12951-13012): the rescue of the windows that did not align at first placement from their aligned
+ * neighbours (push_hc_wlst_exz :12776-12836 through aln_wlst_adv_exz :4057-4131), the early exit after every aligned window and the function's return value
+ * pass_qovlp(x_pos_e + 1 - x_pos_s, align_length, 0.9).  Per overlap, at every window k that aligned at first placement, in ascending order:
+ *   forward:   from the window after the previous aligned window, with the target start = that window's y_end + 1, windows are aligned distance-only with the
+ *              doubled threshold (31 for windows of 300 bases or more) until one fails, the gap is closed or the target is used up;
+ *   backward:  if windows are still open before k, window k is traced (ed_band_cal_semi_64_w_absent_diag_trace; recal_boundary_exz may re-place it) to learn
+ *              its y_start, and the windows before it are aligned leftwards with traceback, each ending at the start of the one after it (again with a
+ *              recal_boundary_exz retry), until one fails, the gap is closed or the target start would be negative;
+ *   exit test: align_length += the rescued windows + window k; pass_qovlp(ovl, ovl - ((q_e + 1 - x_pos_s) - align_length), 0.9) must hold, else the function
+ *              returns 0 at this window (exit_win) and no later window is looked at.
+ * hao_window_rescue_ref runs this on the device over the batch hao_window_ed_ref has just aligned (its pair list, error bytes and pe; HAO_EINVAL without it or
+ * after another window-alignment call): one lane per overlap that has an open window before an aligned one, one alignment step per lane and round, one count
+ * read per round; then a thread per overlap for the verdict.  *n_rescued = rescued windows of the batch (forward + backward, up to each overlap's exit).
+ * hao_fetch_rescue: read rid's overlaps, aligned with hao_fetch_overlaps: ovlp[n], and the window records of overlap i at wins[win_off[i] .. win_off[i + 1])
+ * in ascending window order (pointers valid until the next call on the context).  Records exist for rescued windows and for the aligned windows that were
+ * traced (HAO_RESCUE_ANCHOR: y_start known, y_end / err possibly re-placed); none beyond exit_win.
+ * HAO_RESCUE_UNTRACED in an overlap's flags: a traced alignment of a backward run (the anchor, a window, or a re-placement) fell outside the domain in which
+ * the reference's traced function stays inside its band word (HAO_ALIGN_SEMI's domain below); that run ends there and nothing is guessed.
+ * HAO_DELIVER_RESCUE in the parts of hao_overlap_batch_async runs the same stage on the slots, pairs and records of the batch's reference-placed ED stage and
+ * delivers, after every other part: a hao_rescue_ovlp_t per overlap (aligned with the hao_delivery_t's ol), n_ol + 1 offsets, and the window records in
+ * overlap and window order.  Valid only with HAO_DELIVER_ED on a context configured by hao_deliver_ed_config_ref (else HAO_EINVAL); HAO_EUNSUPP in a sharded
+ * engine.  A batch without the part keeps its arena layout and byte count.
+ *   hao_deliver_rescue: the view of a slot whose batch asked for the part, valid after hao_deliver_wait on that slot (HAO_EINVAL otherwise).
+ *   hao_unpack_rescue:  read rid's overlaps out of the three views - ovlp[n], win_off[0 .. n] counted from the read's first record, and the records.  Returns n;
+ *                       nothing is written when n exceeds cap_ovlp, the read's records exceed cap_wins, or ovlp / win_off / wins is NULL; 0 for a read outside
+ *                       the batch; UINT64_MAX for a NULL view, a view that is not reference-placed, or views that do not belong together (overlap counts,
+ *                       offsets that do not ascend or run past n_wins, a record whose window its overlap does not cover - the overlap's window range is
+ *                       rebuilt from the delivered overlap - or that lies beyond read rid's grid as len, the lengths of all reads, has it).  Pure host code, any
+ *                       thread.
+ * Not built: the cigars of rescued windows, the traced stage in reference placement, gen_extend_err_exz and everything after it in gen_hc_r_alin. */
+typedef struct { uint16_t verdict, flags; uint32_t exit_win, align_length, n_rescued; } hao_rescue_ovlp_t;      /* exit_win 0xffffffff: no early exit */
+typedef struct { int32_t y_start, y_end; uint32_t win, info; } hao_rescue_win_t;      /* win: grid window; info: err | thre << 8 | direction << 16 | flags */
+#define HAO_RESCUE_FWD 0u
+#define HAO_RESCUE_BWD 1u
+#define HAO_RESCUE_ANCHOR 2u
+#define HAO_RESCUE_DIR(info) (((info) >> 16) & 3u)
+#define HAO_RESCUE_REPLACED (1u << 18)      /* info: recal_boundary_exz's re-placement was taken */
+#define HAO_RESCUE_UNTRACED 1u              /* hao_rescue_ovlp_t.flags */
+#define HAO_DELIVER_RESCUE 32u      /* the rescue stage's results of the batch (with HAO_DELIVER_ED in reference placement; hao_deliver_rescue, hao_unpack_rescue) */
+typedef struct {
+	uint64_t n_ol, n_wins, n_rescued;      /* overlaps, window records and rescued windows (forward + backward) of the batch */
+	const hao_rescue_ovlp_t *ovlp;         /* [n_ol] */
+	const uint64_t *win_off;               /* [n_ol + 1]: records of overlap i = wins[win_off[i] .. win_off[i + 1]) */
+	const hao_rescue_win_t *wins;          /* [n_wins] */
+} hao_rescue_delivery_t;
+int hao_window_rescue_ref(hao_ctx *c, uint64_t *n_rescued);
+int hao_fetch_rescue(hao_ctx *c, uint64_t rid, const hao_rescue_ovlp_t **ovlp, uint64_t *n, const uint64_t **win_off, const hao_rescue_win_t **wins);
+int hao_deliver_rescue(hao_ctx *c, int slot, hao_rescue_delivery_t *out);
+uint64_t hao_unpack_rescue(const hao_delivery_t *d, const hao_ed_delivery_t *e, const hao_rescue_delivery_t *r, const uint32_t *len, uint64_t rid,
+                           hao_rescue_ovlp_t *ovlp, uint64_t *win_off, hao_rescue_win_t *wins, uint64_t cap_ovlp, uint64_t cap_wins);
+/* test support (host code, no context): the task of a rescue alignment as the kernel rebuilds it (window `win` of overlap z against the target from toff on;
+ * tab = hao_ref_thresholds; 0: refused), so that the tests can hold the builder against work items recorded from the reference */
+int hao_rescue_task(const hao_ovlp_t *z, uint32_t win, uint32_t window, int64_t toff, const uint8_t *tab, uint32_t target_len, hao_ed_task_t *out);
 
 /* Second variant: global alignment inside the band WITH traceback - ed_band_cal_global_64_w_trace (Levenshtein_distance.h:3370-3442) on a
  * cleared bit_extz_t followed by gen_trace(ez, thre, 1) (:903-985), the call cal_exz_global / Correct.cpp:14537 make once a window's end points are fixed.

@@ -1,0 +1,5 @@
+from simt_suite import reexport, FULL
+
+# (default selection: the small HiFi set at its own configuration and at the tight one that walks the rescue's branches, the wide-window case in which forward
+# steps fail, the streamed path on the small HiFi set, and the contracts; HAO_SIMT_FULL=1: every case the emulator can take)
+reexport(globals(), "test_gpu_rescue", drop=lambda v: not FULL and isinstance(v, (tuple, list)) and not ((v[0] == "hifi" and v[1] in (775, 64)) or v[1] == 1500))

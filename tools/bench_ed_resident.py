@@ -6,7 +6,8 @@ alternately; per batch the ED stage's device time (stage_times "ed_grid" + "ed_a
 delivered step.  usage: python tools/bench_ed_resident.py --deliver [--workload W] [--batch-reads N] [--max-batches K] [--thre T] [--reps R]
 
 --window W: the window of the diagonal grid (default 375).  --ref WINDOW,ERATE (blocking and --deliver): the same stage in REFERENCE placement (hao_window_ed_ref /
-hao_deliver_ed_config_ref: fake-cigar shift, per-window thresholds, init_waln), e.g. --ref 775,0.04 beside the diagonal stage at --window 775 and thre 31."""
+hao_deliver_ed_config_ref: fake-cigar shift, per-window thresholds, init_waln), e.g. --ref 775,0.04 beside the diagonal stage at --window 775 and thre 31.
+--rescue (blocking, with --ref): then the rescue stage (hao_window_rescue_ref) on the same batch: wall and device time per call, rescued windows, verdicts."""
 import argparse
 import json
 import os
@@ -22,6 +23,9 @@ def main():
     from hifiasm_amd.api import Engine
     argv = [x for x in sys.argv[1:]]
     ref, window = None, 375
+    rescue = "--rescue" in argv
+    if rescue:
+        argv.remove("--rescue")
     for flag in ("--ref", "--window"):
         if flag in argv:
             i = argv.index(flag); val = argv[i + 1]; del argv[i:i + 2]
@@ -41,7 +45,19 @@ def main():
         t0 = time.time(); n = run(); ts.append(time.time() - t0)
     t, r = e.fetch_ed_grid(min(n, 1_000_000))
     ok = int((r[:, 0] != 2**31 - 1).sum())
-    print(json.dumps({"workload": "bacterial5M_hifi30x", "reads": int(rs.n), "overlaps": e.batch_totals()["overlaps"], "placement": "reference" if ref else "diagonal",
+    extra = {}
+    if rescue and ref:      # the rescue stage over the batch the last primary pass left (it may run again on the same batch)
+        n_res = e.window_rescue_ref(); tr = []
+        for _ in range(reps):
+            t0 = time.time(); n_res = e.window_rescue_ref(); tr.append(time.time() - t0)
+        dev_ms = dict(e.stage_times()).get("rescue_ref")      # (before the fetches: they are calls of their own)
+        v1 = ol = 0
+        for r in range(rs.n):
+            ov, _ = e.fetch_rescue(r); v1 += int(ov["verdict"].sum()); ol += ov.shape[0]
+        extra = {"rescue_ms_per_call_best": round(min(tr) * 1e3, 3), "rescue_ms_per_call_all": [round(x * 1e3, 3) for x in tr], "rescued_windows": n_res,
+                 "rescue_device_ms": dev_ms, "verdict1_overlaps": v1, "overlaps_judged": ol,
+                 "rescue_over_ed": round(min(tr) / min(ts), 4)}
+    print(json.dumps({**extra, "workload": "bacterial5M_hifi30x", "reads": int(rs.n), "overlaps": e.batch_totals()["overlaps"], "placement": "reference" if ref else "diagonal",
                       "window": ref[0] if ref else window, "thre": None if ref else thre, "e_rate": ref[1] if ref else None, "pairs": n,
                       "ms_per_call_best": round(min(ts) * 1e3, 3), "ms_per_call_all": [round(x * 1e3, 3) for x in ts], "pairs_per_s": round(n / min(ts)),
                       "within_thre_of_first_million": ok, "what": "task generation on the device from ol->list + distance-only window alignment; nothing crosses the host but two totals"}))
