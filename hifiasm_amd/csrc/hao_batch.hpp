@@ -32,7 +32,6 @@ struct hao_ctx::Batch {
 		DevBuf<hao_ed_ovlp_sum> ed_sum;                                                               // HAO_DELIVER_ED in reference placement: the per-overlap summaries (ed_ref_summary_kernel)
 		DevBuf<hao_rs_ovlp> rs_ovlp; DevBuf<uint64_t> rs_off; DevBuf<hao_rs_win> rs_wins;                // HAO_DELIVER_RESCUE: per-overlap results, record offsets per overlap, the records (hao_rescue.cuh)
 		DevBuf<uint64_t> tr_off; DevBuf<uint16_t> tr_ps, tr_ncig, tr_cig;                            // HAO_DELIVER_TRACE: cigar entries per read, ps and entry count per pair, the entries (hao_trace_grid.cuh)
-		void release() { ed_sum.release(); tr_off.release(); tr_ps.release(); tr_ncig.release(); tr_cig.release(); ed_off.release(); ed_err.release(); ed_pe.release(); fcw_off.release(); fcw.release(); ol_out.release(); ol_wire.release(); fin_off.release(); fc_out.release(); fc_out_off.release(); ch_off.release(); cl_off.release(); qm_off.release(); hdr.release(); bits.release(); rank.release(); rank4.release(); codes.release(); exc.release(); qmz.release(); qmz_pos.release(); qmz_cnt.release(); exact.release(); }
 	} out[2];
 	int cur = 0;
 	OutSet &O() { return out[cur]; }
@@ -50,15 +49,11 @@ struct hao_ctx::Batch {
 	// host copies for fetch
 	std::vector<uint64_t> h_seg, h_fin_off, h_cl_off, h_fc_out_off; std::vector<hao_hit_t> h_hits, h_cl; std::vector<hao_ovlp_t> h_ol; std::vector<uint64_t> h_fc;
 	std::vector<uint64_t> fetch_fc_off, h_cco;
-	void release() {
-		pk_tmp.release(); if (ev_pk0) { (void)hipEventDestroy(ev_pk0); (void)hipEventDestroy(ev_pk1); ev_pk0 = ev_pk1 = nullptr; }
-		if (side_ready) { for (int x = 0; x < HAO_NCLS; ++x) { (void)hipStreamDestroy(side[x]); (void)hipEventDestroy(ev_qc[x]); (void)hipEventDestroy(ev_dp[x]); } side_ready = false; }
-		s_start.release(); s_pk.release(); a_off.release(); seg.release(); g_cnt.release(); g_off.release(); g_start.release(); ch_base.release(); cl_base.release();
-		fc_base.release(); fcs.release(); fc_raw.release(); ol_fc_off.release(); cc_off.release(); cc.release(); fc_final.release(); fcf_off.release();
-		nch64.release(); g_tmp.release(); cls_cc.release(); cls_co.release(); glist.release(); g_cls.release(); slow.release(); ovf_list.release(); q_pos.release(); q_cnt.release(); s_n.release(); g_read.release(); wgt.release(); nch.release(); nout.release(); perm.release(); n_final.release(); fclen.release();
-		tm.release(); key_sc.release(); key_xs.release(); key_al.release(); key_tmp.release(); hits.release(); ohits.release(); cl.release(); f.release(); ii.release(); p.release(); t.release(); rec.release(); ol.release(); cd.release(); pk_cnt.release(); pk_ecnt.release(); pk_erank.release(); hq.release(); ohq.release(); hcode.release(); out[0].release(); out[1].release();
-		ed_nwin.release(); ed_wbase.release(); ed_wcnt.release(); ed_woff.release(); ed_pairs.release();
-		if (dl_ready) { (void)hipStreamSynchronize(copy_stream); (void)hipStreamDestroy(copy_stream); for (int x = 0; x < 2; ++x) { (void)hipEventDestroy(ev_ready[x]); (void)hipEventDestroy(ev_done[x]); (void)hipEventDestroy(ev_cstart[x]); arena_free(x); } dl_ready = false; }
+	// the non-memory part: events and streams, the copy stream synchronised before the arenas go; the buffers free themselves after it
+	~Batch() {
+		if (ev_pk0) { (void)hipEventDestroy(ev_pk0); (void)hipEventDestroy(ev_pk1); }
+		if (side_ready) { for (int x = 0; x < HAO_NCLS; ++x) { (void)hipStreamDestroy(side[x]); (void)hipEventDestroy(ev_qc[x]); (void)hipEventDestroy(ev_dp[x]); } }
+		if (dl_ready) { (void)hipStreamSynchronize(copy_stream); (void)hipStreamDestroy(copy_stream); for (int x = 0; x < 2; ++x) { (void)hipEventDestroy(ev_ready[x]); (void)hipEventDestroy(ev_done[x]); (void)hipEventDestroy(ev_cstart[x]); arena_free(x); } }
 	}
 };
 
@@ -187,36 +182,6 @@ static int hao_exact_run(hao_ctx *c)
 	return HAO_OK;
 }
 
-// f3 on the device end to end (hao_grid.cuh): window / candidate pairs of the current batch's final ol->list on the grid, in text order, into c->al_task; then the distance-only
-// window alignment over them where they lie (hao_al_ed_resident, hao_f3.hip): results in c->al_res.  No host round trip but the two totals.
-int hao_al_ed_resident(hao_ctx *c, uint64_t n_tasks, uint32_t nword);      // (hao_f3.hip)
-static int hao_ed_grid_run(hao_ctx *c, uint32_t wl, uint32_t thre, uint64_t *n_tasks)
-{
-	hao_ctx::Batch &B = *c->batch; *n_tasks = 0; c->al_grid_n = 0;
-	if (hao_is_sharded(c)) { hao_set_err(c, "hao_window_ed_grid needs the bases of both reads: single-device mode only"); return HAO_EUNSUPP; }
-	if (wl == 0 || thre > HAO_ED_MAX_THRE) { hao_set_err(c, "hao_window_ed_grid: window length 0 or threshold beyond the widest band"); return HAO_EINVAL; }
-	const uint64_t n = B.n; const uint32_t nword = (2 * thre + 1 + 63) / 64;
-	if (n == 0 || B.n_ol == 0) return HAO_OK;
-	DevBuf<uint64_t> &nwin = c->al_k1, &wbase = c->al_k2;      // (the upload path's key buffers: free here)
-	HIP_TRY(nwin.reserve(n + 2)); HIP_TRY(wbase.reserve(n + 2));
-	hipLaunchKernelGGL(ed_grid_nwin_kernel, dim3((unsigned)((n + 256) / 256)), dim3(256), 0, c->stream, c->d_len.p, B.lo, n, wl, nwin.p); HAO_CHECK_LAUNCH();
-	if (int rc = hao_excl_scan_u64(c, nwin.p, wbase.p, n + 1)) return rc;
-	uint64_t W = 0; HIP_TRY(hipMemcpyAsync(&W, wbase.p + n, 8, hipMemcpyDeviceToHost, c->stream)); HIP_TRY(hipStreamSynchronize(c->stream));
-	DevBuf<uint64_t> &cnt = c->al_path, off; HIP_TRY(cnt.reserve(W + 2)); HIP_TRY(off.reserve(W + 2));
-	HIP_TRY(hipMemsetAsync(cnt.p + W, 0, 8, c->stream));
-	const dim3 g_((unsigned)((n + 3) / 4)), b_(256);
-	hipLaunchKernelGGL((ed_grid_kernel<ED_GRID_COUNT>), g_, b_, 0, c->stream, B.O().ol_out.p, B.O().fin_off.p, c->d_len.p, B.lo, n, wl, thre, nword, wbase.p, cnt.p, (hao_ed_task_t*)nullptr, (hao_ed_pair*)nullptr, hao_ref_args{nullptr, nullptr, nullptr}); HAO_CHECK_LAUNCH();
-	if (int rc = hao_excl_scan_u64(c, cnt.p, off.p, W + 1)) return rc;
-	uint64_t T = 0; HIP_TRY(hipMemcpyAsync(&T, off.p + W, 8, hipMemcpyDeviceToHost, c->stream)); HIP_TRY(hipStreamSynchronize(c->stream));
-	if (T >= (1ULL << 32)) { hao_set_err(c, "hao_window_ed_grid: more than 2^32 pairs in one batch"); return HAO_EUNSUPP; }
-	HIP_TRY(c->al_task.reserve(T + 1));
-	if (T) { hipLaunchKernelGGL((ed_grid_kernel<ED_GRID_TASKS>), g_, b_, 0, c->stream, B.O().ol_out.p, B.O().fin_off.p, c->d_len.p, B.lo, n, wl, thre, nword, wbase.p, off.p, c->al_task.p, (hao_ed_pair*)nullptr, hao_ref_args{nullptr, nullptr, nullptr}); HAO_CHECK_LAUNCH(); }
-	HIP_TRY(hipStreamSynchronize(c->stream));      // (off is a local buffer)
-	off.release();
-	*n_tasks = T; c->al_grid_n = T;
-	return T ? hao_al_ed_resident(c, T, nword) : HAO_OK;
-}
-
 // ---- reference placement (hao_grid_pair.cuh: hao_ref_pair; hao_grid.cuh: the kernels) ----
 // the front of a reference-placed stage over the current batch's final ol->list: covered windows per overlap and their scan (the CSR of the shifts), one peek
 // at their total, the shifts (ed_ref_shift_kernel), the CSR slots' error bytes preset to "none".  tab = the threshold table on the device.
@@ -245,6 +210,73 @@ static int hao_ed_ref_upload(hao_ctx *c, uint32_t wl, double e_rate, DevBuf<uint
 	return HAO_OK;
 }
 
+// ---- the grid's pair list, built in one place for the four stages below ----
+// the one launch site of ed_grid_kernel: the instance of run-time `out` (ED_GRID_*) and `place` (HAO_PLACE_*) over the current batch's final ol->list
+static void hao_ed_grid_launch(hao_ctx *c, int out, uint32_t place, uint32_t wl, uint32_t thre, uint32_t nword, const uint64_t *wbase, uint64_t *cnt_or_off, hao_ed_task_t *tasks, hao_ed_pair *pairs, hao_ref_args A)
+{
+	hao_ctx::Batch &B = *c->batch; hao_ctx::Batch::OutSet &O = B.O();
+	auto go = [&](auto kernel) { hipLaunchKernelGGL(kernel, dim3((unsigned)((B.n + 3) / 4)), dim3(256), 0, c->stream, O.ol_out.p, O.fin_off.p, c->d_len.p, B.lo, B.n, wl, thre, nword, wbase, cnt_or_off, tasks, pairs, A); };
+	switch (out * 2 + (place == HAO_PLACE_REF)) {
+	case ED_GRID_COUNT * 2: go(ed_grid_kernel<ED_GRID_COUNT, HAO_PLACE_DIAG>); break;
+	case ED_GRID_COUNT * 2 + 1: go(ed_grid_kernel<ED_GRID_COUNT, HAO_PLACE_REF>); break;
+	case ED_GRID_TASKS * 2: go(ed_grid_kernel<ED_GRID_TASKS, HAO_PLACE_DIAG>); break;
+	case ED_GRID_TASKS * 2 + 1: go(ed_grid_kernel<ED_GRID_TASKS, HAO_PLACE_REF>); break;
+	case ED_GRID_PAIRS * 2: go(ed_grid_kernel<ED_GRID_PAIRS, HAO_PLACE_DIAG>); break;
+	default: go(ed_grid_kernel<ED_GRID_PAIRS, HAO_PLACE_REF>); break;
+	}
+}
+// what hao_ed_grid_pairs hands back: pairs, grid windows, and in reference placement the covered windows (CSR slots), the unresolved ones and the kernels'
+// arguments (CSR, shifts, table); wbase / woff = the scans of windows per read and pairs per window (ed_read_off_kernel's input)
+struct hao_grid_list { uint64_t T = 0, W = 0, Wc = 0, UR = 0; hao_ref_args A{nullptr, nullptr, nullptr}; const uint64_t *wbase = nullptr, *woff = nullptr; };
+// The pair list of the current batch's final ol->list on the window grid, in text order: windows per read (their total from the host's copy of the lengths: no
+// device round trip) and their scan, in reference placement the shifts (hao_ed_ref_front; tab = the threshold table on the device), pairs per window
+// (ed_grid_kernel) and their scan, the totals, then the fill pass into `tasks` (with, in reference placement, the (overlap, window) list in `pairs` from the same
+// pass) or, without `tasks`, into `pairs`; both are sized here.  Scratch: B.ed_* (compute stream only).  The totals come through mapped host memory
+// (hao_peek_kernel, slots 32 and 38), not a copy - a device-to-host copy would queue behind the previous batch's delivery on the DMA engine - and cost one
+// synchronisation (reference placement: one more, for the covered windows, in hao_ed_ref_front).  who: the caller's name in the error string.  No timer marks.
+// Fill mode: `tasks` alone - ED_GRID_TASKS; `pairs` alone - ED_GRID_PAIRS; both - ED_GRID_TASKS, which writes the pair list too in REFERENCE placement only (in
+// diagonal placement that kernel instance leaves `pairs` unfilled: pass one of the two there).
+static int hao_ed_grid_pairs(hao_ctx *c, const char *who, uint32_t place, uint32_t wl, uint32_t thre, uint32_t nword, const uint8_t *tab, DevBuf<hao_ed_task_t> *tasks, DevBuf<hao_ed_pair> *pairs, hao_grid_list *L)
+{
+	hao_ctx::Batch &B = *c->batch; const uint64_t n = B.n; const bool ref = place == HAO_PLACE_REF && B.n_ol;      // (no overlap: no shifts, no counter - and no pair)
+	*L = hao_grid_list();
+	for (uint64_t r = 0; r < n; ++r) L->W += (c->h_len[B.lo + r] + wl - 1) / wl;
+	const uint64_t W = L->W;
+	HIP_TRY(B.ed_nwin.reserve(n + 2)); HIP_TRY(B.ed_wbase.reserve(n + 2)); HIP_TRY(B.ed_wcnt.reserve(W + 2)); HIP_TRY(B.ed_woff.reserve(W + 2));
+	hipLaunchKernelGGL(ed_grid_nwin_kernel, dim3((unsigned)((n + 256) / 256)), dim3(256), 0, c->stream, c->d_len.p, B.lo, n, wl, B.ed_nwin.p); HAO_CHECK_LAUNCH();
+	if (int rc = hao_excl_scan_u64(c, B.ed_nwin.p, B.ed_wbase.p, n + 1)) return rc;
+	HIP_TRY(hipMemsetAsync(B.ed_wcnt.p + W, 0, 8, c->stream));
+	if (ref) { if (int rc = hao_ed_ref_front(c, wl, tab, &L->A, &L->Wc)) return rc; }
+	hao_ed_grid_launch(c, ED_GRID_COUNT, place, wl, thre, nword, B.ed_wbase.p, B.ed_wcnt.p, nullptr, nullptr, L->A); HAO_CHECK_LAUNCH();
+	if (int rc = hao_excl_scan_u64(c, B.ed_wcnt.p, B.ed_woff.p, W + 1)) return rc;
+	hipLaunchKernelGGL(hao_peek_kernel, dim3(1), dim3(64), 0, c->stream, (const unsigned long long*)(B.ed_woff.p + W), 1, c->peek_d + 32); HAO_CHECK_LAUNCH();
+	if (ref) { hipLaunchKernelGGL(hao_peek_kernel, dim3(1), dim3(64), 0, c->stream, (const unsigned long long*)c->rf.ctr.p, 1, c->peek_d + 38); HAO_CHECK_LAUNCH(); }
+	HIP_TRY(hipStreamSynchronize(c->stream));
+	const uint64_t T = c->peek_h[32];
+	if (T >= (1ULL << 32)) { hao_set_err(c, std::string(who) + ": more than 2^32 pairs in one batch"); return HAO_EUNSUPP; }
+	if (tasks) HIP_TRY(tasks->reserve(T + 1));
+	if (pairs) HIP_TRY(pairs->reserve(T + 1));
+	if (T) { hao_ed_grid_launch(c, tasks ? ED_GRID_TASKS : ED_GRID_PAIRS, place, wl, thre, nword, B.ed_wbase.p, B.ed_woff.p, tasks ? tasks->p : nullptr, pairs ? pairs->p : nullptr, L->A); HAO_CHECK_LAUNCH(); }
+	L->T = T; L->UR = ref ? c->peek_h[38] : 0; L->wbase = B.ed_wbase.p; L->woff = B.ed_woff.p;
+	return HAO_OK;
+}
+
+// f3 on the device end to end (hao_grid.cuh): window / candidate pairs of the current batch's final ol->list on the grid, in text order, into c->al_task; then the distance-only
+// window alignment over them where they lie (hao_al_ed_resident, hao_f3.hip): results in c->al_res.  No host round trip but the total.
+int hao_al_ed_resident(hao_ctx *c, uint64_t n_tasks, uint32_t nword);      // (hao_f3.hip)
+static int hao_ed_grid_run(hao_ctx *c, uint32_t wl, uint32_t thre, uint64_t *n_tasks)
+{
+	hao_ctx::Batch &B = *c->batch; *n_tasks = 0; c->al_grid_n = 0;
+	if (hao_is_sharded(c)) { hao_set_err(c, "hao_window_ed_grid needs the bases of both reads: single-device mode only"); return HAO_EUNSUPP; }
+	if (wl == 0 || thre > HAO_ED_MAX_THRE) { hao_set_err(c, "hao_window_ed_grid: window length 0 or threshold beyond the widest band"); return HAO_EINVAL; }
+	const uint32_t nword = (2 * thre + 1 + 63) / 64;
+	if (B.n == 0 || B.n_ol == 0) return HAO_OK;
+	hao_grid_list L;
+	if (int rc = hao_ed_grid_pairs(c, "hao_window_ed_grid", HAO_PLACE_DIAG, wl, thre, nword, nullptr, &c->al_task, nullptr, &L)) return rc;
+	*n_tasks = L.T; c->al_grid_n = L.T;
+	return L.T ? hao_al_ed_resident(c, L.T, nword) : HAO_OK;
+}
+
 // hao_window_ed_ref: hao_ed_grid_run in reference placement - tasks into c->al_task, results into c->al_res (hao_fetch_ed_grid serves them), plus the pair list,
 // the per-overlap summaries (c->rf_sum) and the count of unresolved windows
 static int hao_ed_ref_run(hao_ctx *c, uint32_t wl, double e_rate, uint64_t *n_tasks, uint64_t *unresolved)
@@ -252,43 +284,20 @@ static int hao_ed_ref_run(hao_ctx *c, uint32_t wl, double e_rate, uint64_t *n_ta
 	hao_ctx::Batch &B = *c->batch; *n_tasks = 0; if (unresolved) *unresolved = 0; c->al_grid_n = 0; c->rf_valid = false; c->rf_hvalid = false; c->rf_unres = 0; c->rs_valid = false; c->rf_T = 0;
 	if (hao_is_sharded(c)) { hao_set_err(c, "hao_window_ed_ref needs the bases of both reads: single-device mode only"); return HAO_EUNSUPP; }
 	if (!hao_ed_ref_args_ok(wl, e_rate)) { hao_set_err(c, "hao_window_ed_ref: window length 0, window + 62 beyond 16 bits, or e_rate outside (0, 1)"); return HAO_EINVAL; }
-	const uint64_t n = B.n;
-	if (n == 0 || B.n_ol == 0) { c->rf_valid = true; return HAO_OK; }
+	if (B.n == 0 || B.n_ol == 0) { c->rf_valid = true; return HAO_OK; }
 	if (B.n_ol >= (1ULL << 32)) { hao_set_err(c, "hao_window_ed_ref: more than 2^32 overlaps in one batch"); return HAO_EUNSUPP; }
 	if (c->rf_tab_wl != wl || c->rf_tab_erate != e_rate) { c->rf_tab_wl = 0; if (int rc = hao_ed_ref_upload(c, wl, e_rate, c->rf_tab)) return rc; c->rf_tab_wl = wl; c->rf_tab_erate = e_rate; }
 	hao_ctx::Batch::OutSet &O = B.O();
-	hao_ref_args A; uint64_t Wc = 0;
-	if (int rc = hao_ed_ref_front(c, wl, c->rf_tab.p, &A, &Wc)) return rc;
-	DevBuf<uint64_t> &nwin = c->al_k1, &wbase = c->al_k2;
-	HIP_TRY(nwin.reserve(n + 2)); HIP_TRY(wbase.reserve(n + 2));
-	hipLaunchKernelGGL(ed_grid_nwin_kernel, dim3((unsigned)((n + 256) / 256)), dim3(256), 0, c->stream, c->d_len.p, B.lo, n, wl, nwin.p); HAO_CHECK_LAUNCH();
-	if (int rc = hao_excl_scan_u64(c, nwin.p, wbase.p, n + 1)) return rc;
-	uint64_t W = 0; HIP_TRY(hipMemcpyAsync(&W, wbase.p + n, 8, hipMemcpyDeviceToHost, c->stream)); HIP_TRY(hipStreamSynchronize(c->stream));
-	DevBuf<uint64_t> &cnt = c->al_path, off; HIP_TRY(cnt.reserve(W + 2)); HIP_TRY(off.reserve(W + 2));
-	HIP_TRY(hipMemsetAsync(cnt.p + W, 0, 8, c->stream));
-	const dim3 g_((unsigned)((n + 3) / 4)), b_(256);
-	hipLaunchKernelGGL((ed_grid_kernel<ED_GRID_COUNT, HAO_PLACE_REF>), g_, b_, 0, c->stream, O.ol_out.p, O.fin_off.p, c->d_len.p, B.lo, n, wl, 0u, 1u, wbase.p, cnt.p, (hao_ed_task_t*)nullptr, (hao_ed_pair*)nullptr, A); HAO_CHECK_LAUNCH();
-	if (int rc = hao_excl_scan_u64(c, cnt.p, off.p, W + 1)) { off.release(); return rc; }
-	uint64_t T = 0, UR = 0;
-	hipError_t e1 = hipMemcpyAsync(&T, off.p + W, 8, hipMemcpyDeviceToHost, c->stream), e2 = hipMemcpyAsync(&UR, c->rf.ctr.p, 8, hipMemcpyDeviceToHost, c->stream), e3 = hipStreamSynchronize(c->stream);
-	if (e1 != hipSuccess || e2 != hipSuccess || e3 != hipSuccess) { off.release(); HIP_TRY(e1); HIP_TRY(e2); HIP_TRY(e3); }
-	if (T >= (1ULL << 32)) { off.release(); hao_set_err(c, "hao_window_ed_ref: more than 2^32 pairs in one batch"); return HAO_EUNSUPP; }
-	hipError_t e4 = c->al_task.reserve(T + 1), e5 = c->rf.pairs.reserve(T + 1), e6 = c->rf_sum.reserve(B.n_ol + 1);
-	if (e4 != hipSuccess || e5 != hipSuccess || e6 != hipSuccess) { off.release(); HIP_TRY(e4); HIP_TRY(e5); HIP_TRY(e6); }
-	if (T) {
-		hipLaunchKernelGGL((ed_grid_kernel<ED_GRID_TASKS, HAO_PLACE_REF>), g_, b_, 0, c->stream, O.ol_out.p, O.fin_off.p, c->d_len.p, B.lo, n, wl, 0u, 1u, wbase.p, off.p, c->al_task.p, c->rf.pairs.p, A);      // (tasks and pair list in one pass)
-	}
-	// (not HAO_CHECK_LAUNCH as elsewhere: `off` is a local buffer the fill kernel reads, so launch error and synchronisation are collected first, `off` is
-	// released, and only then does an error return)
-	const hipError_t e7 = hipGetLastError(), e8 = hipStreamSynchronize(c->stream);
-	off.release();
-	HIP_TRY(e7); HIP_TRY(e8);
-	*n_tasks = T; c->al_grid_n = T; c->rf_T = T; c->rf_unres = UR; if (unresolved) *unresolved = UR;
+	hao_grid_list L;      // (tasks and pair list in one fill pass; threshold and band width come from the table)
+	if (int rc = hao_ed_grid_pairs(c, "hao_window_ed_ref", HAO_PLACE_REF, wl, 0, 1, c->rf_tab.p, &c->al_task, &c->rf.pairs, &L)) return rc;
+	HIP_TRY(c->rf_sum.reserve(B.n_ol + 1));
+	const uint64_t T = L.T;
+	*n_tasks = T; c->al_grid_n = T; c->rf_T = T; c->rf_unres = L.UR; if (unresolved) *unresolved = L.UR;
 	if (T) {
 		if (int rc = hao_al_ed_resident(c, T, 1)) return rc;
-		hipLaunchKernelGGL(ed_ref_scatter_kernel, dim3((unsigned)((T + 255) / 256)), dim3(256), 0, c->stream, O.ol_out.p, c->rf.pairs.p, c->al_res.p, T, wl, A.win_off, c->rf.werr.p); HAO_CHECK_LAUNCH();
+		hipLaunchKernelGGL(ed_ref_scatter_kernel, dim3((unsigned)((T + 255) / 256)), dim3(256), 0, c->stream, O.ol_out.p, c->rf.pairs.p, c->al_res.p, T, wl, L.A.win_off, c->rf.werr.p); HAO_CHECK_LAUNCH();
 	}
-	hipLaunchKernelGGL(ed_ref_summary_kernel, dim3((unsigned)((B.n_ol + 255) / 256)), dim3(256), 0, c->stream, O.ol_out.p, B.n_ol, wl, A.win_off, c->rf.werr.p, c->rf_sum.p); HAO_CHECK_LAUNCH();
+	hipLaunchKernelGGL(ed_ref_summary_kernel, dim3((unsigned)((B.n_ol + 255) / 256)), dim3(256), 0, c->stream, O.ol_out.p, B.n_ol, wl, L.A.win_off, c->rf.werr.p, c->rf_sum.p); HAO_CHECK_LAUNCH();
 	c->rf_valid = true;
 	return HAO_OK;
 }
@@ -320,48 +329,20 @@ static int hao_ed_deliver_run(hao_ctx *c)
 	hao_ctx::Batch &B = *c->batch; hao_ctx::Batch::OutSet &O = B.O(); const uint64_t n = B.n;
 	const uint32_t wl = c->ded_window, thre = c->ded_thre, nword = (2 * thre + 1 + 63) / 64;
 	B.ed_n = 0; B.ed_unres = 0;
-	// reference placement (hao_deliver_ed_config_ref): the shifts first (their own pass), then the same counting / scan / fill with hao_ref_pair, the alignment
-	// kernel's reference instance, and the per-overlap summaries into the output set.  A batch in diagonal placement runs none of it.
-	const bool ref = c->ded_place == HAO_PLACE_REF; hao_ref_args A{nullptr, nullptr, nullptr};
+	// reference placement (hao_deliver_ed_config_ref): the same pair list with hao_ref_pair, the alignment kernel's reference instance, and the per-overlap
+	// summaries into the output set.  A batch in diagonal placement runs none of it.
+	const bool ref = c->ded_place == HAO_PLACE_REF;
 	c->timer.mark("q_totals");      // (labels what ran since q_final - the totals' read-back and, with HAO_DELIVER_EXACT, the exact check - so that ed_grid / ed_align time the ED stage alone)
 	if (B.n_ol >= (1ULL << 32)) { hao_set_err(c, "HAO_DELIVER_ED: more than 2^32 overlaps in one batch"); return HAO_EUNSUPP; }
-	uint64_t W = 0;
-	for (uint64_t r = 0; r < n; ++r) W += (c->h_len[B.lo + r] + wl - 1) / wl;
-	HIP_TRY(B.ed_nwin.reserve(n + 2)); HIP_TRY(B.ed_wbase.reserve(n + 2)); HIP_TRY(B.ed_wcnt.reserve(W + 2)); HIP_TRY(B.ed_woff.reserve(W + 2)); HIP_TRY(O.ed_off.reserve(n + 2));
-	hipLaunchKernelGGL(ed_grid_nwin_kernel, dim3((unsigned)((n + 256) / 256)), dim3(256), 0, c->stream, c->d_len.p, B.lo, n, wl, B.ed_nwin.p); HAO_CHECK_LAUNCH();
-	if (int rc = hao_excl_scan_u64(c, B.ed_nwin.p, B.ed_wbase.p, n + 1)) return rc;
-	HIP_TRY(hipMemsetAsync(B.ed_wcnt.p + W, 0, 8, c->stream));
-	const dim3 g_((unsigned)((n + 3) / 4)), b_(256);
-	if (ref) {
-		uint64_t Wc = 0; HIP_TRY(O.ed_sum.reserve(B.n_ol + 1));
-		if (B.n_ol) { if (int rc = hao_ed_ref_front(c, wl, c->ded_tab.p, &A, &Wc)) return rc; }
-		B.rs_wc = Wc;
-		hipLaunchKernelGGL((ed_grid_kernel<ED_GRID_COUNT, HAO_PLACE_REF>), g_, b_, 0, c->stream, O.ol_out.p, O.fin_off.p, c->d_len.p, B.lo, n, wl, thre, nword, B.ed_wbase.p, B.ed_wcnt.p, (hao_ed_task_t*)nullptr, (hao_ed_pair*)nullptr, A); HAO_CHECK_LAUNCH();
-		if (B.n_ol) { hipLaunchKernelGGL(hao_peek_kernel, dim3(1), dim3(64), 0, c->stream, (const unsigned long long*)c->rf.ctr.p, 1, c->peek_d + 38); HAO_CHECK_LAUNCH(); } else c->peek_h[38] = 0;
-	} else {
-	hipLaunchKernelGGL((ed_grid_kernel<ED_GRID_COUNT>), g_, b_, 0, c->stream, O.ol_out.p, O.fin_off.p, c->d_len.p, B.lo, n, wl, thre, nword, B.ed_wbase.p, B.ed_wcnt.p, (hao_ed_task_t*)nullptr, (hao_ed_pair*)nullptr, hao_ref_args{nullptr, nullptr, nullptr}); HAO_CHECK_LAUNCH();
-	}
-	if (int rc = hao_excl_scan_u64(c, B.ed_wcnt.p, B.ed_woff.p, W + 1)) return rc;
-	hipLaunchKernelGGL(ed_read_off_kernel, dim3((unsigned)((n + 256) / 256)), dim3(256), 0, c->stream, B.ed_wbase.p, B.ed_woff.p, n, O.ed_off.p); HAO_CHECK_LAUNCH();
-	// the total through mapped host memory, not a copy: a device-to-host copy would queue behind the previous batch's delivery on the DMA engine (hao_peek_kernel)
-	hipLaunchKernelGGL(hao_peek_kernel, dim3(1), dim3(64), 0, c->stream, (const unsigned long long*)(B.ed_woff.p + W), 1, c->peek_d + 32); HAO_CHECK_LAUNCH();
-	HIP_TRY(hipStreamSynchronize(c->stream));
-	const uint64_t T = c->peek_h[32];
-	if (T >= (1ULL << 32)) { hao_set_err(c, "HAO_DELIVER_ED: more than 2^32 pairs in one batch"); return HAO_EUNSUPP; }
-	HIP_TRY(B.ed_pairs.reserve(T + 1)); HIP_TRY(O.ed_err.reserve(T + 64)); HIP_TRY(O.ed_pe.reserve(T + 64));
-	if (ref) {
-		B.ed_unres = c->peek_h[38];
-		if (T) { hipLaunchKernelGGL((ed_grid_kernel<ED_GRID_PAIRS, HAO_PLACE_REF>), g_, b_, 0, c->stream, O.ol_out.p, O.fin_off.p, c->d_len.p, B.lo, n, wl, thre, nword, B.ed_wbase.p, B.ed_woff.p, (hao_ed_task_t*)nullptr, B.ed_pairs.p, A); HAO_CHECK_LAUNCH(); }
-		c->timer.mark("ed_grid");
-		if (T) { if (int rc = hao_al_ed_deliver(c, O.ol_out.p, B.ed_pairs.p, T, wl, thre, O.ed_err.p, O.ed_pe.p, HAO_PLACE_REF, A, c->rf.werr.p)) return rc; }
-		if (B.n_ol) { hipLaunchKernelGGL(ed_ref_summary_kernel, dim3((unsigned)((B.n_ol + 255) / 256)), dim3(256), 0, c->stream, O.ol_out.p, B.n_ol, wl, A.win_off, c->rf.werr.p, O.ed_sum.p); HAO_CHECK_LAUNCH(); }
-		c->timer.mark("ed_align");
-		B.ed_n = T;
-		return HAO_OK;
-	}
-	if (T) { hipLaunchKernelGGL((ed_grid_kernel<ED_GRID_PAIRS>), g_, b_, 0, c->stream, O.ol_out.p, O.fin_off.p, c->d_len.p, B.lo, n, wl, thre, nword, B.ed_wbase.p, B.ed_woff.p, (hao_ed_task_t*)nullptr, B.ed_pairs.p, hao_ref_args{nullptr, nullptr, nullptr}); HAO_CHECK_LAUNCH(); }
+	HIP_TRY(O.ed_off.reserve(n + 2)); if (ref) HIP_TRY(O.ed_sum.reserve(B.n_ol + 1));
+	hao_grid_list L;
+	if (int rc = hao_ed_grid_pairs(c, "HAO_DELIVER_ED", c->ded_place, wl, thre, nword, c->ded_tab.p, nullptr, &B.ed_pairs, &L)) return rc;
+	const uint64_t T = L.T; B.ed_unres = L.UR; if (ref) B.rs_wc = L.Wc;
+	HIP_TRY(O.ed_err.reserve(T + 64)); HIP_TRY(O.ed_pe.reserve(T + 64));
+	hipLaunchKernelGGL(ed_read_off_kernel, dim3((unsigned)((n + 256) / 256)), dim3(256), 0, c->stream, L.wbase, L.woff, n, O.ed_off.p); HAO_CHECK_LAUNCH();
 	c->timer.mark("ed_grid");
-	if (T) { if (int rc = hao_al_ed_deliver(c, O.ol_out.p, B.ed_pairs.p, T, wl, thre, O.ed_err.p, O.ed_pe.p)) return rc; }
+	if (T) { if (int rc = hao_al_ed_deliver(c, O.ol_out.p, B.ed_pairs.p, T, wl, thre, O.ed_err.p, O.ed_pe.p, c->ded_place, L.A, ref ? c->rf.werr.p : nullptr)) return rc; }
+	if (ref && B.n_ol) { hipLaunchKernelGGL(ed_ref_summary_kernel, dim3((unsigned)((B.n_ol + 255) / 256)), dim3(256), 0, c->stream, O.ol_out.p, B.n_ol, wl, L.A.win_off, c->rf.werr.p, O.ed_sum.p); HAO_CHECK_LAUNCH(); }
 	c->timer.mark("ed_align");
 	B.ed_n = T;
 	return HAO_OK;
@@ -415,22 +396,10 @@ static int hao_trace_grid_run(hao_ctx *c, uint32_t wl, uint32_t thre, uint64_t o
 	c->tg_wl = wl; c->tg_thre = thre; c->tg_n = c->tg_nsel = c->tg_ncig = c->tg_nuntr = 0;
 	if (n == 0 || B.n_ol == 0) { c->tg_valid = true; return HAO_OK; }
 	if (B.n_ol >= (1ULL << 32)) { hao_set_err(c, "hao_window_trace_grid: more than 2^32 overlaps in one batch"); return HAO_EUNSUPP; }
-	// the pair list as the delivery path forms it (B.ed_* scratch: compute stream only), into the context's own list
-	uint64_t W = 0;
-	for (uint64_t r = 0; r < n; ++r) W += (c->h_len[B.lo + r] + wl - 1) / wl;
-	HIP_TRY(B.ed_nwin.reserve(n + 2)); HIP_TRY(B.ed_wbase.reserve(n + 2)); HIP_TRY(B.ed_wcnt.reserve(W + 2)); HIP_TRY(B.ed_woff.reserve(W + 2));
-	hipLaunchKernelGGL(ed_grid_nwin_kernel, dim3((unsigned)((n + 256) / 256)), dim3(256), 0, c->stream, c->d_len.p, B.lo, n, wl, B.ed_nwin.p); HAO_CHECK_LAUNCH();
-	if (int rc = hao_excl_scan_u64(c, B.ed_nwin.p, B.ed_wbase.p, n + 1)) return rc;
-	HIP_TRY(hipMemsetAsync(B.ed_wcnt.p + W, 0, 8, c->stream));
-	const dim3 g_((unsigned)((n + 3) / 4)), b_(256);
-	hipLaunchKernelGGL((ed_grid_kernel<ED_GRID_COUNT>), g_, b_, 0, c->stream, O.ol_out.p, O.fin_off.p, c->d_len.p, B.lo, n, wl, thre, nword, B.ed_wbase.p, B.ed_wcnt.p, (hao_ed_task_t*)nullptr, (hao_ed_pair*)nullptr, hao_ref_args{nullptr, nullptr, nullptr}); HAO_CHECK_LAUNCH();
-	if (int rc = hao_excl_scan_u64(c, B.ed_wcnt.p, B.ed_woff.p, W + 1)) return rc;
-	hipLaunchKernelGGL(hao_peek_kernel, dim3(1), dim3(64), 0, c->stream, (const unsigned long long*)(B.ed_woff.p + W), 1, c->peek_d + 32); HAO_CHECK_LAUNCH();
-	HIP_TRY(hipStreamSynchronize(c->stream));
-	const uint64_t T = c->peek_h[32];
-	if (T >= (1ULL << 32)) { hao_set_err(c, "hao_window_trace_grid: more than 2^32 pairs in one batch"); return HAO_EUNSUPP; }
-	HIP_TRY(c->tg_pairs.reserve(T + 1)); HIP_TRY(c->tg_err.reserve(T + 64)); HIP_TRY(c->tg_pe.reserve(T + 64)); HIP_TRY(c->tg_ps.reserve(T + 64)); HIP_TRY(c->tg_ncig16.reserve(T + 64));
-	if (T) { hipLaunchKernelGGL((ed_grid_kernel<ED_GRID_PAIRS>), g_, b_, 0, c->stream, O.ol_out.p, O.fin_off.p, c->d_len.p, B.lo, n, wl, thre, nword, B.ed_wbase.p, B.ed_woff.p, (hao_ed_task_t*)nullptr, c->tg_pairs.p, hao_ref_args{nullptr, nullptr, nullptr}); HAO_CHECK_LAUNCH(); }
+	hao_grid_list L;      // (the pair list as the delivery path forms it, into the context's own list)
+	if (int rc = hao_ed_grid_pairs(c, "hao_window_trace_grid", HAO_PLACE_DIAG, wl, thre, nword, nullptr, nullptr, &c->tg_pairs, &L)) return rc;
+	const uint64_t T = L.T;
+	HIP_TRY(c->tg_err.reserve(T + 64)); HIP_TRY(c->tg_pe.reserve(T + 64)); HIP_TRY(c->tg_ps.reserve(T + 64)); HIP_TRY(c->tg_ncig16.reserve(T + 64));
 	c->timer.mark("ed_grid");
 	if (T) { if (int rc = hao_al_ed_deliver(c, O.ol_out.p, c->tg_pairs.p, T, wl, thre, c->tg_err.p, c->tg_pe.p)) return rc; }
 	c->timer.mark("ed_align");

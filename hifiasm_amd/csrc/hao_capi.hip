@@ -51,15 +51,14 @@ int hao_create(int device, const hao_opt_t *opt, hao_ctx **out)
 void hao_destroy(hao_ctx *c)
 {
 	if (!c) return;
-	(void)hipSetDevice(c->device);
+	(void)hipSetDevice(c->device);      // (before anything frees)
 	(void)hipStreamSynchronize(c->stream);
-	hao_batch_free(c);
-	if (c->comm) { if (c->comm->nccl) ncclCommDestroy(c->comm->nccl); c->comm->release(); delete c->comm; c->comm = nullptr; }
-	// DevBuf members are released explicitly (no destructors: the struct is POD-ish on purpose)
-	hao_release_all(c);
-	(void)hipStreamDestroy(c->stream);
-	if (c->peek_h) (void)hipHostFree(c->peek_h);
-	delete c;
+	delete c->batch; c->batch = nullptr;
+	if (c->comm) { if (c->comm->nccl) ncclCommDestroy(c->comm->nccl); delete c->comm; c->comm = nullptr; }
+	const hipStream_t st = c->stream; unsigned long long *const peek_h = c->peek_h;
+	delete c;      // (every DevBuf frees itself)
+	(void)hipStreamDestroy(st);
+	if (peek_h) (void)hipHostFree(peek_h);
 }
 
 const char *hao_last_error(const hao_ctx *c) { return c ? c->err.c_str() : "null ctx"; }

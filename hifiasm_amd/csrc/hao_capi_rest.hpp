@@ -1,23 +1,5 @@
-// remaining C ABI entry points + resource release
+// remaining C ABI entry points
 #pragma once
-
-static void hao_batch_free(hao_ctx *c) { if (c->batch) { c->batch->release(); delete c->batch; c->batch = nullptr; } }
-
-static void hao_release_all(hao_ctx *c)
-{
-	c->d_packed.release(); c->d_pk_off.release(); c->d_len.release(); c->d_len_all.release(); c->d_nsite_off.release(); c->d_nsite.release();
-	c->d_ft_keys.release(); c->d_ft_vals.release(); c->d_ft_bucket.release(); c->d_ft_hbit.release(); c->d_ft_hslot.release();
-	c->d_tile_off.release(); c->d_tile_ord.release(); c->d_n_runs.release(); c->d_tot_l.release(); c->d_chunk_off.release(); c->d_chunk_cnt64.release();
-	c->d_scalar_flag.release(); c->d_scalar_list.release(); c->d_pool_x.release(); c->d_pool_info.release(); c->d_pool_ord.release(); c->d_cursor.release(); c->d_err.release();
-	c->d_chunk_base.release(); c->d_chunk_dst.release(); c->d_chunk_cnt.release(); c->d_g_x.release(); c->d_g_info.release(); c->d_g_ord.release(); c->d_g_off.release();
-	c->d_new_n.release(); c->d_new_n64.release(); c->d_mz_x.release(); c->d_mz_info.release(); c->d_mz_off.release(); c->d_tmp.release(); c->d_ring.release(); c->d_ringord.release(); c->d_cnt_ws.release();
-	c->w_ukeys.release(); c->w_flag.release(); c->w_kpos.release(); c->w_ustart.release(); c->w_ucnt.release(); c->w_hist.release(); c->w_ok.release(); c->w_ok2.release(); c->w_oi.release(); c->w_oi2.release();
-	c->w_lkv2.release(); c->w_s40_list.release(); c->w_s40_o.release(); c->w_s40_x.release(); c->w_s40_cnt.release(); c->d_ix_lk.release(); c->w_runid.release(); c->d_ix_mz_x.release(); c->d_ix_mz_info.release(); c->d_ix_mz_off.release(); c->d_ix_sx.release(); c->d_ix_sinfo.release();
-	c->d_ix_keys.release(); c->d_ix_start.release(); c->d_ix_cnt.release(); c->d_ix_bucket.release();
-	c->al_task.release(); c->al_k1.release(); c->al_k2.release(); c->al_path.release(); c->al_i1.release(); c->al_order.release(); c->al_sel.release(); c->al_res.release(); c->al_tres.release(); c->al_want.release(); c->al_cig.release();
-	c->rf.release(); c->ded_tab.release(); c->rf_tab.release(); c->rf_sum.release(); c->rf_valid = false; c->rs.release(); c->rs_valid = false;
-	c->tg.release(); c->tg_pairs.release(); c->tg_err.release(); c->tg_pe.release(); c->tg_ps.release(); c->tg_ncig16.release(); c->tg_cig.release(); c->tg_valid = false;
-}
 
 #include <atomic>
 #include <new>
@@ -367,7 +349,7 @@ int hao_fetch_trace_grid(hao_ctx *c, hao_ed_task_t *tasks, hao_trace_result_t *r
 	HIP_TRY(hipSetDevice(c->device));
 	const uint64_t n = std::min<uint64_t>(cap_pairs, c->tg_n);
 	DevBuf<hao_ed_task_t> dt; DevBuf<hao_trace_result_t> dr; DevBuf<uint64_t> doff;
-	auto done = [&](int rc) { HIP_TRY(hipStreamSynchronize(c->stream)); dt.release(); dr.release(); doff.release(); return rc; };
+	auto done = [&](int rc) { HIP_TRY(hipStreamSynchronize(c->stream)); return rc; };
 	if (n && (tasks || res)) {
 		HIP_TRY(dt.reserve(n)); HIP_TRY(dr.reserve(n));
 		if (int rc = hao_al_trace_grid_expand(c, c->batch->O().ol_out.p, n, dt.p, dr.p)) return done(rc);
@@ -697,7 +679,6 @@ int hao_batch_digest(hao_ctx *c, uint64_t *out, uint64_t *out_kh)
 	HIP_TRY(hipMemcpyAsync(out, d.p, n * 8, hipMemcpyDeviceToHost, c->stream));
 	if (out_kh) HIP_TRY(hipMemcpyAsync(out_kh, d.p + n, n * 8, hipMemcpyDeviceToHost, c->stream));
 	HIP_TRY(hipStreamSynchronize(c->stream));
-	d.release();
 	return HAO_OK;
 }
 
@@ -738,7 +719,6 @@ int hao_selftest_sortbits(hao_ctx *c, uint64_t n, uint64_t out[4])
 		if (hipMemcpyAsync(&hb, bad.p, 8, hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) rc = HAO_ENODEV;
 		out[0] = hb; out[1] = c->peek_h[16]; out[2] = c->peek_h[17]; out[3] = c->peek_h[18];
 	}
-	x.release(); s1.release(); s2.release(); o.release(); o1.release(); o2.release(); bad.release();
 	return rc;
 }
 
@@ -772,7 +752,6 @@ int hao_selftest_rocprim(uint64_t n, uint64_t out[2])
 		for (uint64_t i = 0; i < n; ++i) if (hv[i] >= n || hx[i] != hao_hash64(hv[i] * 0x9E3779B97F4A7C15ULL + 12345)) ++bad;      // a permutation of the input pairs
 		out[which] = bad;
 	}
-	x.release(); v.release(); x2.release(); v2.release(); gx.release(); gv.release(); ok.release(); ok2.release(); oi.release(); oi2.release(); tmp.release();
 	return HAO_OK;
 }
 
@@ -801,7 +780,6 @@ int hao_selftest_big(uint64_t n, uint64_t out[3])
 		out[2] = hao_dbg_reduce(c, rocprim::make_transform_iterator(uc.p, hao_not8()), out[0], rocprim::plus<uint64_t>());
 	}
 	HIP_TRY(hipDeviceSynchronize());
-	k.release(); uk.release(); uc.release(); c->d_cursor.release(); c->d_tmp.release();
 	return HAO_OK;
 }
 

@@ -26,7 +26,6 @@ struct hao_comm {
 	DevBuf<char> ag_tmp;      // padded slots of the balanced all-gather-v
 	DevBuf<uint64_t> sc_a, sc_b;      // scratch of the small host-value collectives (allocated once: no hipMalloc / hipFree on the timed path)
 	bool active() const { return world > 1 || nccl || loop; }
-	void release() { ag_tmp.release(); sc_a.release(); sc_b.release(); }
 };
 static bool hao_comm_is_active(const hao_comm *cm) { return cm->active(); }
 

@@ -12,9 +12,14 @@
 struct hao_ctx;
 static void hao_set_err(hao_ctx *c, const std::string &m);
 
-// grow-only device buffer
+// grow-only device buffer that owns its memory: freed when it goes out of scope (or with its context), movable, not copyable
 template<typename T> struct DevBuf {
 	T *p = nullptr; size_t cap = 0; bool borrowed = false;      // borrowed: a read-only view of another engine's buffer (hao_attach) - never freed or grown here
+	DevBuf() = default;
+	DevBuf(const DevBuf&) = delete; DevBuf &operator=(const DevBuf&) = delete;
+	DevBuf(DevBuf &&o) noexcept : p(o.p), cap(o.cap), borrowed(o.borrowed) { o.p = nullptr; o.cap = 0; o.borrowed = false; }
+	DevBuf &operator=(DevBuf &&o) noexcept { if (this != &o) { release(); p = o.p; cap = o.cap; borrowed = o.borrowed; o.p = nullptr; o.cap = 0; o.borrowed = false; } return *this; }
+	~DevBuf() { release(); }
 	hipError_t reserve(size_t n) {
 		if (n <= cap) return hipSuccess;
 		if (borrowed) return hipErrorInvalidValue;
@@ -39,7 +44,7 @@ template<typename T> struct DevBuf {
 	void borrow(const DevBuf<T> &o) { release(); p = o.p; cap = o.cap; borrowed = o.p != nullptr; }
 };
 
-static bool hao_dbg_sync = false;      // HAO_DBG_PRINT=sync (hao_switches::load): wait after every stage and say its name - localises a device fault
+inline bool hao_dbg_sync = false;      // HAO_DBG_PRINT=sync (hao_switches::load): wait after every stage and say its name - localises a device fault
 struct StageTimer {
 	std::vector<std::string> names; std::vector<hipEvent_t> ev; std::vector<double> host_t; hipStream_t st = nullptr;
 	static double now() { struct timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return ts.tv_sec + 1e-9 * ts.tv_nsec; }
@@ -170,7 +175,6 @@ struct hao_ctx {
 	uint32_t ded_place = 0; double ded_erate = 0; DevBuf<uint8_t> ded_tab;
 	struct RefGrid {
 		DevBuf<uint64_t> cnt, woff; DevBuf<int16_t> shift; DevBuf<uint8_t> werr; DevBuf<hao_ed_pair> pairs; DevBuf<unsigned long long> ctr;
-		void release() { cnt.release(); woff.release(); shift.release(); werr.release(); pairs.release(); ctr.release(); }
 	} rf;
 	DevBuf<uint8_t> rf_tab; uint32_t rf_tab_wl = 0; double rf_tab_erate = 0; DevBuf<hao_ed_ovlp_sum> rf_sum; std::vector<hao_ed_ovlp_sum> rf_hsum; bool rf_valid = false, rf_hvalid = false; uint64_t rf_unres = 0;
 	// the rescue stage (hao_rescue.cuh; hao_window_rescue_ref): pe per CSR slot, record region start per overlap, the states of the overlaps with an open
@@ -179,14 +183,12 @@ struct hao_ctx {
 	struct Rescue {
 		DevBuf<uint16_t> wpe; DevBuf<uint64_t> rbase, path; DevBuf<hao_rs_state> st; DevBuf<hao_rs_win> rec; DevBuf<hao_rs_ovlp> ovlp; DevBuf<unsigned long long> ctr;
 		std::vector<hao_rs_ovlp> h_ovlp; std::vector<uint64_t> h_win_off; std::vector<hao_rs_win> h_wins;
-		void release() { wpe.release(); rbase.release(); path.release(); st.release(); rec.release(); ovlp.release(); ctr.release(); }
 	} rs;
 	bool rs_valid = false, rs_hvalid = false; uint64_t rf_T = 0, rs_slots = 0, rs_rounds = 0, rs_active = 0, rs_total = 0;
 	// f3 with traceback on the grid (hao_trace_grid.cuh): the stage's scratch, compute stream only (hao_window_trace_grid and HAO_DELIVER_TRACE share it) -
 	// flags and selected pairs, entry counts and their scans, the compact array's offsets, the column scratch, the rows of one slice, two counters
 	struct TraceGrid {
 		DevBuf<uint8_t> want; DevBuf<uint32_t> sel; DevBuf<uint64_t> cnt, loc, off, path; DevBuf<uint16_t> rows; DevBuf<unsigned long long> ctr;
-		void release() { want.release(); sel.release(); cnt.release(); loc.release(); off.release(); path.release(); rows.release(); ctr.release(); }
 	} tg;
 	// hao_window_trace_grid's results, kept for hao_fetch_trace_grid (tg_valid: they belong to the current batch and no window-alignment batch has run since):
 	// the pair list, the distance-only err / pe, ps and entry count per pair, the compact cigars; pairs, traced pairs, entries, aligned but untraced pairs

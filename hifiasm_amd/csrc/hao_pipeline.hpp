@@ -4,9 +4,6 @@
 #include "hao_sketch.cuh"
 #include "hao_sketch3.cuh"
 
-static void hao_batch_free(hao_ctx *c);
-static void hao_release_all(hao_ctx *c);
-
 struct U32ToU64 { __host__ __device__ uint64_t operator()(uint32_t v) const { return v; } };
 
 __global__ void hao_chunk_count_kernel(const uint32_t *n_runs, const uint8_t *scalar_flag, uint64_t n_sel, int k, int chunk, uint64_t *cnt)

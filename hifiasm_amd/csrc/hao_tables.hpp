@@ -162,7 +162,6 @@ static int hao_sort_rle_hist(hao_ctx *c, uint64_t *d_keys, uint64_t *d_keys_alt,
 	HAO_CHECK_LAUNCH();
 	HIP_TRY(hipMemcpyAsync(hist, dh.p, HAO_N_COUNTS * 8, hipMemcpyDeviceToHost, c->stream));
 	HIP_TRY(hipStreamSynchronize(c->stream));
-	dh.release();
 	return HAO_OK;
 }
 
@@ -279,7 +278,6 @@ static int hao_bloom_filter(hao_ctx *c, uint64_t *in, uint64_t *alt, uint64_t n,
 		HAO_CHECK_LAUNCH();
 		HIP_TRY(hipStreamSynchronize(c->stream));
 		lap("replay");
-		rk.release(); rl.release(); rs.release();
 	}
 	HIP_TRY(c->d_cursor.reserve(2));
 	tb = 0;
@@ -290,7 +288,6 @@ static int hao_bloom_filter(hao_ctx *c, uint64_t *in, uint64_t *alt, uint64_t n,
 	*out = dv.alternate(); *out_alt = dv.current();
 	lap("select");
 	if (dbg) fprintf(stderr, "[bloom] %llu of %llu occurrences reach the count table\n", (unsigned long long)*n_out, (unsigned long long)n);
-	blk.release(); blk2.release(); flag.release();
 	return HAO_OK;
 }
 
@@ -535,14 +532,13 @@ static int hao_ft_run(hao_ctx *c)
 			return hao_sort_rle_hist(c, ci, ca, n_ci, ukeys, ucnt, &n_unique, c->ft_hist, &sorted, bias);
 		};
 		if (int rc = hao_comm_allreduce_i64(c, cm, c->ft_hist, HAO_N_COUNTS, local_count())) return rc;
-		rv.release(); rv2.release(); dt.release(); dc.release();
 	}
 	if (P > 1) {      // this pass's runs behind the earlier ones
 		if (all_unique + n_unique + 1 > all_keys.cap) {
 			const uint64_t want = std::max<uint64_t>((all_unique + n_unique) * (pass + 1 < P ? 2 : 1) + 64, (n_unique + 64) * (P - pass));
 			DevBuf<uint64_t> nk_; DevBuf<uint32_t> nc_; HIP_TRY(nk_.reserve_exact(want)); HIP_TRY(nc_.reserve_exact(want));
 			if (all_unique) { HIP_TRY(hipMemcpyAsync(nk_.p, all_keys.p, all_unique * 8, hipMemcpyDeviceToDevice, c->stream)); HIP_TRY(hipMemcpyAsync(nc_.p, all_cnt.p, all_unique * 4, hipMemcpyDeviceToDevice, c->stream)); HIP_TRY(hipStreamSynchronize(c->stream)); }
-			std::swap(all_keys, nk_); std::swap(all_cnt, nc_); nk_.release(); nc_.release();
+			std::swap(all_keys, nk_); std::swap(all_cnt, nc_);
 		}
 		if (n_unique) { HIP_TRY(hipMemcpyAsync(all_keys.p + all_unique, ukeys.p, n_unique * 8, hipMemcpyDeviceToDevice, c->stream)); HIP_TRY(hipMemcpyAsync(all_cnt.p + all_unique, ucnt.p, n_unique * 4, hipMemcpyDeviceToDevice, c->stream)); HIP_TRY(hipStreamSynchronize(c->stream)); }
 		all_unique += n_unique;
@@ -550,7 +546,7 @@ static int hao_ft_run(hao_ctx *c)
 	}
 	}      // passes
 	if (P > 1) {
-		kh.release(); kh2.release(); ch_tmp.release(); ch_sel.release(); ukeys.release(); ucnt.release();
+		kh.release(); kh2.release(); ch_tmp.release(); ch_sel.release(); ukeys.release(); ucnt.release();      // (peak memory: the pass buffers go before the sort below allocates its twins)
 		if (bloom && all_unique) {      // passes own sub-tables, not hash ranges: the concatenation is not sorted by key yet
 			DevBuf<uint64_t> k2; DevBuf<uint32_t> c2; HIP_TRY(k2.reserve_exact(all_unique + 1)); HIP_TRY(c2.reserve_exact(all_unique + 1));
 			size_t tb = 0; rocprim::double_buffer<uint64_t> dk(all_keys.p, k2.p); rocprim::double_buffer<uint32_t> dv(all_cnt.p, c2.p);
@@ -559,13 +555,12 @@ static int hao_ft_run(hao_ctx *c)
 			HIP_TRY(hipStreamSynchronize(c->stream));
 			if (dk.current() != all_keys.p) std::swap(all_keys, k2);
 			if (dv.current() != all_cnt.p) std::swap(all_cnt, c2);
-			k2.release(); c2.release();
 		}
 		std::swap(ukeys, all_keys); std::swap(ucnt, all_cnt); n_unique = all_unique;
 		memcpy(c->ft_hist, all_hist, sizeof(all_hist));
 	}
 	c->timer.mark("ft_count");
-	kh.release(); kh2.release();
+	kh.release(); kh2.release();      // (peak memory: the engine's largest allocations go before the table is built)
 	c->ft_peak_hom = hao_find_peaks(c->ft_hist, HAO_N_COUNTS, c->opt.min_hist_cnt, &c->ft_peak_het, hao_prior_hom(c));
 	int cutoff = (int)(c->ft_peak_hom * c->opt.high_factor);                 // htab.cpp:1160
 	if (cutoff > HAO_MAX_COUNT - 1) cutoff = HAO_MAX_COUNT - 1;
@@ -573,7 +568,7 @@ static int hao_ft_run(hao_ctx *c)
 	DevBuf<uint32_t> kcnt; uint64_t n_kept = 0;
 	const int keep_rc = hao_keep_runs(c, ukeys.p, ucnt.p, n_unique, cutoff, HAO_MAX_COUNT, c->d_ft_keys, nullptr, kcnt, &n_kept, nullptr);
 	if (keep_rc && !sharded) return keep_rc;
-	ukeys.release(); ucnt.release(); c->w_flag.release(); c->w_kpos.release(); c->w_ustart.release();      // k-mer sized scratch: do not keep it
+	ukeys.release(); ucnt.release(); c->w_flag.release(); c->w_kpos.release(); c->w_ustart.release();      // (peak memory: k-mer sized scratch goes before the table's buffers come)
 	if (sharded) {   // every rank kept its hash range: concatenation in rank order is the globally sorted table
 		hao_comm &cm = *c->comm; std::vector<uint64_t> cnts;
 		if (int rc = hao_comm_allgather_u64(c, cm, n_kept, cnts, keep_rc)) return rc;
@@ -592,9 +587,8 @@ static int hao_ft_run(hao_ctx *c)
 			HIP_TRY(hipStreamSynchronize(c->stream));
 			if (dk.current() != gk.p) std::swap(gk, gk2);
 			if (dv.current() != gc.p) std::swap(gc, gc2);
-			gk2.release(); gc2.release();
 		}
-		std::swap(c->d_ft_keys, gk); std::swap(kcnt, gc); gk.release(); gc.release();
+		std::swap(c->d_ft_keys, gk); std::swap(kcnt, gc);
 		n_kept = tot;
 	}
 	// map values (gen_hh, htab.cpp:1038-1062) as ha_ft_cnt returns them (htab.cpp:1064-1070)
@@ -613,7 +607,7 @@ static int hao_ft_run(hao_ctx *c)
 	if (int rc = hao_build_bucket(c, c->d_ft_keys.p, n_kept, 16, c->d_ft_bucket)) return rc;
 	if (int rc = hao_ft_build_hash(c, n_kept)) return rc;
 	HIP_TRY(hipStreamSynchronize(c->stream));
-	kcnt.release(); slots.release(); chunks.release(); kmer_off.release(); kh_chunk_off.release();
+	kcnt.release(); slots.release(); chunks.release(); kmer_off.release(); kh_chunk_off.release();      // (timed: inside ft_table, so that hao_ft_gen's ft_release mark keeps measuring what is left)
 	c->has_ft = true;
 	{	// ha_opt_update_cov
 		int mx = (int)(c->ft_peak_hom * c->opt.high_factor + .499);
@@ -877,7 +871,7 @@ static int hao_pt_run(hao_ctx *c)
 		}
 		HIP_TRY(hipStreamSynchronize(c->stream));
 		c->ix_n_sorted = m; c->ix_n_keys = nk; c->ix_n_pos = np;
-		lsx.release(); lsi.release(); rx.release(); ri.release(); px.release(); pi.release(); lkr.release(); lkl.release(); ai.release(); ai2.release(); pk.release(); pst.release(); pc.release(); dt.release(); dc.release();
+		lsx.release(); lsi.release(); rx.release(); ri.release(); px.release(); pi.release(); lkr.release(); lkl.release(); ai.release(); ai2.release(); pk.release(); pst.release(); pc.release(); dt.release(); dc.release();      // (timed: inside pt_allgather)
 		c->timer.mark("pt_allgather");
 	}
 	int bits = 16; while ((1ULL << bits) < c->ix_n_keys / 2 && bits < 26) ++bits;

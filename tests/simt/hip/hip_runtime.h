@@ -17,6 +17,7 @@
 #include <string.h>
 #include <limits.h>
 #include <algorithm>
+#include <atomic>
 #include <functional>
 #include <mutex>
 #include <map>
@@ -71,14 +72,16 @@ inline hipError_t hipDeviceGetAttribute(int *v, hipDeviceAttribute_t, int) { *v 
 inline hipError_t hipDeviceGetPCIBusId(char *b, int len, int) { snprintf(b, len, "0000:00:00.0"); return hipSuccess; }
 inline hipError_t hipDeviceGetStreamPriorityRange(int *lo, int *hi) { *lo = 0; *hi = 0; return hipSuccess; }
 // device memory is not zeroed (0xA5 here), and every allocation sits between guard zones that hipFree checks: a kernel that writes before or past its buffer ends the process
-namespace hao_simt_mem { constexpr size_t G = 256; struct Hdr { size_t n; size_t magic; }; }
+// (a buffer that is never freed is never checked: `live` counts the allocations that hipFree has not seen yet, hao_simt_live_allocations hands it to the tests)
+namespace hao_simt_mem { constexpr size_t G = 256; struct Hdr { size_t n; size_t magic; }; inline std::atomic<long> live{0}; }
+extern "C" __attribute__((weak, used)) long hao_simt_live_allocations() { return hao_simt_mem::live.load(); }
 inline hipError_t hipMalloc(void **p, size_t n)
 {
 	using namespace hao_simt_mem;
 	char *b = (char*)malloc(n + 2 * G); if (!b) { *p = nullptr; return hipErrorOutOfMemory; }
 	memset(b, 0x5c, G); memset(b + G, getenv("HAO_SIMT_ZERO") ? 0 : 0xa5, n); memset(b + G + n, 0x5c, G);
 	Hdr h{n, 0x68616f73696d74ULL}; memcpy(b, &h, sizeof h);
-	*p = b + G; return hipSuccess;
+	*p = b + G; ++live; return hipSuccess;
 }
 template<class T> inline hipError_t hipMalloc(T **p, size_t n) { return hipMalloc((void**)p, n); }
 inline hipError_t hipFree(void *p)
@@ -90,7 +93,7 @@ inline hipError_t hipFree(void *p)
 	for (size_t i = sizeof h; ok && i < G; ++i) ok = b[i] == (char)0x5c;
 	for (size_t i = 0; ok && i < G; ++i) ok = b[G + h.n + i] == (char)0x5c;
 	if (!ok) { fprintf(stderr, "tests/simt: a device buffer of %zu bytes was written outside its bounds\n", h.magic == 0x68616f73696d74ULL ? h.n : (size_t)0); abort(); }
-	free(b); return hipSuccess;
+	free(b); --live; return hipSuccess;
 }
 inline hipError_t hipHostMalloc(void **p, size_t n, unsigned = 0) { *p = malloc(n ? n : 1); return *p ? hipSuccess : hipErrorOutOfMemory; }
 template<class T> inline hipError_t hipHostMalloc(T **p, size_t n, unsigned f = 0) { return hipHostMalloc((void**)p, n, f); }
