@@ -66,7 +66,13 @@ class RescueDelivery(C.Structure):
     _fields_ = [("n_ol", C.c_uint64), ("n_wins", C.c_uint64), ("n_rescued", C.c_uint64), ("ovlp", C.c_void_p), ("win_off", C.c_void_p), ("wins", C.c_void_p)]
 
 
-DELIVER_OL, DELIVER_CL, DELIVER_EXACT, DELIVER_ED, DELIVER_TRACE, DELIVER_RESCUE = 1, 2, 4, 8, 16, 32
+class WlistDelivery(C.Structure):
+    """hao_wlist_delivery_t: the window lists of a batch delivered with HAO_DELIVER_WLIST (pointers into the same pinned arena as its Delivery)"""
+    _fields_ = [("n_ol", C.c_uint64), ("n_wins", C.c_uint64), ("n_cigar", C.c_uint64), ("n_swept", C.c_uint64), ("n_replace", C.c_uint64), ("n_untraced", C.c_uint64),
+                ("win_off", C.c_void_p), ("wins", C.c_void_p), ("cig_off", C.c_void_p), ("cigars", C.c_void_p)]
+
+
+DELIVER_OL, DELIVER_CL, DELIVER_EXACT, DELIVER_ED, DELIVER_TRACE, DELIVER_RESCUE, DELIVER_WLIST = 1, 2, 4, 8, 16, 32, 64
 PLACE_DIAG, PLACE_REF = 0, 1      # hao_ed_delivery_t::placement
 
 ABI_SYMBOLS = [
@@ -79,11 +85,22 @@ ABI_SYMBOLS = [
     "hao_window_trace_grid", "hao_fetch_trace_grid", "hao_deliver_trace", "hao_unpack_trace",
     "hao_window_ed_ref", "hao_fetch_ed_ovlp", "hao_deliver_ed_config_ref", "hao_ref_thresholds",
     "hao_window_rescue_ref", "hao_fetch_rescue", "hao_rescue_task", "hao_deliver_rescue", "hao_unpack_rescue",
+    "hao_window_wlist_ref", "hao_fetch_wlist", "hao_deliver_wlist", "hao_unpack_wlist",
 ]
 
 
 RESCUE_OVLP = np.dtype([("verdict", np.uint16), ("flags", np.uint16), ("exit_win", np.uint32), ("align_length", np.uint32), ("n_rescued", np.uint32)])
 RESCUE_FWD, RESCUE_BWD, RESCUE_ANCHOR, RESCUE_UNTRACED, RESCUE_NO_EXIT = 0, 1, 2, 1, 0xFFFFFFFF
+WLIST_PRIMARY, WLIST_UNTRACED = 3, 1 << 19      # hao_wlist_win_t::info: source of a first-placement window the rescue did not trace; the untraced flag
+
+
+def wlist_records(raw):
+    """hao_wlist_win_t records (uint32 [m, 4]) -> int64 [m, 8]: grid window, y_start, y_end, err, thre, source, re-placed, untraced"""
+    raw = np.asarray(raw, dtype=np.uint32).reshape(-1, 4)
+    out = np.zeros((raw.shape[0], 8), dtype=np.int64)
+    out[:, :7] = rescue_records(raw)
+    out[:, 7] = (raw[:, 3].astype(np.int64) >> 19) & 1
+    return out
 
 
 def rescue_records(raw):
@@ -115,6 +132,35 @@ def unpack_rescue(d, e, r, lengths, rid):
     if got != n:
         raise HaoError(f"hao_unpack_rescue: read {rid}: {got} != {n}")
     return ov, [rescue_records(raw[int(wo[i]):int(wo[i + 1])]) for i in range(n)]
+
+
+def _wlist_split(wo, raw, co, cig):
+    recs = wlist_records(raw)
+    return [(recs[int(wo[i]):int(wo[i + 1])], [cig[int(co[j]):int(co[j + 1])].copy() for j in range(int(wo[i]), int(wo[i + 1]))]) for i in range(len(wo) - 1)]
+
+
+def unpack_wlist(d, e, r, w, lengths, rid):
+    """hao_unpack_wlist (host code) over the four views -> fetch_wlist's shapes: one (wins int64 [m, 8], [uint16 cigar per record]) per overlap of read rid"""
+    L = np.ascontiguousarray(lengths, dtype=np.uint32)
+    u32p, u64p = C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)
+    f = lib().hao_unpack_wlist
+    args = (C.byref(d), C.byref(e), C.byref(r), C.byref(w), L.ctypes.data_as(u32p), rid)
+    n = int(f(*args, None, None, None, None, 0, 0, 0))
+    if n == 2**64 - 1:
+        raise HaoError(f"hao_unpack_wlist: read {rid}: the views do not belong together")
+    m = k = 0
+    if n:
+        oo = _arr(d.ol_off + 8 * (rid - d.rid_lo), 2, np.uint64)
+        ww = _arr(w.win_off + 8 * int(oo[0]), n + 1, np.uint64)
+        m = int(ww[n] - ww[0])
+        if m:
+            cc = _arr(w.cig_off + 8 * int(ww[0]), m + 1, np.uint64)
+            k = int(cc[m] - cc[0])
+    wo = np.zeros(n + 1, dtype=np.uint64); raw = np.zeros((max(m, 1), 4), dtype=np.uint32); co = np.zeros(m + 1, dtype=np.uint64); cig = np.zeros(max(k, 1), dtype=np.uint16)
+    got = int(f(*args, wo.ctypes.data_as(u64p), raw.ctypes.data_as(C.c_void_p), co.ctypes.data_as(u64p), cig.ctypes.data_as(C.c_void_p), n, m, k))
+    if got != n:
+        raise HaoError(f"hao_unpack_wlist: read {rid}: {got} != {n}")
+    return _wlist_split(wo, raw[:m], co, cig[:k])
 
 
 def rescue_task(z, win, window, toff, tab, target_len):
@@ -188,6 +234,11 @@ def lib():
         L.hao_unpack_rescue.restype = C.c_uint64
         L.hao_fetch_rescue.argtypes = [vp, C.c_uint64, C.POINTER(vp), u64p, C.POINTER(vp), C.POINTER(vp)]
         L.hao_rescue_task.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_int64, u8p, C.c_uint32, vp]
+        L.hao_window_wlist_ref.argtypes = [vp, u64p]
+        L.hao_deliver_wlist.argtypes = [vp, C.c_int, C.POINTER(WlistDelivery)]
+        L.hao_unpack_wlist.argtypes = [C.POINTER(Delivery), C.POINTER(EdDelivery), C.POINTER(RescueDelivery), C.POINTER(WlistDelivery), u32p, C.c_uint64, u64p, vp, u64p, vp, C.c_uint64, C.c_uint64, C.c_uint64]
+        L.hao_unpack_wlist.restype = C.c_uint64
+        L.hao_fetch_wlist.argtypes = [vp, C.c_uint64, u64p, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
         L.hao_ref_thresholds.argtypes = [C.c_uint32, C.c_double, u8p]; L.hao_ref_thresholds.restype = None
         L.hao_fetch_trace_grid.argtypes = [vp, vp, vp, u64p, vp, C.c_uint64, C.c_uint64]
         L.hao_deliver_trace.argtypes = [vp, C.c_int, C.POINTER(TraceDelivery)]
@@ -392,6 +443,9 @@ class Engine:
         if not hasattr(self, "_rs_slot"):
             self._rs_slot = {}
         self._rs_slot[slot.value] = bool(parts & DELIVER_RESCUE)
+        if not hasattr(self, "_wl_slot"):
+            self._wl_slot = {}
+        self._wl_slot[slot.value] = bool(parts & DELIVER_WLIST)
         return slot.value
 
     def deliver_wait(self, slot):
@@ -401,6 +455,7 @@ class Engine:
         d.ed = self.deliver_ed(slot) if getattr(self, "_ed_slot", {}).get(slot) else None
         d.tr = self.deliver_trace(slot) if getattr(self, "_tr_slot", {}).get(slot) else None
         d.rs = self.deliver_rescue(slot) if getattr(self, "_rs_slot", {}).get(slot) else None
+        d.wl = self.deliver_wlist(slot) if getattr(self, "_wl_slot", {}).get(slot) else None
         return d
 
     def deliver_ed_config(self, window=375, thre=15):
@@ -589,6 +644,38 @@ class Engine:
             a, b = int(wo[i]), int(wo[i + 1])
             wins.append(rescue_records(_arr(pr.value + 16 * a, 4 * (b - a), np.uint32).reshape(-1, 4)))
         return ov, wins
+
+    def deliver_wlist(self, slot):
+        """the WlistDelivery view of a waited-for slot whose batch asked for DELIVER_WLIST"""
+        w = WlistDelivery()
+        self._ck(self.L.hao_deliver_wlist(self.h, slot, C.byref(w)), "hao_deliver_wlist")
+        return w
+
+    def delivered_wlist(self, d, rid, lengths=None):
+        """the window lists of read rid out of a Delivery with DELIVER_ED | DELIVER_RESCUE | DELIVER_WLIST - fetch_wlist's shapes and values (hao_unpack_wlist)"""
+        if getattr(d, "ed", None) is None or getattr(d, "rs", None) is None or getattr(d, "wl", None) is None:
+            raise HaoError("delivered_wlist: the batch was not delivered with DELIVER_ED | DELIVER_RESCUE | DELIVER_WLIST")
+        if lengths is None:
+            raise HaoError("delivered_wlist: the lengths of all reads are needed (pass lengths=)")
+        return unpack_wlist(d, d.ed, d.rs, d.wl, lengths, rid)
+
+    def window_wlist_ref(self):
+        """hao_window_wlist_ref: the window lists of the batch window_ed_ref and window_rescue_ref have just processed - every aligned window of every overlap
+        with verdict 1, traced; returns (window records, windows swept, re-placement sweeps, cigar entries, untraced windows).  fetch_wlist serves them"""
+        out = (C.c_uint64 * 5)()
+        self._ck(self.L.hao_window_wlist_ref(self.h, out), "hao_window_wlist_ref")
+        return tuple(int(x) for x in out)
+
+    def fetch_wlist(self, rid):
+        """the window lists of read rid after window_wlist_ref, aligned with h_ec_lchain(rid)[0]: one (wins, cigars) per overlap - wins = int64 [m, 8] (grid window,
+        y_start, y_end, err, thre, source, re-placed, untraced) in window order, cigars = one uint16 array per record (push_trace's encoding; empty when untraced)"""
+        n, pw, pr, po, pc = C.c_uint64(), C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p()
+        self._ck(self.L.hao_fetch_wlist(self.h, rid, C.byref(n), C.byref(pw), C.byref(pr), C.byref(po), C.byref(pc)), "hao_fetch_wlist")
+        m = int(n.value)
+        wo = _arr(pw.value, m + 1, np.uint64)
+        nrec = int(wo[m])
+        co = _arr(po.value, nrec + 1, np.uint64)
+        return _wlist_split(wo, _arr(pr.value, 4 * nrec, np.uint32).reshape(-1, 4), co, _arr(pc.value, int(co[nrec]), np.uint16))
 
     def window_trace_grid(self, window=375, thre=15):
         """hao_window_trace_grid: the last batch's grid pairs aligned with traceback where they align inside the semi-global domain;

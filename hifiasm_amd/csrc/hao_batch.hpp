@@ -30,6 +30,7 @@ struct hao_ctx::Batch {
 		DevBuf<uint8_t> exact;                                                                        // exact-overlap flags of ol_out
 		DevBuf<uint64_t> ed_off; DevBuf<uint8_t> ed_err; DevBuf<uint16_t> ed_pe;                      // HAO_DELIVER_ED: pairs per read, error byte and pattern end per pair (hao_ed_deliver.cuh)
 		DevBuf<hao_ed_ovlp_sum> ed_sum;                                                               // HAO_DELIVER_ED in reference placement: the per-overlap summaries (ed_ref_summary_kernel)
+		DevBuf<uint64_t> wl_woff, wl_cigoff; DevBuf<hao_rs_win> wl_wins; DevBuf<uint16_t> wl_cig;      // HAO_DELIVER_WLIST: record offsets per overlap, the records, entry offsets per record, the entries (hao_wlist.cuh)
 		DevBuf<hao_rs_ovlp> rs_ovlp; DevBuf<uint64_t> rs_off; DevBuf<hao_rs_win> rs_wins;                // HAO_DELIVER_RESCUE: per-overlap results, record offsets per overlap, the records (hao_rescue.cuh)
 		DevBuf<uint64_t> tr_off; DevBuf<uint16_t> tr_ps, tr_ncig, tr_cig;                            // HAO_DELIVER_TRACE: cigar entries per read, ps and entry count per pair, the entries (hao_trace_grid.cuh)
 	} out[2];
@@ -43,6 +44,7 @@ struct hao_ctx::Batch {
 	uint64_t ed_unres = 0;      // HAO_DELIVER_ED in reference placement: windows of the batch whose start resolved to no cigar entry
 	DevBuf<uint64_t> ed_nwin, ed_wbase, ed_wcnt, ed_woff; DevBuf<hao_ed_pair> ed_pairs; uint64_t ed_n = 0;      // HAO_DELIVER_ED scratch (compute stream only: not per output set); ed_n = pairs of the batch
 	hao_ed_delivery_t ed_dl[2] = {};      // the ED view of each slot (window 0: the slot's batch did not ask for HAO_DELIVER_ED)
+	uint64_t wl_cnt[5] = { 0, 0, 0, 0, 0 }; hao_wlist_delivery_t wl_dl[2] = {}; bool wl_on[2] = { false, false };      // HAO_DELIVER_WLIST: hao_al_wlist's five counts of the batch; the view of each slot
 	uint64_t rs_nw = 0, rs_nres = 0, rs_wc = 0; hao_rescue_delivery_t rs_dl[2] = {}; bool rs_on[2] = { false, false };      // HAO_DELIVER_RESCUE: window records and rescued windows of the batch, its covered windows; the view of each slot
 	uint64_t tr_n = 0, tr_ncig = 0; hao_trace_delivery_t tr_dl[2] = {}; bool tr_on[2] = { false, false };      // HAO_DELIVER_TRACE: traced pairs and cigar entries of the batch; the view of each slot (tr_on: the slot's batch asked for it)
 	hao_delivery_t dl[2]; uint64_t dl_seq = 0, n_exc = 0; uint32_t dl_parts = 0; bool exact_valid = false; std::vector<uint8_t> h_exact;
@@ -281,7 +283,7 @@ static int hao_ed_grid_run(hao_ctx *c, uint32_t wl, uint32_t thre, uint64_t *n_t
 // the per-overlap summaries (c->rf_sum) and the count of unresolved windows
 static int hao_ed_ref_run(hao_ctx *c, uint32_t wl, double e_rate, uint64_t *n_tasks, uint64_t *unresolved)
 {
-	hao_ctx::Batch &B = *c->batch; *n_tasks = 0; if (unresolved) *unresolved = 0; c->al_grid_n = 0; c->rf_valid = false; c->rf_hvalid = false; c->rf_unres = 0; c->rs_valid = false; c->rf_T = 0;
+	hao_ctx::Batch &B = *c->batch; *n_tasks = 0; if (unresolved) *unresolved = 0; c->al_grid_n = 0; c->rf_valid = false; c->rf_hvalid = false; c->rf_unres = 0; c->rs_valid = false; c->wl_valid = false; c->rf_T = 0;
 	if (hao_is_sharded(c)) { hao_set_err(c, "hao_window_ed_ref needs the bases of both reads: single-device mode only"); return HAO_EUNSUPP; }
 	if (!hao_ed_ref_args_ok(wl, e_rate)) { hao_set_err(c, "hao_window_ed_ref: window length 0, window + 62 beyond 16 bits, or e_rate outside (0, 1)"); return HAO_EINVAL; }
 	if (B.n == 0 || B.n_ol == 0) { c->rf_valid = true; return HAO_OK; }
@@ -308,13 +310,32 @@ int hao_al_rescue(hao_ctx *c, const hao_ovlp_t *ol, uint64_t n_ol, uint32_t wl, 
 		const uint8_t *err8 = nullptr, const uint16_t *pe16 = nullptr, hao_rs_ovlp *out = nullptr, DevBuf<uint64_t> *d_off = nullptr, DevBuf<hao_rs_win> *d_wins = nullptr, uint64_t *n_wins = nullptr);      // (hao_f3.hip)
 static int hao_rescue_ref_run(hao_ctx *c, uint64_t *n_rescued)
 {
-	hao_ctx::Batch &B = *c->batch; *n_rescued = 0; c->rs_valid = false; c->rs_hvalid = false;
+	hao_ctx::Batch &B = *c->batch; *n_rescued = 0; c->rs_valid = false; c->rs_hvalid = false; c->wl_valid = false;
 	if (!c->rf_valid || c->al_grid_n != c->rf_T) { hao_set_err(c, "hao_window_rescue_ref: hao_window_ed_ref has not run on this batch (or another window-alignment call has run since)"); return HAO_EINVAL; }
 	if (B.n == 0 || B.n_ol == 0) { c->rs_total = c->rs_rounds = c->rs_active = c->rs_slots = 0; c->rs_valid = true; return HAO_OK; }
 	hao_ref_args A; A.win_off = c->rf.woff.p; A.shift = c->rf.shift.p; A.tab = c->rf_tab.p;
 	uint64_t Wc = 0; HIP_TRY(hipMemcpyAsync(&Wc, c->rf.woff.p + B.n_ol, 8, hipMemcpyDeviceToHost, c->stream)); HIP_TRY(hipStreamSynchronize(c->stream));
 	if (int rc = hao_al_rescue(c, B.O().ol_out.p, B.n_ol, c->rf_tab_wl, A, c->rf.werr.p, c->rf.pairs.p, c->al_res.p, c->rf_T, Wc)) return rc;
-	*n_rescued = c->rs_total; c->rs_valid = true;
+	*n_rescued = c->rs_total; c->rs_wc = Wc; c->rs_valid = true;
+	return HAO_OK;
+}
+
+// hao_window_wlist_ref: the window lists (hao_wlist.cuh) over what hao_rescue_ref_run left - the CSR, shifts and error bytes in c->rf, pe per slot, the rescue
+// records and the verdicts in c->rs, none of which it changes
+int hao_al_wlist(hao_ctx *c, const hao_ovlp_t *ol, uint64_t n_ol, uint32_t wl, hao_ref_args RA, const uint8_t *werr, const hao_rs_ovlp *ov, uint64_t n_slots, uint64_t out[5],
+		DevBuf<uint64_t> &o_woff, DevBuf<hao_rs_win> &o_wins, DevBuf<uint64_t> &o_cigoff, DevBuf<uint16_t> &o_cig);      // (hao_f3.hip)
+static int hao_wlist_ref_run(hao_ctx *c, uint64_t out[5])
+{
+	hao_ctx::Batch &B = *c->batch; c->wl_valid = false; c->wl_hvalid = false;
+	for (int k = 0; k < 5; ++k) out[k] = 0;
+	if (hao_is_sharded(c)) { hao_set_err(c, "hao_window_wlist_ref needs the bases of both reads: single-device mode only"); return HAO_EUNSUPP; }
+	if (!c->rf_valid || !c->rs_valid || c->al_grid_n != c->rf_T) { hao_set_err(c, "hao_window_wlist_ref: hao_window_ed_ref and hao_window_rescue_ref have not both run on this batch (or another window-alignment call has run since)"); return HAO_EINVAL; }
+	if (B.n && B.n_ol && c->rs_wc) {
+		hao_ref_args A; A.win_off = c->rf.woff.p; A.shift = c->rf.shift.p; A.tab = c->rf_tab.p;
+		if (int rc = hao_al_wlist(c, B.O().ol_out.p, B.n_ol, c->rf_tab_wl, A, c->rf.werr.p, c->rs.ovlp.p, c->rs_wc, out, c->wl.woff, c->wl.wins, c->wl.cig_off, c->wl.cig)) return rc;
+	}
+	for (int k = 0; k < 5; ++k) c->wl_out[k] = out[k];
+	c->wl_valid = true;
 	return HAO_OK;
 }
 
@@ -384,6 +405,20 @@ static int hao_rescue_deliver_run(hao_ctx *c)
 	return HAO_OK;
 }
 
+// HAO_DELIVER_WLIST: the window lists over what the batch's ED and rescue stages have just left (c->rf, c->rs, the output set's verdicts), into the output set's
+// own buffers.  Two count reads: the stage's sizes, and its totals, which size the arena part
+static int hao_wlist_deliver_run(hao_ctx *c)
+{
+	hao_ctx::Batch &B = *c->batch; hao_ctx::Batch::OutSet &O = B.O();
+	for (int k = 0; k < 5; ++k) B.wl_cnt[k] = 0;
+	HIP_TRY(O.wl_woff.reserve(B.n_ol + 2)); HIP_TRY(O.wl_wins.reserve(1)); HIP_TRY(O.wl_cigoff.reserve(2)); HIP_TRY(O.wl_cig.reserve(1));
+	if (B.n_ol == 0 || B.rs_wc == 0) { HIP_TRY(hipMemsetAsync(O.wl_woff.p, 0, (B.n_ol + 1) * 8, c->stream)); HIP_TRY(hipMemsetAsync(O.wl_cigoff.p, 0, 8, c->stream)); c->timer.mark("wlist"); return HAO_OK; }
+	hao_ref_args A; A.win_off = c->rf.woff.p; A.shift = c->rf.shift.p; A.tab = c->ded_tab.p;
+	if (int rc = hao_al_wlist(c, O.ol_out.p, B.n_ol, c->ded_window, A, c->rf.werr.p, O.rs_ovlp.p, B.rs_wc, B.wl_cnt, O.wl_woff, O.wl_wins, O.wl_cigoff, O.wl_cig)) return rc;
+	c->timer.mark("wlist");
+	return HAO_OK;
+}
+
 // hao_window_trace_grid: the grid pairs of the current batch (hao_window_ed_grid's), their distance-only alignment (the delivery path's kernel, into the
 // context's own buffers) and the traced stage; everything stays resident for hao_fetch_trace_grid.  out: pairs, traced pairs, cigar entries, aligned but untraced pairs.
 static int hao_trace_grid_run(hao_ctx *c, uint32_t wl, uint32_t thre, uint64_t out[4])
@@ -415,7 +450,7 @@ static int hao_deliver_enqueue(hao_ctx *c)
 {
 	hao_ctx::Batch &B = *c->batch; const int s = B.cur; hao_ctx::Batch::OutSet &O = B.O(); const uint64_t n = B.n; const uint32_t parts = B.dl_parts;
 	auto al = [](size_t v) { return (v + 63) & ~(size_t)63; };
-	const bool ol = parts & HAO_DELIVER_OL, cl = parts & HAO_DELIVER_CL, ex = parts & HAO_DELIVER_EXACT, ed = parts & HAO_DELIVER_ED, tr = parts & HAO_DELIVER_TRACE, rsq = parts & HAO_DELIVER_RESCUE;
+	const bool ol = parts & HAO_DELIVER_OL, cl = parts & HAO_DELIVER_CL, ex = parts & HAO_DELIVER_EXACT, ed = parts & HAO_DELIVER_ED, tr = parts & HAO_DELIVER_TRACE, rsq = parts & HAO_DELIVER_RESCUE, wlq = parts & HAO_DELIVER_WLIST;
 	size_t o_oloff = 0, o_ol = o_oloff + (ol ? al((n + 1) * 8) : 0), o_fcoff = o_ol + (ol ? al(B.n_ol * sizeof(hao_ovlp_wire_t)) : 0), o_fc = o_fcoff + (ol ? al((B.n_ol + 1) * 8) : 0);
 	size_t o_choff = o_fc + (ol ? al(B.n_fcw * 4) : 0), o_cloff = o_choff + (cl ? al((n + 1) * 8) : 0), o_qmoff = o_cloff + (cl ? al((n + 1) * 8) : 0), o_hdr = o_qmoff + (cl ? al((n + 1) * 8) : 0);
 	const bool q16 = O.qmz16;      // the minimizer tables in 2 + 2 bytes per minimizer (hao_qtab16_kernel) instead of 8
@@ -427,7 +462,8 @@ static int hao_deliver_enqueue(hao_ctx *c)
 	const bool edref = ed && B.ed_dl[s].placement == HAO_PLACE_REF;      // (reference placement: the per-overlap summaries travel after the pairs' records)
 	size_t o_ederr = o_edoff + (ed ? al((n + 1) * 8) : 0), o_edpe = o_ederr + (ed ? al(B.ed_n) : 0), o_edsum = o_edpe + (ed ? al(B.ed_n * 2) : 0), o_troff = o_edsum + (edref ? al(B.n_ol * sizeof(hao_ed_ovlp_sum)) : 0);      // (without HAO_DELIVER_ED: o_troff = o_edoff, the layout of before; in diagonal placement o_troff = o_edsum)
 	size_t o_trps = o_troff + (tr ? al((n + 1) * 8) : 0), o_trnc = o_trps + (tr ? al(B.ed_n * 2) : 0), o_trcig = o_trnc + (tr ? al(B.ed_n * 2) : 0), o_rsov = o_trcig + (tr ? al(B.tr_ncig * 2) : 0);      // (without HAO_DELIVER_TRACE: o_rsov = o_troff)
-	size_t o_rsoff = o_rsov + (rsq ? al(B.n_ol * sizeof(hao_rs_ovlp)) : 0), o_rswin = o_rsoff + (rsq ? al((B.n_ol + 1) * 8) : 0), total = o_rswin + (rsq ? al(B.rs_nw * sizeof(hao_rs_win)) : 0);      // (without HAO_DELIVER_RESCUE: total = o_rsov, the layout of before)
+	size_t o_rsoff = o_rsov + (rsq ? al(B.n_ol * sizeof(hao_rs_ovlp)) : 0), o_rswin = o_rsoff + (rsq ? al((B.n_ol + 1) * 8) : 0), o_wloff = o_rswin + (rsq ? al(B.rs_nw * sizeof(hao_rs_win)) : 0);      // (without HAO_DELIVER_RESCUE: o_wloff = o_rsov, the layout of before)
+	size_t o_wlwin = o_wloff + (wlq ? al((B.n_ol + 1) * 8) : 0), o_wlcoff = o_wlwin + (wlq ? al(B.wl_cnt[0] * sizeof(hao_rs_win)) : 0), o_wlcig = o_wlcoff + (wlq ? al((B.wl_cnt[0] + 1) * 8) : 0), total = o_wlcig + (wlq ? al(B.wl_cnt[3] * 2) : 0);      // (without HAO_DELIVER_WLIST: total = o_wloff)
 	if (total > B.arena_cap[s] || B.arena_bad[s]) {
 		const bool redo_ = B.arena_bad[s]; B.arena_bad[s] = false;      // (hao_deliver_wait saw this slot's last batch copied at less than 40 GB/s: the probe below tries every NUMA node)
 		B.arena_free(s);
@@ -532,6 +568,14 @@ static int hao_deliver_enqueue(hao_ctx *c)
 		r.n_ol = B.n_ol; r.n_wins = B.rs_nw; r.n_rescued = B.rs_nres; r.ovlp = (const hao_rescue_ovlp_t*)(a + o_rsov); r.win_off = (const uint64_t*)(a + o_rsoff); r.wins = (const hao_rescue_win_t*)(a + o_rswin);
 		d.bytes += B.n_ol * sizeof(hao_rs_ovlp) + (B.n_ol + 1) * 8 + B.rs_nw * sizeof(hao_rs_win);
 	}
+	if (wlq && n) {
+		const uint64_t N = B.wl_cnt[0], E = B.wl_cnt[3];
+		HIP_TRY(cp(o_wloff, O.wl_woff.p, (B.n_ol + 1) * 8)); HIP_TRY(cp(o_wlwin, O.wl_wins.p, N * sizeof(hao_rs_win))); HIP_TRY(cp(o_wlcoff, O.wl_cigoff.p, (N + 1) * 8)); HIP_TRY(cp(o_wlcig, O.wl_cig.p, E * 2));
+		hao_wlist_delivery_t &w = B.wl_dl[s];
+		w.n_ol = B.n_ol; w.n_wins = N; w.n_cigar = E; w.n_swept = B.wl_cnt[1]; w.n_replace = B.wl_cnt[2]; w.n_untraced = B.wl_cnt[4];
+		w.win_off = (const uint64_t*)(a + o_wloff); w.wins = (const hao_wlist_win_t*)(a + o_wlwin); w.cig_off = (const uint64_t*)(a + o_wlcoff); w.cigars = (const uint16_t*)(a + o_wlcig);
+		d.bytes += (B.n_ol + 1) * 8 + N * sizeof(hao_rs_win) + (N + 1) * 8 + E * 2;
+	}
 	HIP_TRY(hipEventRecord(B.ev_done[s], B.copy_stream));
 	B.dl_pending[s] = true;
 	return HAO_OK;
@@ -556,7 +600,7 @@ static int hao_overlap_run(hao_ctx *c, uint64_t lo, uint64_t hi, const hao_pass_
 	if (!c->has_pt) { hao_set_err(c, "hao_pt_gen must run before hao_overlap_batch"); return HAO_EINVAL; }
 	if (!c->batch) c->batch = new hao_ctx::Batch();
 	hao_ctx::Batch &B = *c->batch; const double t_run0 = hao_now();
-	c->al_grid_n = 0; c->tg_valid = false; c->rf_valid = false; c->rs_valid = false;      // (the window-alignment grid of the previous batch's overlaps is stale)
+	c->al_grid_n = 0; c->tg_valid = false; c->rf_valid = false; c->rs_valid = false; c->wl_valid = false;      // (the window-alignment grid of the previous batch's overlaps is stale)
 	B.valid = false; B.host_valid = false; B.cl_valid = false; B.exact_valid = false; B.h_exact.clear(); B.lo = lo; B.n = hi - lo; B.dl_parts = parts; B.n_exc = 0;
 	const uint64_t n = B.n;
 	if (parts) {
@@ -569,7 +613,8 @@ static int hao_overlap_run(hao_ctx *c, uint64_t lo, uint64_t hi, const hao_pass_
 	if (parts) { memset(&B.dl[B.cur], 0, sizeof(hao_delivery_t)); B.dl[B.cur].rid_lo = lo; B.dl[B.cur].n_reads = n;
 		memset(&B.ed_dl[B.cur], 0, sizeof(hao_ed_delivery_t)); if (parts & HAO_DELIVER_ED) { B.ed_dl[B.cur].window = c->ded_window; B.ed_dl[B.cur].thre = c->ded_thre; B.ed_dl[B.cur].placement = c->ded_place; B.ed_dl[B.cur].e_rate = c->ded_place == HAO_PLACE_REF ? c->ded_erate : 0; }
 		memset(&B.tr_dl[B.cur], 0, sizeof(hao_trace_delivery_t)); B.tr_on[B.cur] = (parts & HAO_DELIVER_TRACE) != 0;
-		memset(&B.rs_dl[B.cur], 0, sizeof(hao_rescue_delivery_t)); B.rs_on[B.cur] = (parts & HAO_DELIVER_RESCUE) != 0; }
+		memset(&B.rs_dl[B.cur], 0, sizeof(hao_rescue_delivery_t)); B.rs_on[B.cur] = (parts & HAO_DELIVER_RESCUE) != 0;
+		memset(&B.wl_dl[B.cur], 0, sizeof(hao_wlist_delivery_t)); B.wl_on[B.cur] = (parts & HAO_DELIVER_WLIST) != 0; }
 	if (n == 0) { B.n_anchor = B.n_groups = B.n_chains = B.n_cl = B.n_ol = B.n_fc = B.n_fcw = B.n_mz = 0; B.valid = true; return HAO_OK; }      // (an empty delivery: nothing to copy, the view stays zeroed)
 	// minimizer range of the batch (host knows the per-read offsets? keep a host copy once)
 	if (c->h_ix_mz_off.size() != c->n_reads + 1) {
@@ -932,6 +977,7 @@ static int hao_overlap_run(hao_ctx *c, uint64_t lo, uint64_t hi, const hao_pass_
 	if (parts & HAO_DELIVER_ED) { if (int rc = hao_ed_deliver_run(c)) return rc; }
 	if (parts & HAO_DELIVER_TRACE) { if (int rc = hao_trace_deliver_run(c)) return rc; }
 	if (parts & HAO_DELIVER_RESCUE) { if (int rc = hao_rescue_deliver_run(c)) return rc; }
+	if (parts & HAO_DELIVER_WLIST) { if (int rc = hao_wlist_deliver_run(c)) return rc; }
 	if (parts) { const double t0_ = hao_now(); const int rc_ = hao_deliver_enqueue(c); B.t_enq += hao_now() - t0_; ++B.t_n; if (c->sw.dltime && (B.t_n & 15) == 0) fprintf(stderr, "[deliver] %llu batches: slot wait %.1f ms, enqueue %.1f ms (arena alloc %.1f ms)\n", (unsigned long long)B.t_n, B.t_evsync * 1e3, B.t_enq * 1e3, B.t_alloc * 1e3); return rc_; }
 	return HAO_OK;
 }

@@ -126,6 +126,11 @@ int hao_overlap_batch_async(hao_ctx *c, uint64_t rid_lo, uint64_t rid_hi, const 
 		if (!(parts & HAO_DELIVER_ED)) { hao_set_err(c, "HAO_DELIVER_RESCUE needs HAO_DELIVER_ED: it rescues the windows the ED stage left open"); return HAO_EINVAL; }
 		if (c->ded_place != HAO_PLACE_REF) { hao_set_err(c, "HAO_DELIVER_RESCUE needs reference placement (hao_deliver_ed_config_ref)"); return HAO_EINVAL; }
 	}
+	if (parts & HAO_DELIVER_WLIST) {
+		if (hao_is_sharded(c)) { hao_set_err(c, "HAO_DELIVER_WLIST needs the bases of both reads: single-device mode only"); return HAO_EUNSUPP; }
+		if (!(parts & HAO_DELIVER_ED) || !(parts & HAO_DELIVER_RESCUE)) { hao_set_err(c, "HAO_DELIVER_WLIST needs HAO_DELIVER_ED | HAO_DELIVER_RESCUE: it traces the windows those stages aligned"); return HAO_EINVAL; }
+		if (c->ded_place != HAO_PLACE_REF) { hao_set_err(c, "HAO_DELIVER_WLIST needs reference placement (hao_deliver_ed_config_ref)"); return HAO_EINVAL; }
+	}
 	if ((parts & HAO_DELIVER_TRACE) && !(parts & HAO_DELIVER_ED)) { hao_set_err(c, "HAO_DELIVER_TRACE needs HAO_DELIVER_ED: it traces the pairs the ED stage aligned"); return HAO_EINVAL; }
 	hao_pass_t ps;
 	if (!pass) { if (int rc = hao_pass_default(c, &ps)) return rc; pass = &ps; }
@@ -499,6 +504,93 @@ int hao_fetch_rescue(hao_ctx *c, uint64_t rid, const hao_rescue_ovlp_t **ovlp, u
 	*ovlp = (const hao_rescue_ovlp_t*)(G.h_ovlp.data() + s_); *n = e_ - s_;
 	*win_off = G.h_win_off.data() + s_; *wins = (const hao_rescue_win_t*)G.h_wins.data();
 	return HAO_OK;
+}
+
+int hao_window_wlist_ref(hao_ctx *c, uint64_t out[5])
+{
+	if (!c || !out || !c->batch || !c->batch->valid) return HAO_EINVAL;
+	if (int rc = hao_view_refresh(c)) return rc;
+	HIP_TRY(hipSetDevice(c->device));
+	c->timer.begin(c->stream);
+	if (int rc = hao_wlist_ref_run(c, out)) return rc;
+	HIP_TRY(hipStreamSynchronize(c->stream));
+	c->timer.mark("wlist_ref"); c->timer.collect(c->stage_ms);
+	return HAO_OK;
+}
+
+int hao_fetch_wlist(hao_ctx *c, uint64_t rid, uint64_t *n_ol, const uint64_t **win_off, const hao_wlist_win_t **wins, const uint64_t **cig_off, const uint16_t **cigars)
+{
+	if (!c || !n_ol || !win_off || !wins || !cig_off || !cigars) return HAO_EINVAL;
+	if (!c->batch || !c->batch->valid || !c->rf_valid || !c->rs_valid || !c->wl_valid || c->al_grid_n != c->rf_T) { hao_set_err(c, "hao_fetch_wlist: no results of hao_window_wlist_ref are resident (a new batch or another window-alignment stage has run since)"); return HAO_EINVAL; }
+	hao_ctx::Batch &B = *c->batch;
+	if (rid < B.lo || rid >= B.lo + B.n) return HAO_EINVAL;
+	HIP_TRY(hipSetDevice(c->device));
+	if (int rc = hao_batch_download(c)) return rc;
+	hao_ctx::Wlist &G = c->wl;
+	if (!c->wl_hvalid) {      // the whole batch once
+		const uint64_t m = B.n_ol, N = c->wl_out[0], E = c->wl_out[3];
+		G.h_woff.assign(m + 1, 0); G.h_wins.assign(N + 1, hao_rs_win{0, 0, 0, 0}); G.h_cig_off.assign(N + 1, 0); G.h_cig.assign(E + 1, 0);
+		if (N) {
+			HIP_TRY(hipMemcpy(G.h_woff.data(), G.woff.p, (m + 1) * 8, hipMemcpyDeviceToHost));
+			HIP_TRY(hipMemcpy(G.h_wins.data(), G.wins.p, N * sizeof(hao_rs_win), hipMemcpyDeviceToHost));
+			HIP_TRY(hipMemcpy(G.h_cig_off.data(), G.cig_off.p, (N + 1) * 8, hipMemcpyDeviceToHost));
+			if (E) HIP_TRY(hipMemcpy(G.h_cig.data(), G.cig.p, E * 2, hipMemcpyDeviceToHost));
+		}
+		c->wl_hvalid = true;
+	}
+	const uint64_t r = rid - B.lo, s_ = B.h_fin_off[r], e_ = B.h_fin_off[r + 1], n = e_ - s_, g0 = G.h_woff[s_], g1 = G.h_woff[e_];
+	G.r_woff.resize(n + 1); G.r_cig_off.resize(g1 - g0 + 1);
+	for (uint64_t i = 0; i <= n; ++i) G.r_woff[i] = G.h_woff[s_ + i] - g0;
+	for (uint64_t g = g0; g <= g1; ++g) G.r_cig_off[g - g0] = G.h_cig_off[g] - G.h_cig_off[g0];
+	*n_ol = n; *win_off = G.r_woff.data(); *wins = (const hao_wlist_win_t*)(G.h_wins.data() + g0); *cig_off = G.r_cig_off.data(); *cigars = G.h_cig.data() + G.h_cig_off[g0];
+	return HAO_OK;
+}
+
+int hao_deliver_wlist(hao_ctx *c, int slot, hao_wlist_delivery_t *out)
+{
+	if (!c || !out || slot < 0 || slot > 1 || !c->batch || !c->batch->dl_ready) return HAO_EINVAL;
+	hao_ctx::Batch &B = *c->batch;
+	if (!B.wl_on[slot]) { hao_set_err(c, "hao_deliver_wlist: the slot's batch did not ask for HAO_DELIVER_WLIST"); return HAO_EINVAL; }
+	if (B.dl_pending[slot]) { hao_set_err(c, "hao_deliver_wlist: hao_deliver_wait has not been called on the slot"); return HAO_EINVAL; }
+	*out = B.wl_dl[slot];
+	return HAO_OK;
+}
+
+uint64_t hao_unpack_wlist(const hao_delivery_t *d, const hao_ed_delivery_t *e, const hao_rescue_delivery_t *r, const hao_wlist_delivery_t *w, const uint32_t *len, uint64_t rid,
+		uint64_t *win_off, hao_wlist_win_t *wins, uint64_t *cig_off, uint16_t *cigars, uint64_t cap_ovlp, uint64_t cap_wins, uint64_t cap_cigars)
+{
+	if (!d || !e || !r || !w || !len) return UINT64_MAX;
+	if (rid < d->rid_lo || rid >= d->rid_lo + d->n_reads) return 0;
+	if (!e->window || e->placement != HAO_PLACE_REF || !d->ol_off || !d->ol || r->n_ol != d->n_ol || w->n_ol != d->n_ol || (w->n_ol && (!w->win_off || !r->ovlp)) || (w->n_wins && (!w->wins || !w->cig_off)) ||
+		(w->n_cigar && !w->cigars)) return UINT64_MAX;
+	const uint64_t q = rid - d->rid_lo, o0 = d->ol_off[q], o1 = d->ol_off[q + 1];
+	if (o0 > o1 || o1 > w->n_ol) return UINT64_MAX;
+	const uint64_t n = o1 - o0;
+	if (n == 0) return 0;
+	if (w->win_off[w->n_ol] != w->n_wins || (w->n_wins ? w->cig_off[w->n_wins] : 0) != w->n_cigar) return UINT64_MAX;      // (the counts add up)
+	const uint64_t g0 = w->win_off[o0], g1 = w->win_off[o1];
+	if (g0 > g1 || g1 > w->n_wins) return UINT64_MAX;
+	// every record in a window its overlap covers, in ascending window order, inside the read's grid, in an overlap that passed; entry offsets ascend
+	std::vector<hao_ovlp_t> zs(n);
+	if (hao_unpack_overlaps(d, rid, zs.data(), n) != n) return UINT64_MAX;
+	const uint32_t wl = e->window; const uint64_t nwin = ((uint64_t)len[rid] + wl - 1) / wl;
+	for (uint64_t i = 0; i < n; ++i) {
+		const uint64_t a = w->win_off[o0 + i], b = w->win_off[o0 + i + 1];
+		if (a > b || b > g1) return UINT64_MAX;
+		if (b > a && !r->ovlp[o0 + i].verdict) return UINT64_MAX;
+		for (uint64_t k = a; k < b; ++k) {
+			const uint32_t x = w->wins[k].win;
+			if (x < zs[i].x_pos_s / wl || x > zs[i].x_pos_e / wl || x >= nwin || (k > a && w->wins[k - 1].win >= x)) return UINT64_MAX;
+			if (w->cig_off[k] > w->cig_off[k + 1] || w->cig_off[k + 1] > w->n_cigar) return UINT64_MAX;
+		}
+	}
+	const uint64_t c0 = g1 > g0 ? w->cig_off[g0] : 0, c1 = g1 > g0 ? w->cig_off[g1] : 0;
+	if (n > cap_ovlp || g1 - g0 > cap_wins || c1 - c0 > cap_cigars || !win_off || !wins || !cig_off || !cigars) return n;
+	for (uint64_t i = 0; i <= n; ++i) win_off[i] = w->win_off[o0 + i] - g0;
+	for (uint64_t k = g0; k < g1; ++k) { wins[k - g0] = w->wins[k]; cig_off[k - g0] = w->cig_off[k] - c0; }
+	cig_off[g1 - g0] = c1 - c0;
+	for (uint64_t j = c0; j < c1; ++j) cigars[j - c0] = w->cigars[j];
+	return n;
 }
 
 int hao_rescue_task(const hao_ovlp_t *z, uint32_t win, uint32_t window, int64_t toff, const uint8_t *tab, uint32_t target_len, hao_ed_task_t *out)

@@ -185,6 +185,14 @@ struct hao_ctx {
 		std::vector<hao_rs_ovlp> h_ovlp; std::vector<uint64_t> h_win_off; std::vector<hao_rs_win> h_wins;
 	} rs;
 	bool rs_valid = false, rs_hvalid = false; uint64_t rf_T = 0, rs_slots = 0, rs_rounds = 0, rs_active = 0, rs_total = 0;
+	// the window lists (hao_wlist.cuh; hao_window_wlist_ref): records per overlap and their scan, the plan, the records, entry counts and their scan (the CSR
+	// offsets), sort keys and record indices (sel: the records that need a sweep, in text order), the column scratch, two rows per swept record, the compact
+	// cigars, five counters; wl_valid: the results belong to the current batch's rescue results; h_*: hao_fetch_wlist's host copies and the read it last served
+	struct Wlist {
+		DevBuf<uint64_t> cnt, woff, ncig, cig_off, key, key2, path; DevBuf<hao_wl_plan> plan; DevBuf<hao_rs_win> wins; DevBuf<uint32_t> idx, sel, rowof; DevBuf<uint16_t> rows, cig; DevBuf<unsigned long long> ctr;
+		std::vector<uint64_t> h_woff, h_cig_off, r_woff, r_cig_off; std::vector<hao_rs_win> h_wins; std::vector<uint16_t> h_cig;
+	} wl;
+	bool wl_valid = false, wl_hvalid = false; uint64_t rs_wc = 0, wl_out[5] = { 0, 0, 0, 0, 0 };
 	// f3 with traceback on the grid (hao_trace_grid.cuh): the stage's scratch, compute stream only (hao_window_trace_grid and HAO_DELIVER_TRACE share it) -
 	// flags and selected pairs, entry counts and their scans, the compact array's offsets, the column scratch, the rows of one slice, two counters
 	struct TraceGrid {

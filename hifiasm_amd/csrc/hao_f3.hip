@@ -1,6 +1,7 @@
 // libhao.so, second translation unit: f3, the window-alignment batches (hao_align.cuh) - 36 instantiations of hao_al_kernel (five modes, with and without
 // traceback, bands of one to four words), the four of the delivery path's kernel (hao_ed_deliver.cuh) and the four of the traced grid stage's
-// (hao_trace_grid.cuh) that the rest of the library reaches through hao_al_ed_resident / hao_al_ed_deliver / hao_al_trace_grid only; compiled beside
+// (hao_trace_grid.cuh) that the rest of the library reaches through hao_al_ed_resident / hao_al_ed_deliver / hao_al_trace_grid only, the rescue stage
+// (hao_rescue.cuh, hao_al_rescue) and the window lists (hao_wlist.cuh, hao_al_wlist); compiled beside
 // hao_capi.hip (hifiasm_amd/build.py).
 #include <algorithm>
 #include <cmath>
@@ -11,6 +12,7 @@
 #include "hao_ed_deliver.cuh"
 #include "hao_trace_grid.cuh"
 #include "hao_rescue.cuh"
+#include "hao_wlist.cuh"
 
 // ---- f3 (hao_align.cuh): host side of the window-alignment batches ----
 // tasks -> device, and their order by text window (hao_align.cuh: a wave takes 64 neighbours of that order, which mostly share one text)
@@ -226,6 +228,69 @@ int hao_al_rescue(hao_ctx *c, const hao_ovlp_t *ol, uint64_t n_ol, uint32_t wl, 
 	HIP_TRY(hipStreamSynchronize(c->stream));
 	c->rs_total = c->peek_h[43]; c->rs_rounds = rounds; c->rs_active = na; c->rs_slots = ns;
 	if (G.path.cap > (1ULL << 27)) G.path.release();      // (more than 1 GB of column scratch is not kept between calls)
+	return HAO_OK;
+}
+
+// the window lists (hao_wlist.cuh; hao_window_wlist_ref and HAO_DELIVER_WLIST, hao_batch.hpp): over the n_ol overlaps of the batch whose rescue stage has just
+// run - RA, werr as for hao_al_rescue; pe per slot, the rescue records and their region starts in c->rs; ov = the per-overlap results; n_slots = the batch's
+// covered windows (the bound of the records, so that nothing the plan writes is sized by a count read).  Results into o_woff (records per overlap, scanned),
+// o_wins, o_cigoff and o_cig: the context's own buffers (blocking) or the output set's (streamed: its copy runs under the next batch's compute, which reuses the
+// scratch in c->wl).  out: records, windows swept, re-placement sweeps, cigar entries, untraced windows.  Host round trips: one for the sizes of the sort,
+// the rows and the cigar array, one for the totals at the end (which the streamed path needs to size its arena part).
+int hao_al_wlist(hao_ctx *c, const hao_ovlp_t *ol, uint64_t n_ol, uint32_t wl, hao_ref_args RA, const uint8_t *werr, const hao_rs_ovlp *ov, uint64_t n_slots, uint64_t out[5],
+		DevBuf<uint64_t> &o_woff, DevBuf<hao_rs_win> &o_wins, DevBuf<uint64_t> &o_cigoff, DevBuf<uint16_t> &o_cig)
+{
+	hao_ctx::Wlist &G = c->wl;
+	if (n_slots >= (1ULL << 28)) { hao_set_err(c, "window lists: more than 2^28 covered windows in one batch"); return HAO_EUNSUPP; }
+	HIP_TRY(G.cnt.reserve(n_ol + 2)); HIP_TRY(o_woff.reserve(n_ol + 2)); HIP_TRY(G.plan.reserve(n_slots + 1)); HIP_TRY(o_wins.reserve(n_slots + 1)); HIP_TRY(G.ncig.reserve(n_slots + 2));
+	HIP_TRY(o_cigoff.reserve(n_slots + 2)); HIP_TRY(G.key.reserve(n_slots + 1)); HIP_TRY(G.key2.reserve(n_slots + 1)); HIP_TRY(G.idx.reserve(n_slots + 1)); HIP_TRY(G.sel.reserve(n_slots + 1));
+	HIP_TRY(G.rowof.reserve(n_slots + 1)); HIP_TRY(G.ctr.reserve(8));
+	HIP_TRY(hipMemsetAsync(G.ctr.p, 0, 64, c->stream));
+	hao_wl_args W; W.A.ol = ol; W.A.n_ol = n_ol; W.A.wl = wl; W.A.win_off = RA.win_off; W.A.shift = RA.shift; W.A.tab = RA.tab; W.A.werr = werr; W.A.wpe = c->rs.wpe.p; W.A.len = c->d_len.p;
+	W.rbase = c->rs.rbase.p; W.rec = c->rs.rec.p; W.ov = ov;
+	// sort key of a record that needs a sweep: query read << wbits | grid window (a read has fewer than 2^32 / wl windows)
+	uint32_t wbits = 32; while (wbits > 1 && (wl >> (32 - wbits + 1))) --wbits;
+	uint32_t rbits = 1; while (rbits < 32 && (c->n_reads >> rbits)) ++rbits;
+	const dim3 b_(256), go((unsigned)((n_ol + 255) / 256));
+	hipLaunchKernelGGL(hao_wl_count_kernel, dim3((unsigned)((n_ol + 256) / 256)), b_, 0, c->stream, W, G.cnt.p); HAO_CHECK_LAUNCH();
+	if (int rc = hao_excl_scan_u64(c, G.cnt.p, o_woff.p, n_ol + 1)) return rc;
+	hipLaunchKernelGGL(hao_wl_plan_kernel, go, b_, 0, c->stream, W, o_woff.p, G.plan.p, o_wins.p, G.ncig.p, G.key.p, G.idx.p, wbits, G.ctr.p); HAO_CHECK_LAUNCH();
+	hipLaunchKernelGGL(hao_peek_kernel, dim3(1), dim3(64), 0, c->stream, (const unsigned long long*)(o_woff.p + n_ol), 1, c->peek_d + 48); HAO_CHECK_LAUNCH();
+	hipLaunchKernelGGL(hao_peek_kernel, dim3(1), dim3(64), 0, c->stream, (const unsigned long long*)G.ctr.p, 3, c->peek_d + 49); HAO_CHECK_LAUNCH();
+	HIP_TRY(hipStreamSynchronize(c->stream));
+	const uint64_t N = c->peek_h[48], M = c->peek_h[49], bound = c->peek_h[50];
+	if (N > n_slots || M > N) { hao_set_err(c, "window lists: more records than covered windows"); return HAO_EUNSUPP; }
+	const uint32_t cap = 2 * 31 + 3 + (2 * wl + 62) / 0x3fff;      // (hao_tg_bound for thre <= 31 and a window of wl bases)
+	if (M) {
+		// text order: the records that need a sweep to the front, by (query read, grid window); stable, so overlaps of one window keep their order
+		size_t tb = 0;
+		HIP_TRY(rocprim::radix_sort_pairs(nullptr, tb, G.key.p, G.key2.p, G.idx.p, G.sel.p, N, 0, wbits + rbits, c->stream)); HIP_TRY(hao_tmp(c, tb));
+		HIP_TRY(rocprim::radix_sort_pairs(c->d_tmp.p, tb, G.key.p, G.key2.p, G.idx.p, G.sel.p, N, 0, wbits + rbits, c->stream));
+		// column scratch: 24 bytes per text column (t_len <= wl, + slot 0) and lane, in slices whose columns fit ~4 GB; two rows of `cap` entries per swept record
+		const hao_ed_reads R = hao_al_reads_of(c);
+		const uint64_t ncol = (uint64_t)wl + 1;
+		const uint64_t slice = std::max<uint64_t>(256, std::min<uint64_t>((M + 255) & ~255ULL, ((4ULL << 30) / (24 * ncol)) & ~255ULL));
+		HIP_TRY(G.path.reserve(3 * ncol * slice + 1)); HIP_TRY(G.rows.reserve(M * 2 * (uint64_t)cap + 1));
+		for (uint64_t lo = 0; lo < M; lo += slice) {
+			const uint64_t m = std::min<uint64_t>(slice, M - lo);
+			hipLaunchKernelGGL(hao_wl_trace_kernel, dim3((unsigned)((m + 255) / 256)), b_, 0, c->stream, R, W, G.plan.p, G.sel.p + lo, m, lo, G.path.p, slice, G.rows.p, cap, o_wins.p, G.ncig.p, G.rowof.p, G.ctr.p); HAO_CHECK_LAUNCH();
+		}
+	}
+	HIP_TRY(hipMemsetAsync(G.ncig.p + N, 0, 8, c->stream));
+	if (int rc = hao_excl_scan_u64(c, G.ncig.p, o_cigoff.p, N + 1)) return rc;
+	HIP_TRY(o_cig.reserve(bound + 1));
+	if (N) { hipLaunchKernelGGL(hao_wl_fill_kernel, dim3((unsigned)((N + 255) / 256)), b_, 0, c->stream, W, G.plan.p, o_wins.p, N, o_cigoff.p, G.rowof.p, G.rows.p, cap, o_cig.p, bound); HAO_CHECK_LAUNCH(); }
+	hipLaunchKernelGGL(hao_peek_kernel, dim3(1), dim3(64), 0, c->stream, (const unsigned long long*)(o_cigoff.p + N), 1, c->peek_d + 52); HAO_CHECK_LAUNCH();
+	hipLaunchKernelGGL(hao_peek_kernel, dim3(1), dim3(64), 0, c->stream, (const unsigned long long*)G.ctr.p, 6, c->peek_d + 53); HAO_CHECK_LAUNCH();
+	HIP_TRY(hipStreamSynchronize(c->stream));
+	if (G.path.cap > (1ULL << 27)) G.path.release();      // (more than 1 GB of column scratch is not kept between calls)
+	if (G.rows.cap > (1ULL << 29)) G.rows.release();      // (nor more than 1 GB of rows)
+	if (c->peek_h[52] > bound) { hao_set_err(c, "window lists: more cigar entries than their bound"); return HAO_EUNSUPP; }      // (hao_tg_bound rules it out)
+	if (c->peek_h[57] || c->peek_h[58]) {      // (a broken invariant is an error, not an untraced window)
+		hao_set_err(c, "window lists: " + std::to_string(c->peek_h[58]) + " records whose task could not be rebuilt from the rescue records, " + std::to_string(c->peek_h[57]) + " whose traced sweep lost the distance-only alignment or overran its row");
+		return HAO_EUNSUPP;
+	}
+	out[0] = N; out[1] = M; out[2] = c->peek_h[56]; out[3] = c->peek_h[52]; out[4] = c->peek_h[55];
 	return HAO_OK;
 }
 

@@ -14,7 +14,7 @@
 //      the result and steps its state to the next alignment.  Rounds repeat until a launch reports no lane left; the host reads that one count per round.
 //   3. hao_rs_verdict_kernel: a thread per overlap, every overlap: the running align_length over its slots and rescued records, the exit window, the verdict;
 //      records beyond the exit are dropped (the reference never computed them).
-// Cigars are not kept: only ps, pe and err of a traced step are used.
+// Cigars are not kept: only ps, pe and err of a traced step are used (hao_wlist.cuh traces every window of a passing overlap again and keeps the walks).
 #pragma once
 #include "hao_align.cuh"
 #include "hao_grid_pair.cuh"

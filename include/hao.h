@@ -290,7 +290,8 @@ int hao_fetch_ed_grid(hao_ctx *c, hao_ed_task_t *tasks, hao_ed_result_t *res, ui
  *   hao_deliver_ed_config_ref: this context's following HAO_DELIVER_ED batches are reference-placed (hao_deliver_ed_config switches back).  The 3 bytes per pair
  *                              and the per-read offsets travel as before, the summaries (16 bytes per overlap) after them; hao_deliver_ed's view names placement
  *                              and e_rate, and hao_unpack_ed rebuilds a read's tasks from the delivered overlaps AND their delivered fake cigars.
- * Not built: the traced stage in reference placement - HAO_DELIVER_TRACE on a reference-placed context returns HAO_EUNSUPP, hao_window_trace_grid has no
+ * The traced stage in reference placement is hao_window_wlist_ref / HAO_DELIVER_WLIST (below; it traces the windows of the overlaps that pass the rescue stage's
+ * verdict).  The diagonal traced grid has no reference-placed form: HAO_DELIVER_TRACE on a reference-placed context returns HAO_EUNSUPP, hao_window_trace_grid has no
  * reference-placed form, and hao_unpack_trace returns 0 for a reference-placed view (never diagonal cigars under a reference-placed configuration).  The reference's rescue of unaligned windows from their aligned neighbours, its early exit and its
  * return value: hao_window_rescue_ref below (blocking path). */
 #define HAO_PLACE_DIAG 0u
@@ -347,7 +348,7 @@ void hao_ref_thresholds(uint32_t window, double e_rate, uint8_t *out /* [window 
  *                       offsets that do not ascend or run past n_wins, a record whose window its overlap does not cover - the overlap's window range is
  *                       rebuilt from the delivered overlap - or that lies beyond read rid's grid as len, the lengths of all reads, has it).  Pure host code, any
  *                       thread.
- * Not built: the cigars of rescued windows, the traced stage in reference placement, gen_extend_err_exz and everything after it in gen_hc_r_alin. */
+ * The cigars of every window of an overlap that passed: hao_window_wlist_ref below.  Not built: gen_extend_err_exz and everything after it in gen_hc_r_alin. */
 typedef struct { uint16_t verdict, flags; uint32_t exit_win, align_length, n_rescued; } hao_rescue_ovlp_t;      /* exit_win 0xffffffff: no early exit */
 typedef struct { int32_t y_start, y_end; uint32_t win, info; } hao_rescue_win_t;      /* win: grid window; info: err | thre << 8 | direction << 16 | flags */
 #define HAO_RESCUE_FWD 0u
@@ -368,6 +369,57 @@ int hao_fetch_rescue(hao_ctx *c, uint64_t rid, const hao_rescue_ovlp_t **ovlp, u
 int hao_deliver_rescue(hao_ctx *c, int slot, hao_rescue_delivery_t *out);
 uint64_t hao_unpack_rescue(const hao_delivery_t *d, const hao_ed_delivery_t *e, const hao_rescue_delivery_t *r, const uint32_t *len, uint64_t rid,
                            hao_rescue_ovlp_t *ovlp, uint64_t *win_off, hao_rescue_win_t *wins, uint64_t cap_ovlp, uint64_t cap_wins);
+/* The product of align_hc_ed_post_extz: z->w_list, the window records of every overlap with their alignments, as the reference holds them once every window
+ * has been through gen_backtrace_adv_exz (Correct.cpp:12563-12639) - what gen_extend_err_exz and gen_hc_fast_cigar0 read next.  Per overlap whose rescue
+ * verdict is 1 (the others get an empty list: the reference drops them, :25637), one record per window that is aligned after the rescue, in ascending window
+ * order.  The trace is a pure function of the record align_hc_ed_post_extz left, so every window is traced eagerly, on the task it aligned on:
+ *   HAO_WLIST_PRIMARY / HAO_RESCUE_ANCHOR  the first-placement task (hao_window_ed_ref's), with the primary (err, pe);
+ *   HAO_RESCUE_FWD                         the rescue task from the predecessor's y_end + 1 as the rescue left it;
+ *   HAO_RESCUE_BWD                         the rescue task that ends at the successor's final y_start - 1.
+ *   err == 0:  the traced function's shortcut (Levenshtein_distance.h:3783-3787): no sweep, y_start = y_end - (q_l - 1), one match run of q_l bases;
+ *   err > 0:   ed_band_cal_semi_64_w_absent_diag_trace + gen_trace, then recal_boundary_exz (:2429-2468) where the alignment touches an end of the pattern: the
+ *              re-placed task is swept too and taken iff it aligns with a strictly smaller err (HAO_RESCUE_REPLACED; its cigar replaces the first);
+ *   a task outside HAO_ALIGN_SEMI's domain: nothing is guessed - the record keeps its distance-only err and y_end, y_start = the task's start, no cigar,
+ *              HAO_WLIST_UNTRACED; a re-placement outside the domain is not made and the first trace stands.
+ * Backward-rescued windows and anchors come out with the y_start, y_end, err and re-placed bit hao_fetch_rescue reports (they are traced again here from the
+ * same tasks; the rescue stage and its records are unchanged).  Cigars are in push_trace's encoding and in the orientation of
+ * hao_window_trace_batch(HAO_ALIGN_SEMI) for the same task, at most 2 * 31 + 3 entries plus the 0x3fff splits.
+ *   hao_window_wlist_ref: blocking, over the batch hao_window_ed_ref and hao_window_rescue_ref have just processed (HAO_EINVAL without both, after another
+ *                         window-alignment call or a new batch; HAO_EUNSUPP in a sharded engine).  out = window records, windows swept (err > 0, in the domain),
+ *                         re-placement sweeps made, cigar entries, untraced windows.  The rescue results stay fetchable; a second call gives the same result.
+ *   hao_fetch_wlist:      read rid's overlaps, aligned with hao_fetch_overlaps / hao_fetch_rescue: *n_ol of them, the records of overlap i at
+ *                         wins[win_off[i] .. win_off[i + 1]) (counted from the read's first record), the cigar of record j at cigars[cig_off[j] .. cig_off[j + 1])
+ *                         (counted from the read's first entry).  Pointers valid until the next call on the context.
+ * HAO_DELIVER_WLIST in the parts of hao_overlap_batch_async runs the same stage inside the batch, after the rescue stage, and delivers after every other part:
+ * n_ol + 1 record offsets, the records, n_wins + 1 entry offsets and the entries (each padded to 64 bytes in the arena).  Valid only together with
+ * HAO_DELIVER_ED | HAO_DELIVER_RESCUE on a context configured by hao_deliver_ed_config_ref (else HAO_EINVAL); HAO_EUNSUPP in a sharded engine.  A batch without
+ * the part keeps its arena layout and byte count.
+ *   hao_deliver_wlist:    the view of a slot whose batch asked for the part, valid after hao_deliver_wait on that slot (HAO_EINVAL otherwise).
+ *   hao_unpack_wlist:     read rid's lists out of the four views - win_off[0 .. n] counted from the read's first record, the records, cig_off[0 .. records]
+ *                         counted from the read's first entry, the entries.  Returns the read's overlap count n; nothing is written when n exceeds cap_ovlp,
+ *                         the records cap_wins, the entries cap_cigars, or an output pointer is NULL; 0 for a read outside the batch; UINT64_MAX for a NULL
+ *                         view, a view that is not reference-placed, or views that do not belong together (overlap counts that differ, offsets that do not
+ *                         ascend or run past their totals, a record whose window its overlap does not cover or that lies beyond read rid's grid as len has
+ *                         it, a record in an overlap whose delivered verdict is 0, entry counts that do not add up).  Pure host code, any thread.
+ * Not built: gen_extend_err_exz and everything after it in gen_hc_r_alin - its extension functions (Reserve_Banded_BPM_Extension[_REV]) are not reachable
+ * through the reference harness, so nothing could hold them. */
+typedef struct { int32_t y_start, y_end; uint32_t win, info; } hao_wlist_win_t;      /* info: err | thre << 8 | source << 16 | flags */
+#define HAO_WLIST_PRIMARY 3u               /* source: a first-placement window the rescue did not trace (beside HAO_RESCUE_FWD / BWD / ANCHOR) */
+#define HAO_WLIST_UNTRACED (1u << 19)      /* info: the task lies outside the traced domain: distance-only values, no cigar */
+#define HAO_DELIVER_WLIST 64u      /* the window lists of the batch (with HAO_DELIVER_ED | HAO_DELIVER_RESCUE in reference placement; hao_deliver_wlist, hao_unpack_wlist) */
+typedef struct {
+	uint64_t n_ol, n_wins, n_cigar;              /* overlaps, window records and cigar entries of the batch */
+	uint64_t n_swept, n_replace, n_untraced;     /* windows swept, re-placement sweeps made, untraced windows (hao_window_wlist_ref's out[1], out[2], out[4]) */
+	const uint64_t *win_off;                     /* [n_ol + 1]: records of overlap i = wins[win_off[i] .. win_off[i + 1]) */
+	const hao_wlist_win_t *wins;                 /* [n_wins] */
+	const uint64_t *cig_off;                     /* [n_wins + 1]: entries of record j = cigars[cig_off[j] .. cig_off[j + 1]) */
+	const uint16_t *cigars;                      /* [n_cigar] */
+} hao_wlist_delivery_t;
+int hao_window_wlist_ref(hao_ctx *c, uint64_t out[5]);
+int hao_deliver_wlist(hao_ctx *c, int slot, hao_wlist_delivery_t *out);
+uint64_t hao_unpack_wlist(const hao_delivery_t *d, const hao_ed_delivery_t *e, const hao_rescue_delivery_t *r, const hao_wlist_delivery_t *w, const uint32_t *len, uint64_t rid,
+                          uint64_t *win_off, hao_wlist_win_t *wins, uint64_t *cig_off, uint16_t *cigars, uint64_t cap_ovlp, uint64_t cap_wins, uint64_t cap_cigars);
+int hao_fetch_wlist(hao_ctx *c, uint64_t rid, uint64_t *n_ol, const uint64_t **win_off, const hao_wlist_win_t **wins, const uint64_t **cig_off, const uint16_t **cigars);
 /* test support (host code, no context): the task of a rescue alignment as the kernel rebuilds it (window `win` of overlap z against the target from toff on;
  * tab = hao_ref_thresholds; 0: refused), so that the tests can hold the builder against work items recorded from the reference */
 int hao_rescue_task(const hao_ovlp_t *z, uint32_t win, uint32_t window, int64_t toff, const uint8_t *tab, uint32_t target_len, hao_ed_task_t *out);

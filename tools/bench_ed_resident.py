@@ -7,7 +7,10 @@ delivered step.  usage: python tools/bench_ed_resident.py --deliver [--workload 
 
 --window W: the window of the diagonal grid (default 375).  --ref WINDOW,ERATE (blocking and --deliver): the same stage in REFERENCE placement (hao_window_ed_ref /
 hao_deliver_ed_config_ref: fake-cigar shift, per-window thresholds, init_waln), e.g. --ref 775,0.04 beside the diagonal stage at --window 775 and thre 31.
---rescue (blocking, with --ref): then the rescue stage (hao_window_rescue_ref) on the same batch: wall and device time per call, rescued windows, verdicts."""
+--rescue (blocking, with --ref): then the rescue stage (hao_window_rescue_ref) on the same batch: wall and device time per call, rescued windows, verdicts.
+--wlist (with --ref --rescue): then the window lists (hao_window_wlist_ref) on the same batch: wall and device time per call, records, windows swept,
+re-placement sweeps, cigar entries, untraced windows and their shares.  --deliver --ref W,E --wlist: the streamed pass also with OL|CL|ED|RESCUE and with
+OL|CL|ED|RESCUE|WLIST, alternating: wall time per pass and arena bytes per batch."""
 import argparse
 import json
 import os
@@ -26,6 +29,9 @@ def main():
     rescue = "--rescue" in argv
     if rescue:
         argv.remove("--rescue")
+    wlist = "--wlist" in argv
+    if wlist:
+        argv.remove("--wlist")
     for flag in ("--ref", "--window"):
         if flag in argv:
             i = argv.index(flag); val = argv[i + 1]; del argv[i:i + 2]
@@ -57,6 +63,14 @@ def main():
         extra = {"rescue_ms_per_call_best": round(min(tr) * 1e3, 3), "rescue_ms_per_call_all": [round(x * 1e3, 3) for x in tr], "rescued_windows": n_res,
                  "rescue_device_ms": dev_ms, "verdict1_overlaps": v1, "overlaps_judged": ol,
                  "rescue_over_ed": round(min(tr) / min(ts), 4)}
+        if wlist:      # the window lists over the same batch (the stage may run again on the same rescue results)
+            out = e.window_wlist_ref(); tw = []
+            for _ in range(reps):
+                t0 = time.time(); out = e.window_wlist_ref(); tw.append(time.time() - t0)
+            extra.update({"wlist_ms_per_call_best": round(min(tw) * 1e3, 3), "wlist_ms_per_call_all": [round(x * 1e3, 3) for x in tw], "wlist_device_ms": dict(e.stage_times()).get("wlist_ref"),
+                          "wlist_records": out[0], "wlist_swept": out[1], "wlist_replacement_sweeps": out[2], "wlist_cigar_entries": out[3], "wlist_untraced": out[4],
+                          "wlist_share_err0": round((out[0] - out[1] - out[4]) / max(1, out[0]), 4), "wlist_share_swept": round(out[1] / max(1, out[0]), 4),
+                          "wlist_share_replacement_tried": round(out[2] / max(1, out[0]), 4), "wlist_share_untraced": round(out[4] / max(1, out[0]), 4)})
     print(json.dumps({**extra, "workload": "bacterial5M_hifi30x", "reads": int(rs.n), "overlaps": e.batch_totals()["overlaps"], "placement": "reference" if ref else "diagonal",
                       "window": ref[0] if ref else window, "thre": None if ref else thre, "e_rate": ref[1] if ref else None, "pairs": n,
                       "ms_per_call_best": round(min(ts) * 1e3, 3), "ms_per_call_all": [round(x * 1e3, 3) for x in ts], "pairs_per_s": round(n / min(ts)),
@@ -66,7 +80,7 @@ def main():
 
 def deliver(a):
     from hifiasm_amd import workloads
-    from hifiasm_amd.api import Engine, DELIVER_OL, DELIVER_CL, DELIVER_ED
+    from hifiasm_amd.api import Engine, DELIVER_OL, DELIVER_CL, DELIVER_ED, DELIVER_RESCUE, DELIVER_WLIST
     hi_all = workloads.n_reads_of(a.workload)
     rs = workloads.workload_reads(a.workload)
     e = Engine(0); e.set_readset(rs); e.ha_ft_gen(); e.ha_pt_gen()
@@ -98,8 +112,13 @@ def deliver(a):
 
     one_pass(DELIVER_OL | DELIVER_CL | DELIVER_ED); one_pass(DELIVER_OL | DELIVER_CL)      # warm-up (allocations, arenas)
     walls = {"ol_cl": [], "ol_cl_ed": []}; last = {}
+    passes = [("ol_cl", DELIVER_OL | DELIVER_CL), ("ol_cl_ed", DELIVER_OL | DELIVER_CL | DELIVER_ED)]
+    if a.wlist and ref:      # the rescue stage and the window lists riding along: ED | RESCUE against ED | RESCUE | WLIST
+        passes += [("ol_cl_ed_rescue", DELIVER_OL | DELIVER_CL | DELIVER_ED | DELIVER_RESCUE), ("ol_cl_ed_rescue_wlist", DELIVER_OL | DELIVER_CL | DELIVER_ED | DELIVER_RESCUE | DELIVER_WLIST)]
+        walls.update({"ol_cl_ed_rescue": [], "ol_cl_ed_rescue_wlist": []})
+        one_pass(passes[-1][1])      # warm-up
     for _ in range(a.reps):
-        for key, parts in (("ol_cl", DELIVER_OL | DELIVER_CL), ("ol_cl_ed", DELIVER_OL | DELIVER_CL | DELIVER_ED)):
+        for key, parts in passes:
             w, per = one_pass(parts); walls[key].append(round(w, 2)); last[key] = per
     batches = []
     for b0, b1 in zip(last["ol_cl"], last["ol_cl_ed"]):
@@ -110,6 +129,7 @@ def deliver(a):
                             kernels_ms_ol_cl=round(b0["kernels_ms"], 3), kernels_ms_ol_cl_ed=round(b1["kernels_ms"], 3)))
     print(json.dumps({"workload": a.workload, "reads_indexed": int(rs.n), "placement": "reference" if ref else "diagonal", "window": ref[0] if ref else a.window,
                       "thre": None if ref else a.thre, "e_rate": ref[1] if ref else None, "batches": batches,
+                      "delivered_step_ms_all": walls, "arena_bytes_last": {k: [b["bytes"] for b in v] for k, v in last.items()},
                       "delivered_step_ms_ol_cl": walls["ol_cl"], "delivered_step_ms_ol_cl_ed": walls["ol_cl_ed"],
                       "delivered_step_ms_best": {k: min(v) for k, v in walls.items()},
                       "what": "passes over the listed batches with both slots in flight: host wall time per pass with OL|CL and with OL|CL|ED (alternating), the ED stage's device time per batch (stage_times), the bytes it adds to the arena"}))
@@ -127,6 +147,7 @@ if __name__ == "__main__":
         ap.add_argument("--reps", type=int, default=3)
         ap.add_argument("--window", type=int, default=375)
         ap.add_argument("--ref", default="", help="WINDOW,ERATE: reference placement")
+        ap.add_argument("--wlist", action="store_true", help="with --ref: also passes with ED | RESCUE and with ED | RESCUE | WLIST")
         deliver(ap.parse_args())
     else:
         main()
