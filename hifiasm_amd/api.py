@@ -86,6 +86,7 @@ ABI_SYMBOLS = [
     "hao_window_ed_ref", "hao_fetch_ed_ovlp", "hao_deliver_ed_config_ref", "hao_ref_thresholds",
     "hao_window_rescue_ref", "hao_fetch_rescue", "hao_rescue_task", "hao_deliver_rescue", "hao_unpack_rescue",
     "hao_window_wlist_ref", "hao_fetch_wlist", "hao_deliver_wlist", "hao_unpack_wlist",
+    "hao_dist_gather_reads", "hao_reads_digest",
 ]
 
 
@@ -250,6 +251,8 @@ def lib():
         L.hao_loop_create.argtypes = [C.c_int]; L.hao_loop_create.restype = vp
         L.hao_loop_destroy.argtypes = [vp]
         L.hao_dist_init_loopback.argtypes = [vp, vp, C.c_int]
+        L.hao_dist_gather_reads.argtypes = [vp]
+        L.hao_reads_digest.argtypes = [vp, u64p]
         _LIB = L
     return _LIB
 
@@ -284,7 +287,7 @@ class Engine:
     def attach(self):
         """hao_attach: a second batch context (own stream, scratch, results) over this engine's reads and index, for a second host thread"""
         v = Engine.__new__(Engine)
-        v.L = self.L; v.opt = self.opt; v.bw_thres = self.bw_thres; v.n_reads = self.n_reads; v.owner = self; v.lengths = getattr(self, "lengths", None)
+        v.L = self.L; v.opt = self.opt; v.bw_thres = self.bw_thres; v.n_reads = self.n_reads; v.owner = self; v.lengths = getattr(self, "lengths", None); v.rid_base = getattr(self, "rid_base", 0)
         h = C.c_void_p()
         self._ck(self.L.hao_attach(self.h, C.byref(h)), "hao_attach")
         v.h = h
@@ -349,6 +352,26 @@ class Engine:
 
     def dist_init_loopback(self, group, rank: int):
         self._ck(self.L.hao_dist_init_loopback(self.h, group, rank), "hao_dist_init_loopback")
+
+    def dist_gather_reads(self):
+        """hao_dist_gather_reads (a collective): the bases of ALL reads on every rank of a sharded engine, which opens the exact check and the window-alignment
+        stages to it; a no-op on an unsharded engine and while the store is valid"""
+        self._ck(self.L.hao_dist_gather_reads(self.h), "hao_dist_gather_reads")
+
+    def reads_digest(self):
+        """hao_reads_digest: (bases, N sites) digests of the reads the stages beyond the seam see - equal on every rank of a sharded engine and on an unsharded one"""
+        out = (C.c_uint64 * 2)()
+        self._ck(self.L.hao_reads_digest(self.h, out), "hao_reads_digest")
+        return int(out[0]), int(out[1])
+
+    def delivery_global(self, d):
+        """a copy of a sharded engine's Delivery with rid_lo as a GLOBAL read id: what the delivered_* / hao_unpack_* helpers take together with the lengths
+        of all reads and global read ids (they index one lengths array by the delivery's read ids and by y_id)"""
+        g = Delivery.from_buffer_copy(d)
+        g.rid_lo = int(d.rid_lo) + getattr(self, "rid_base", 0)
+        for k in ("ed", "tr", "rs", "wl"):
+            setattr(g, k, getattr(d, k, None))
+        return g
 
     # ---- ha_ft_gen / ha_pt_gen ----
     def ha_ft_gen(self):

@@ -171,12 +171,12 @@ static int hao_exact_run(hao_ctx *c)
 {
 	hao_ctx::Batch &B = *c->batch;
 	if (B.exact_valid) return HAO_OK;
-	if (hao_is_sharded(c)) { hao_set_err(c, "hao_exact_check needs the bases of the target reads: single-device mode only"); return HAO_EUNSUPP; }
+	HAO_STAGE_VIEW(c, V, "hao_exact_check needs the bases of the target reads");
 	HIP_TRY(B.O().exact.reserve(B.n_ol + 1));
 	if (B.n_ol) {
 		hao_exact_args a;
-		a.ol = B.O().ol_out.p; a.n_ol = B.n_ol; a.rid_base = c->rid_base; a.packed = c->d_packed.p; a.pk_off = c->d_pk_off.p; a.len = c->d_len.p;
-		a.nsite_off = c->has_n ? c->d_nsite_off.p : nullptr; a.nsite = c->has_n ? c->d_nsite.p : nullptr; a.flags = B.O().exact.p;
+		a.ol = B.O().ol_out.p; a.n_ol = B.n_ol; a.rid_base = V.id_base; a.packed = V.packed; a.pk_off = V.pk_off; a.len = V.len;
+		a.nsite_off = V.nsite_off; a.nsite = V.nsite; a.flags = B.O().exact.p;
 		hipLaunchKernelGGL(hao_exact_check_kernel, dim3((unsigned)((B.n_ol + 3) / 4)), dim3(256), 0, c->stream, a);
 		HAO_CHECK_LAUNCH();
 	}
@@ -217,7 +217,8 @@ static int hao_ed_ref_upload(hao_ctx *c, uint32_t wl, double e_rate, DevBuf<uint
 static void hao_ed_grid_launch(hao_ctx *c, int out, uint32_t place, uint32_t wl, uint32_t thre, uint32_t nword, const uint64_t *wbase, uint64_t *cnt_or_off, hao_ed_task_t *tasks, hao_ed_pair *pairs, hao_ref_args A)
 {
 	hao_ctx::Batch &B = *c->batch; hao_ctx::Batch::OutSet &O = B.O();
-	auto go = [&](auto kernel) { hipLaunchKernelGGL(kernel, dim3((unsigned)((B.n + 3) / 4)), dim3(256), 0, c->stream, O.ol_out.p, O.fin_off.p, c->d_len.p, B.lo, B.n, wl, thre, nword, wbase, cnt_or_off, tasks, pairs, A); };
+	hao_read_view V; (void)hao_reads_view(c, &V);      // (the callers hold a view: they refused otherwise)
+	auto go = [&](auto kernel) { hipLaunchKernelGGL(kernel, dim3((unsigned)((B.n + 3) / 4)), dim3(256), 0, c->stream, O.ol_out.p, O.fin_off.p, V.len, V.local0 + B.lo, B.n, wl, thre, nword, wbase, cnt_or_off, tasks, pairs, A); };
 	switch (out * 2 + (place == HAO_PLACE_REF)) {
 	case ED_GRID_COUNT * 2: go(ed_grid_kernel<ED_GRID_COUNT, HAO_PLACE_DIAG>); break;
 	case ED_GRID_COUNT * 2 + 1: go(ed_grid_kernel<ED_GRID_COUNT, HAO_PLACE_REF>); break;
@@ -242,10 +243,11 @@ static int hao_ed_grid_pairs(hao_ctx *c, const char *who, uint32_t place, uint32
 {
 	hao_ctx::Batch &B = *c->batch; const uint64_t n = B.n; const bool ref = place == HAO_PLACE_REF && B.n_ol;      // (no overlap: no shifts, no counter - and no pair)
 	*L = hao_grid_list();
+	hao_read_view V; if (!hao_reads_view(c, &V)) { hao_set_err(c, std::string(who) + " needs the bases of both reads: single-device mode only"); return HAO_EUNSUPP; }
 	for (uint64_t r = 0; r < n; ++r) L->W += (c->h_len[B.lo + r] + wl - 1) / wl;
 	const uint64_t W = L->W;
 	HIP_TRY(B.ed_nwin.reserve(n + 2)); HIP_TRY(B.ed_wbase.reserve(n + 2)); HIP_TRY(B.ed_wcnt.reserve(W + 2)); HIP_TRY(B.ed_woff.reserve(W + 2));
-	hipLaunchKernelGGL(ed_grid_nwin_kernel, dim3((unsigned)((n + 256) / 256)), dim3(256), 0, c->stream, c->d_len.p, B.lo, n, wl, B.ed_nwin.p); HAO_CHECK_LAUNCH();
+	hipLaunchKernelGGL(ed_grid_nwin_kernel, dim3((unsigned)((n + 256) / 256)), dim3(256), 0, c->stream, V.len, V.local0 + B.lo, n, wl, B.ed_nwin.p); HAO_CHECK_LAUNCH();
 	if (int rc = hao_excl_scan_u64(c, B.ed_nwin.p, B.ed_wbase.p, n + 1)) return rc;
 	HIP_TRY(hipMemsetAsync(B.ed_wcnt.p + W, 0, 8, c->stream));
 	if (ref) { if (int rc = hao_ed_ref_front(c, wl, tab, &L->A, &L->Wc)) return rc; }
@@ -269,7 +271,7 @@ int hao_al_ed_resident(hao_ctx *c, uint64_t n_tasks, uint32_t nword);      // (h
 static int hao_ed_grid_run(hao_ctx *c, uint32_t wl, uint32_t thre, uint64_t *n_tasks)
 {
 	hao_ctx::Batch &B = *c->batch; *n_tasks = 0; c->al_grid_n = 0;
-	if (hao_is_sharded(c)) { hao_set_err(c, "hao_window_ed_grid needs the bases of both reads: single-device mode only"); return HAO_EUNSUPP; }
+	{ HAO_STAGE_VIEW(c, V, "hao_window_ed_grid needs the bases of both reads"); (void)V; }
 	if (wl == 0 || thre > HAO_ED_MAX_THRE) { hao_set_err(c, "hao_window_ed_grid: window length 0 or threshold beyond the widest band"); return HAO_EINVAL; }
 	const uint32_t nword = (2 * thre + 1 + 63) / 64;
 	if (B.n == 0 || B.n_ol == 0) return HAO_OK;
@@ -284,7 +286,7 @@ static int hao_ed_grid_run(hao_ctx *c, uint32_t wl, uint32_t thre, uint64_t *n_t
 static int hao_ed_ref_run(hao_ctx *c, uint32_t wl, double e_rate, uint64_t *n_tasks, uint64_t *unresolved)
 {
 	hao_ctx::Batch &B = *c->batch; *n_tasks = 0; if (unresolved) *unresolved = 0; c->al_grid_n = 0; c->rf_valid = false; c->rf_hvalid = false; c->rf_unres = 0; c->rs_valid = false; c->wl_valid = false; c->rf_T = 0;
-	if (hao_is_sharded(c)) { hao_set_err(c, "hao_window_ed_ref needs the bases of both reads: single-device mode only"); return HAO_EUNSUPP; }
+	{ HAO_STAGE_VIEW(c, V, "hao_window_ed_ref needs the bases of both reads"); (void)V; }
 	if (!hao_ed_ref_args_ok(wl, e_rate)) { hao_set_err(c, "hao_window_ed_ref: window length 0, window + 62 beyond 16 bits, or e_rate outside (0, 1)"); return HAO_EINVAL; }
 	if (B.n == 0 || B.n_ol == 0) { c->rf_valid = true; return HAO_OK; }
 	if (B.n_ol >= (1ULL << 32)) { hao_set_err(c, "hao_window_ed_ref: more than 2^32 overlaps in one batch"); return HAO_EUNSUPP; }
@@ -312,6 +314,7 @@ static int hao_rescue_ref_run(hao_ctx *c, uint64_t *n_rescued)
 {
 	hao_ctx::Batch &B = *c->batch; *n_rescued = 0; c->rs_valid = false; c->rs_hvalid = false; c->wl_valid = false;
 	if (!c->rf_valid || c->al_grid_n != c->rf_T) { hao_set_err(c, "hao_window_rescue_ref: hao_window_ed_ref has not run on this batch (or another window-alignment call has run since)"); return HAO_EINVAL; }
+	{ HAO_STAGE_VIEW(c, V, "hao_window_rescue_ref needs the bases of both reads"); (void)V; }      // (the gathered store has gone since hao_window_ed_ref)
 	if (B.n == 0 || B.n_ol == 0) { c->rs_total = c->rs_rounds = c->rs_active = c->rs_slots = 0; c->rs_valid = true; return HAO_OK; }
 	hao_ref_args A; A.win_off = c->rf.woff.p; A.shift = c->rf.shift.p; A.tab = c->rf_tab.p;
 	uint64_t Wc = 0; HIP_TRY(hipMemcpyAsync(&Wc, c->rf.woff.p + B.n_ol, 8, hipMemcpyDeviceToHost, c->stream)); HIP_TRY(hipStreamSynchronize(c->stream));
@@ -328,7 +331,7 @@ static int hao_wlist_ref_run(hao_ctx *c, uint64_t out[5])
 {
 	hao_ctx::Batch &B = *c->batch; c->wl_valid = false; c->wl_hvalid = false;
 	for (int k = 0; k < 5; ++k) out[k] = 0;
-	if (hao_is_sharded(c)) { hao_set_err(c, "hao_window_wlist_ref needs the bases of both reads: single-device mode only"); return HAO_EUNSUPP; }
+	{ HAO_STAGE_VIEW(c, V, "hao_window_wlist_ref needs the bases of both reads"); (void)V; }
 	if (!c->rf_valid || !c->rs_valid || c->al_grid_n != c->rf_T) { hao_set_err(c, "hao_window_wlist_ref: hao_window_ed_ref and hao_window_rescue_ref have not both run on this batch (or another window-alignment call has run since)"); return HAO_EINVAL; }
 	if (B.n && B.n_ol && c->rs_wc) {
 		hao_ref_args A; A.win_off = c->rf.woff.p; A.shift = c->rf.shift.p; A.tab = c->rf_tab.p;
@@ -425,7 +428,7 @@ static int hao_trace_grid_run(hao_ctx *c, uint32_t wl, uint32_t thre, uint64_t o
 {
 	hao_ctx::Batch &B = *c->batch; hao_ctx::Batch::OutSet &O = B.O(); const uint64_t n = B.n;
 	c->tg_valid = false; out[0] = out[1] = out[2] = out[3] = 0;
-	if (hao_is_sharded(c)) { hao_set_err(c, "hao_window_trace_grid needs the bases of both reads: single-device mode only"); return HAO_EUNSUPP; }
+	{ HAO_STAGE_VIEW(c, V, "hao_window_trace_grid needs the bases of both reads"); (void)V; }
 	if (wl == 0 || thre > HAO_ED_MAX_THRE || (uint64_t)wl + 2 * (uint64_t)thre >= 0xffff) { hao_set_err(c, "hao_window_trace_grid: window length 0, threshold beyond the widest band, or window + 2 thre beyond 16 bits"); return HAO_EINVAL; }
 	const uint32_t nword = (2 * thre + 1 + 63) / 64;
 	c->tg_wl = wl; c->tg_thre = thre; c->tg_n = c->tg_nsel = c->tg_ncig = c->tg_nuntr = 0;

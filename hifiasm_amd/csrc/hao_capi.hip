@@ -12,6 +12,7 @@
 #include "hao_chain.cuh"
 #include "hao_deliver.cuh"
 #include "hao_comm.hpp"
+#include "hao_gather.hpp"
 #include "hao_pipeline.hpp"
 #include "hao_tables.hpp"
 #include "hao_batch.hpp"
@@ -82,6 +83,7 @@ int hao_set_reads(hao_ctx *c, const uint8_t *packed, const uint64_t *pk_off, con
 {
 	if (!c || !packed || !pk_off || !len) return HAO_EINVAL;
 	HAO_NOT_ON_VIEW(c, "hao_set_reads"); ++c->index_gen;
+	hao_gather_drop(c);      // (a gathered store describes the reads it was gathered from)
 	if (n_reads >= (1ULL << 28)) { hao_set_err(c, "more than 2^28 reads (htab.cpp:765)"); return HAO_EUNSUPP; }
 	HIP_TRY(hipSetDevice(c->device));
 	c->n_reads = n_reads; c->n_pk_bytes = pk_off[n_reads]; c->max_len = 0;
@@ -118,6 +120,7 @@ int hao_set_shard(hao_ctx *c, uint64_t rid_base, uint64_t n_total, const uint32_
 {
 	if (!c || !all_len || rid_base + c->n_reads > n_total) return HAO_EINVAL;
 	HAO_NOT_ON_VIEW(c, "hao_set_shard"); ++c->index_gen;
+	hao_gather_drop(c);
 	if (n_total >= (1ULL << 28)) { hao_set_err(c, "more than 2^28 reads (htab.cpp:765)"); return HAO_EUNSUPP; }
 	for (uint64_t i = 0; i < c->n_reads; ++i) if (all_len[rid_base + i] != c->h_len[i]) { hao_set_err(c, "all_len disagrees with the local read lengths"); return HAO_EINVAL; }
 	HIP_TRY(hipSetDevice(c->device));

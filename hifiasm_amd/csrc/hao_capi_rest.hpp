@@ -116,18 +116,18 @@ int hao_overlap_batch_async(hao_ctx *c, uint64_t rid_lo, uint64_t rid_hi, const 
 	if (c) { if (int rc = hao_view_refresh(c)) return rc; }
 	if (!c || rid_lo > rid_hi || rid_hi > c->n_reads || !(parts & (HAO_DELIVER_OL | HAO_DELIVER_CL | HAO_DELIVER_EXACT))) return HAO_EINVAL;
 	if (parts & HAO_DELIVER_ED) {
-		if (hao_is_sharded(c)) { hao_set_err(c, "HAO_DELIVER_ED needs the bases of both reads: single-device mode only"); return HAO_EUNSUPP; }
+		{ HAO_STAGE_VIEW(c, V, "HAO_DELIVER_ED needs the bases of both reads"); (void)V; }
 		if (!(parts & HAO_DELIVER_OL)) { hao_set_err(c, "HAO_DELIVER_ED needs HAO_DELIVER_OL: the decoder rebuilds the pairs from the delivered overlaps"); return HAO_EINVAL; }
 		if (!c->ded_window) { hao_set_err(c, "HAO_DELIVER_ED before hao_deliver_ed_config"); return HAO_EINVAL; }
 	}
 	if ((parts & HAO_DELIVER_TRACE) && (parts & HAO_DELIVER_ED) && c->ded_place == HAO_PLACE_REF) { hao_set_err(c, "HAO_DELIVER_TRACE: the traced grid stage is not built in reference placement (hao_deliver_ed_config_ref)"); return HAO_EUNSUPP; }
 	if (parts & HAO_DELIVER_RESCUE) {
-		if (hao_is_sharded(c)) { hao_set_err(c, "HAO_DELIVER_RESCUE needs the bases of both reads: single-device mode only"); return HAO_EUNSUPP; }
+		{ HAO_STAGE_VIEW(c, V, "HAO_DELIVER_RESCUE needs the bases of both reads"); (void)V; }
 		if (!(parts & HAO_DELIVER_ED)) { hao_set_err(c, "HAO_DELIVER_RESCUE needs HAO_DELIVER_ED: it rescues the windows the ED stage left open"); return HAO_EINVAL; }
 		if (c->ded_place != HAO_PLACE_REF) { hao_set_err(c, "HAO_DELIVER_RESCUE needs reference placement (hao_deliver_ed_config_ref)"); return HAO_EINVAL; }
 	}
 	if (parts & HAO_DELIVER_WLIST) {
-		if (hao_is_sharded(c)) { hao_set_err(c, "HAO_DELIVER_WLIST needs the bases of both reads: single-device mode only"); return HAO_EUNSUPP; }
+		{ HAO_STAGE_VIEW(c, V, "HAO_DELIVER_WLIST needs the bases of both reads"); (void)V; }
 		if (!(parts & HAO_DELIVER_ED) || !(parts & HAO_DELIVER_RESCUE)) { hao_set_err(c, "HAO_DELIVER_WLIST needs HAO_DELIVER_ED | HAO_DELIVER_RESCUE: it traces the windows those stages aligned"); return HAO_EINVAL; }
 		if (c->ded_place != HAO_PLACE_REF) { hao_set_err(c, "HAO_DELIVER_WLIST needs reference placement (hao_deliver_ed_config_ref)"); return HAO_EINVAL; }
 	}

@@ -71,11 +71,11 @@ struct StageTimer {
 //   HAO_ARENA_NUMA                                          placement of the pinned delivery arenas
 //   HAO_DBG_PRINT=seed,qc,dp,sel,dl,bloom,sync              timers / counters on stderr (sync: wait after every stage and say its name - localises a device fault)
 //   HAO_DBG_FORCE=seq_chain,dp_seqtail,dp_nospec,dp_serial,seq_prune,noql      send every read / group down one of the engine's FALLBACK paths (tests: each has to give the default path's bytes)
-//   HAO_DBG_TEST=ix_pad=N,sort40_min=N,sk_gcap=N,exc_cap=N,fc_raw_every=N,exc_every=N,qmz_raw=1,arena_probe=1,ft_chunk_slots=N      capacities and thresholds shrunk so that small inputs reach the overflow / big-index code
+//   HAO_DBG_TEST=ix_pad=N,sort40_min=N,sk_gcap=N,exc_cap=N,fc_raw_every=N,exc_every=N,qmz_raw=1,arena_probe=1,ft_chunk_slots=N,gather_chunk=N      capacities and thresholds shrunk so that small inputs reach the overflow / big-index code
 struct hao_switches {
 	bool seedphase = false, qcphase = false, dp_stats = false, selphase = false, dltime = false, bloom = false;                 // HAO_DBG_PRINT
 	bool seq_chain = false, dp_seqtail = false, dp_nospec = false, dp_serial = false, seq_prune = false, seed_noql = false;     // HAO_DBG_FORCE
-	long long sk_gcap = -1, exc_cap = -1, ft_chunk_slots = 0; unsigned long long ix_pad = 0, sort40_min = 1ULL << 23; int fc_raw_every = 0, exc_every = 0; bool qmz_raw = false, arena_probe = false;      // HAO_DBG_TEST
+	long long sk_gcap = -1, exc_cap = -1, ft_chunk_slots = 0; unsigned long long gather_chunk = 64ULL << 20, ix_pad = 0, sort40_min = 1ULL << 23; int fc_raw_every = 0, exc_every = 0; bool qmz_raw = false, arena_probe = false;      // HAO_DBG_TEST
 	int arena_numa = 3, seed_merge_maxn = 24000, seed_lds_ratio = 120, ft_passes = 0, seed_lds = 1;
 	static bool in_list(const char *v, const char *name) {      // name is an element of the comma-separated list v
 		const size_t n = strlen(name);
@@ -110,6 +110,7 @@ struct hao_switches {
 			if (in_kv(v, "qmz_raw", x)) qmz_raw = x != 0;                   // the delivered minimizer tables in their 8-byte form whatever the read lengths (the form of batches with a read of 65 536 bases or more)
 			if (in_kv(v, "arena_probe", x)) arena_probe = x != 0;           // the delivery arenas' placement probe (hao_deliver_enqueue) whatever their size and rate
 			if (in_kv(v, "ft_chunk_slots", x)) ft_chunk_slots = (long long)x;      // k-mer slots hashed per chunk of reads in ha_ft_gen's pass mode
+			if (in_kv(v, "gather_chunk", x)) gather_chunk = std::max<unsigned long long>(x, 64);      // bytes a rank contributes per exchange of hao_dist_gather_reads (default 64 MB: a few KB walk the multi-chunk path on a small read set)
 		}
 		if (const char *e = getenv("HAO_SEED_LDS")) seed_lds = atoi(e) ? 1 : 0;      // 0 = the table kernels (hao_query.cuh, hao_query3.cuh) for every read instead of the list-major kernel (hao_query5.cuh): the tests run them on every scenario - they carry repeat-rich batches and the reads the list-major kernel leaves
 		if (const char *e = getenv("HAO_SEED_LDS_RATIO")) seed_lds_ratio = std::max(0, atoi(e));      // (per cent) batches with more seed hits per (query minimizer x coverage peak) than this take the table kernels: reads across repeat families (hao_batch.hpp); tests force either side
@@ -136,6 +137,10 @@ struct hao_ctx {
 	std::vector<uint32_t> h_len; std::vector<uint64_t> h_nsite_off;
 	// sharded mode: this engine holds reads [rid_base, rid_base + n_reads) of n_total; lengths of ALL reads are replicated
 	uint64_t rid_base = 0, n_total = 0; uint32_t max_len_all = 0; int n_cu = 256; DevBuf<uint32_t> d_len_all; std::vector<uint32_t> h_len_all; struct hao_comm *comm = nullptr;
+	// the gathered store (hao_dist_gather_reads, hao_gather.hpp): the bases and N sites of ALL n_total reads in global read-id order, on every rank of a sharded
+	// engine (with d_len_all it is what hao_reads_view hands the stages beyond the seam); gs_valid: it belongs to the current reads and shard layout
+	bool gs_valid = false, gs_has_n = false; uint64_t gs_pk_bytes = 0, gs_nsites = 0;
+	DevBuf<uint8_t> g_packed; DevBuf<uint64_t> g_pk_off, g_nsite_off; DevBuf<uint32_t> g_nsite;
 	// ---- filter table ----
 	bool has_ft = false; int ft_peak_hom = -1, ft_peak_het = -1, ft_cutoff = 0, ft_passes_used = 1; int64_t ft_hist[HAO_N_COUNTS];
 	std::vector<uint64_t> h_ft_keys; std::vector<int32_t> h_ft_vals;
@@ -215,6 +220,29 @@ static void hao_set_err(hao_ctx *c, const std::string &m) { if (c) c->err = m; }
 static bool hao_comm_is_active(const struct hao_comm *cm);
 static inline bool hao_is_sharded(const hao_ctx *c) { const hao_ctx *o = c->owner ? c->owner : c; return o->comm && hao_comm_is_active(o->comm); }
 
+// The reads as the stages beyond the seam see them (hao_exact_check, the window alignments, hao_reads_digest): ONE store whose entries are named by the ids the
+// tasks, ol->list and the batch's queries carry.  An unsharded engine: its local store (id_base = rid_base, the id of entry 0, which only the exact check
+// subtracts; local0 = 0).  A sharded engine with a gathered store: that store and the replicated lengths, entries = global ids (id_base = 0; local0 = rid_base,
+// the entry of the engine's local read 0).  A sharded engine without one has no view: the stages refuse.  h_len: the host's copy of len.
+struct hao_read_view {
+	const uint8_t *packed; const uint64_t *pk_off; const uint32_t *len; const uint64_t *nsite_off; const uint32_t *nsite;      // nsite_off == nullptr: no read has N
+	const uint32_t *h_len; uint64_t n, id_base, local0;
+};
+static inline bool hao_reads_view(const hao_ctx *c, hao_read_view *V)
+{
+	if (!hao_is_sharded(c)) {
+		V->packed = c->d_packed.p; V->pk_off = c->d_pk_off.p; V->len = c->d_len.p; V->nsite_off = c->has_n ? c->d_nsite_off.p : nullptr; V->nsite = c->has_n ? c->d_nsite.p : nullptr;
+		V->h_len = c->h_len.data(); V->n = c->n_reads; V->id_base = c->rid_base; V->local0 = 0;
+		return true;
+	}
+	if (!c->gs_valid) return false;
+	V->packed = c->g_packed.p; V->pk_off = c->g_pk_off.p; V->len = c->d_len_all.p; V->nsite_off = c->gs_has_n ? c->g_nsite_off.p : nullptr; V->nsite = c->gs_has_n ? c->g_nsite.p : nullptr;
+	V->h_len = c->h_len_all.data(); V->n = c->n_total; V->id_base = 0; V->local0 = c->rid_base;
+	return true;
+}
+// a stage's first step: its view, or today's refusal (`what`: the entry point and what it needs, as the message has always said)
+#define HAO_STAGE_VIEW(c, V, what) hao_read_view V; do { if (!hao_reads_view((c), &V)) { hao_set_err((c), what ": single-device mode only"); return HAO_EUNSUPP; } } while (0)
+
 // scratch for rocprim calls
 static inline hipError_t hao_tmp(hao_ctx *c, size_t bytes) { return c->d_tmp.reserve(bytes + 256); }
 
@@ -240,6 +268,8 @@ static int hao_view_refresh(hao_ctx *c)
 	c->has_pt = o->has_pt; c->ix_n_mz = o->ix_n_mz; c->ix_n_sorted = o->ix_n_sorted; c->ix_n_keys = o->ix_n_keys; c->ix_n_pos = o->ix_n_pos; c->ix_pad = o->ix_pad; c->ix_bucket_bits = o->ix_bucket_bits; c->lk_valid = o->lk_valid;
 	c->h_len = o->h_len; c->h_nsite_off = o->h_nsite_off; c->h_len_all = o->h_len_all; c->h_ix_mz_off = o->h_ix_mz_off;      // (empty: copied from the device on first use)
 	c->d_packed.borrow(o->d_packed); c->d_pk_off.borrow(o->d_pk_off); c->d_len.borrow(o->d_len); c->d_len_all.borrow(o->d_len_all); c->d_nsite_off.borrow(o->d_nsite_off); c->d_nsite.borrow(o->d_nsite);
+	c->gs_valid = o->gs_valid; c->gs_has_n = o->gs_has_n; c->gs_pk_bytes = o->gs_pk_bytes; c->gs_nsites = o->gs_nsites;
+	c->g_packed.borrow(o->g_packed); c->g_pk_off.borrow(o->g_pk_off); c->g_nsite_off.borrow(o->g_nsite_off); c->g_nsite.borrow(o->g_nsite);
 	c->d_ix_mz_x.borrow(o->d_ix_mz_x); c->d_ix_mz_info.borrow(o->d_ix_mz_info); c->d_ix_mz_off.borrow(o->d_ix_mz_off); c->d_ix_sinfo.borrow(o->d_ix_sinfo); c->d_ix_lk.borrow(o->d_ix_lk);
 	c->d_ix_keys.borrow(o->d_ix_keys); c->d_ix_start.borrow(o->d_ix_start); c->d_ix_cnt.borrow(o->d_ix_cnt); c->d_ix_bucket.borrow(o->d_ix_bucket);
 	c->attached_gen = o->index_gen;

@@ -26,9 +26,11 @@ static int hao_al_upload_sorted(hao_ctx *c, const hao_ed_task_t *tasks, uint64_t
 	HIP_TRY(rocprim::radix_sort_pairs(c->d_tmp.p, tb, c->al_k1.p, c->al_k2.p, c->al_i1.p, c->al_order.p, n, 0, 64, c->stream));
 	return HAO_OK;
 }
+// the reads of a launch: the context's view (hao_ctx.hpp: hao_reads_view; the entry points refuse before they get here when there is none)
 static hao_ed_reads hao_al_reads_of(hao_ctx *c)
 {
-	hao_ed_reads R; R.packed = c->d_packed.p; R.pk_off = c->d_pk_off.p; R.len = c->d_len.p; R.nsite_off = c->has_n ? c->d_nsite_off.p : nullptr; R.nsite = c->has_n ? c->d_nsite.p : nullptr;
+	hao_read_view V; (void)hao_reads_view(c, &V);
+	hao_ed_reads R; R.packed = V.packed; R.pk_off = V.pk_off; R.len = V.len; R.nsite_off = V.nsite_off; R.nsite = V.nsite;
 	return R;
 }
 
@@ -112,7 +114,7 @@ int hao_al_trace_grid(hao_ctx *c, const hao_ovlp_t *ol, const hao_ed_pair *pairs
 	const uint32_t nword = hao_al_nword(thre), cap = 2 * thre + 3;
 	HIP_TRY(G.want.reserve(n + 1)); HIP_TRY(G.sel.reserve(n + 1)); HIP_TRY(G.ctr.reserve(2)); HIP_TRY(c->d_cursor.reserve(2));
 	HIP_TRY(hipMemsetAsync(ps16, 0xff, n * 2, c->stream)); HIP_TRY(hipMemsetAsync(ncig16, 0, n * 2, c->stream)); HIP_TRY(hipMemsetAsync(G.ctr.p, 0, 16, c->stream));
-	hipLaunchKernelGGL(hao_tg_flag_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, c->d_len.p, ol, pairs, n, wl, thre, err, G.want.p, G.ctr.p); HAO_CHECK_LAUNCH();
+	hipLaunchKernelGGL(hao_tg_flag_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, R.len, ol, pairs, n, wl, thre, err, G.want.p, G.ctr.p); HAO_CHECK_LAUNCH();
 	size_t tb = 0;
 	const auto idx = rocprim::make_counting_iterator<uint32_t>(0);
 	HIP_TRY(rocprim::select(nullptr, tb, idx, G.want.p, G.sel.p, (uint64_t*)c->d_cursor.p, n, c->stream)); HIP_TRY(hao_tmp(c, tb));
@@ -163,7 +165,7 @@ int hao_al_trace_grid_off(hao_ctx *c, const uint64_t *at, uint64_t n, uint64_t n
 int hao_al_trace_grid_expand(hao_ctx *c, const hao_ovlp_t *ol, uint64_t n, hao_ed_task_t *tasks, hao_trace_result_t *res)
 {
 	if (n == 0) return HAO_OK;
-	hipLaunchKernelGGL(hao_tg_expand_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, c->d_len.p, ol, c->tg_pairs.p, n, c->tg_wl, c->tg_thre,
+	hipLaunchKernelGGL(hao_tg_expand_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, hao_al_reads_of(c).len, ol, c->tg_pairs.p, n, c->tg_wl, c->tg_thre,
 		c->tg_err.p, c->tg_pe.p, c->tg_ps.p, c->tg_ncig16.p, tasks, res); HAO_CHECK_LAUNCH();
 	return HAO_OK;
 }
@@ -186,7 +188,7 @@ int hao_al_rescue(hao_ctx *c, const hao_ovlp_t *ol, uint64_t n_ol, uint32_t wl, 
 	const dim3 b_(256), go((unsigned)((n_ol + 255) / 256));
 	if (n_pairs && res) { hipLaunchKernelGGL(hao_rs_scatter_pe_kernel, dim3((unsigned)((n_pairs + 255) / 256)), b_, 0, c->stream, ol, pairs, res, n_pairs, wl, RA.win_off, G.wpe.p); HAO_CHECK_LAUNCH(); }
 	else if (n_pairs) { hipLaunchKernelGGL(hao_rs_scatter_pe16_kernel, dim3((unsigned)((n_pairs + 255) / 256)), b_, 0, c->stream, ol, pairs, err8, pe16, n_pairs, wl, RA.win_off, G.wpe.p); HAO_CHECK_LAUNCH(); }
-	hao_rs_args A; A.ol = ol; A.n_ol = n_ol; A.wl = wl; A.win_off = RA.win_off; A.shift = RA.shift; A.tab = RA.tab; A.werr = werr; A.wpe = G.wpe.p; A.len = c->d_len.p;
+	hao_rs_args A; A.ol = ol; A.n_ol = n_ol; A.wl = wl; A.win_off = RA.win_off; A.shift = RA.shift; A.tab = RA.tab; A.werr = werr; A.wpe = G.wpe.p; A.len = hao_al_reads_of(c).len;
 	hipLaunchKernelGGL((hao_rs_gap_kernel<false>), go, b_, 0, c->stream, A, G.ctr.p, (uint64_t*)nullptr, (hao_rs_state*)nullptr, (hao_rs_win*)nullptr); HAO_CHECK_LAUNCH();
 	hipLaunchKernelGGL(hao_peek_kernel, dim3(1), dim3(64), 0, c->stream, (const unsigned long long*)G.ctr.p, 2, c->peek_d + 40); HAO_CHECK_LAUNCH();
 	HIP_TRY(hipStreamSynchronize(c->stream));
@@ -246,11 +248,12 @@ int hao_al_wlist(hao_ctx *c, const hao_ovlp_t *ol, uint64_t n_ol, uint32_t wl, h
 	HIP_TRY(o_cigoff.reserve(n_slots + 2)); HIP_TRY(G.key.reserve(n_slots + 1)); HIP_TRY(G.key2.reserve(n_slots + 1)); HIP_TRY(G.idx.reserve(n_slots + 1)); HIP_TRY(G.sel.reserve(n_slots + 1));
 	HIP_TRY(G.rowof.reserve(n_slots + 1)); HIP_TRY(G.ctr.reserve(8));
 	HIP_TRY(hipMemsetAsync(G.ctr.p, 0, 64, c->stream));
-	hao_wl_args W; W.A.ol = ol; W.A.n_ol = n_ol; W.A.wl = wl; W.A.win_off = RA.win_off; W.A.shift = RA.shift; W.A.tab = RA.tab; W.A.werr = werr; W.A.wpe = c->rs.wpe.p; W.A.len = c->d_len.p;
+	hao_wl_args W; W.A.ol = ol; W.A.n_ol = n_ol; W.A.wl = wl; W.A.win_off = RA.win_off; W.A.shift = RA.shift; W.A.tab = RA.tab; W.A.werr = werr; W.A.wpe = c->rs.wpe.p; W.A.len = hao_al_reads_of(c).len;
 	W.rbase = c->rs.rbase.p; W.rec = c->rs.rec.p; W.ov = ov;
 	// sort key of a record that needs a sweep: query read << wbits | grid window (a read has fewer than 2^32 / wl windows)
 	uint32_t wbits = 32; while (wbits > 1 && (wl >> (32 - wbits + 1))) --wbits;
-	uint32_t rbits = 1; while (rbits < 32 && (c->n_reads >> rbits)) ++rbits;
+	hao_read_view V; (void)hao_reads_view(c, &V);
+	uint32_t rbits = 1; while (rbits < 32 && (V.n >> rbits)) ++rbits;      // (x_id names a read of the view)
 	const dim3 b_(256), go((unsigned)((n_ol + 255) / 256));
 	hipLaunchKernelGGL(hao_wl_count_kernel, dim3((unsigned)((n_ol + 256) / 256)), b_, 0, c->stream, W, G.cnt.p); HAO_CHECK_LAUNCH();
 	if (int rc = hao_excl_scan_u64(c, G.cnt.p, o_woff.p, n_ol + 1)) return rc;
@@ -300,7 +303,7 @@ int hao_window_ed_batch(hao_ctx *c, const hao_ed_task_t *tasks, uint64_t n_tasks
 {
 	if (!c || (!tasks && n_tasks) || (!out && n_tasks)) return HAO_EINVAL;
 	if (int rc = hao_view_refresh(c)) return rc;
-	if (hao_is_sharded(c)) { hao_set_err(c, "hao_window_ed_batch needs the bases of both reads: single-device mode only"); return HAO_EUNSUPP; }
+	HAO_STAGE_VIEW(c, V, "hao_window_ed_batch needs the bases of both reads");
 	c->al_grid_n = 0;      // (the task / result scratch is shared with hao_window_ed_grid: what that call left is gone)
 	c->tg_valid = false;      // (and hao_window_trace_grid's results follow the same rule)
 	if (n_tasks == 0) return HAO_OK;
@@ -308,7 +311,7 @@ int hao_window_ed_batch(hao_ctx *c, const hao_ed_task_t *tasks, uint64_t n_tasks
 	uint32_t words = 0;      // bit (nword - 1): some band needs nword 64-bit words (the reference's cal_exz_infi picks nword = ceil((2 thre + 1) / 64), Correct.cpp:14508-14565)
 	for (uint64_t i = 0; i < n_tasks; ++i) {      // the reference indexes its strings unchecked; a device kernel must not
 		const hao_ed_task_t &t = tasks[i];
-		if (t.p_rid >= c->n_reads || t.t_rid >= c->n_reads || (uint64_t)t.p_pos + t.p_len > c->h_len[t.p_rid] || (uint64_t)t.t_pos + t.t_len > c->h_len[t.t_rid] ||
+		if (t.p_rid >= V.n || t.t_rid >= V.n || (uint64_t)t.p_pos + t.p_len > V.h_len[t.p_rid] || (uint64_t)t.t_pos + t.t_len > V.h_len[t.t_rid] ||
 			t.thre > HAO_ED_MAX_THRE || t.abs_diag > 2 * t.thre) { hao_set_err(c, "hao_window_ed_batch: task " + std::to_string(i) + " out of range"); return HAO_EINVAL; }
 		const uint32_t nw = hao_al_nword(t.thre);
 		if (nw > 1 && (int64_t)t.p_len - (int64_t)t.t_len + (int64_t)t.abs_diag > 64 * (int64_t)nw) {      // the final scan would read VP / VN bits beyond the band's words (the reference then indexes the neighbouring vectors of its bit_extz_t)
@@ -334,14 +337,14 @@ int hao_window_trace_batch(hao_ctx *c, int mode, const hao_ed_task_t *tasks, uin
 {
 	if (!c || (mode < HAO_ALIGN_GLOBAL || mode > HAO_ALIGN_SEMI) || (!tasks && n_tasks) || (!out && n_tasks) || (!cigars && n_tasks && cigar_cap)) return HAO_EINVAL;
 	if (int rc = hao_view_refresh(c)) return rc;
-	if (hao_is_sharded(c)) { hao_set_err(c, "hao_window_trace_batch needs the bases of both reads: single-device mode only"); return HAO_EUNSUPP; }
+	HAO_STAGE_VIEW(c, V, "hao_window_trace_batch needs the bases of both reads");
 	c->al_grid_n = 0; c->tg_valid = false;
 	if (n_tasks == 0) return HAO_OK;
 	if (n_tasks >= (1ULL << 32)) { hao_set_err(c, "hao_window_trace_batch: more than 2^32 tasks in one call"); return HAO_EUNSUPP; }
 	uint64_t tn_max = 1; uint32_t words = 0;      // bit (nword - 1): some band needs nword 64-bit words
 	for (uint64_t i = 0; i < n_tasks; ++i) {      // the reference indexes its strings unchecked; a device kernel must not
 		const hao_ed_task_t &t = tasks[i];
-		if (t.p_rid >= c->n_reads || t.t_rid >= c->n_reads || (uint64_t)t.p_pos + t.p_len > c->h_len[t.p_rid] || (uint64_t)t.t_pos + t.t_len > c->h_len[t.t_rid] ||
+		if (t.p_rid >= V.n || t.t_rid >= V.n || (uint64_t)t.p_pos + t.p_len > V.h_len[t.p_rid] || (uint64_t)t.t_pos + t.t_len > V.h_len[t.t_rid] ||
 			t.thre > HAO_ED_MAX_THRE) { hao_set_err(c, "hao_window_trace_batch: task " + std::to_string(i) + " out of range"); return HAO_EINVAL; }
 		words |= 1u << (hao_al_nword(t.thre) - 1);
 		if (mode == HAO_ALIGN_SEMI) {

@@ -14,11 +14,14 @@ Per-unit figures (bytes) and where they come from:
   index            8 / minimizer of ALL reads + 20 / kept key (key, start, count) + 2^26 x 4  hao_pt_run: the all-gather's slots ARE the replicated index
   pass, per batch  130 / seed hit with both delivery sets (k_mer_hit 16, sorted copy 16,     bench.py's batch sizing (measured: 6 batches of 1.07e9 hits of configs[2] = 180 GB with the index)
                    group tables, chain records, fake cigars, codes, two output sets)
+  gathered reads   0.25 / base + 9 / read of ALL reads (packed bytes, pack offsets), resident     hao_dist_gather_reads (hao_gather.hpp); optional (gathered_reads=True): only
+                   from the gather on; + world x 64 MB of staging while it runs                  the stages beyond the seam need it in a sharded engine
 Minimizer and seed-hit densities are the REFERENCE's on the full-size fixtures (tests/golden/*.npz: sum of count x histogram of ha_pt_gen; seed hits per read)."""
 from __future__ import annotations
 
 HBM_BYTES = 288e9
 FT_PER_SLOT, FT_PER_SLOT_SHARDED, FT_RUN_PER_SLOT, FT_CHUNK_SLOTS, FT_PER_SLOT_BLOOM = 20.0, 46.0, 3.0, 1 << 28, 10.0
+GATHER_CHUNK = 64 << 20      # bytes a rank sends per exchange of hao_dist_gather_reads (hao_ctx.hpp: hao_switches::gather_chunk)
 
 
 def ft_passes(slots: float, free_bytes: float, sharded: bool, bloom: bool = False) -> int:
@@ -34,8 +37,10 @@ def ft_passes(slots: float, free_bytes: float, sharded: bool, bloom: bool = Fals
 
 
 def rank_plan(total_bases: float, n_reads: float, world: int, mz_per_base: float, hits_per_read: float, genome: float, err: float = 0.001, k: int = 51,
-              batch_hits: float = 1.07e9, kept_key_frac: float = 0.6, bloom: bool = False) -> dict:
-    """bytes resident on one of `world` ranks in each phase; every phase includes what stays from the earlier ones"""
+              batch_hits: float = 1.07e9, kept_key_frac: float = 0.6, bloom: bool = False, gathered_reads: bool = False) -> dict:
+    """bytes resident on one of `world` ranks in each phase; every phase includes what stays from the earlier ones.  gathered_reads: the plan of a sharded run that
+    calls hao_dist_gather_reads before its all-reads pass (off by default: the plan without it does not move) - the store joins that pass, and "gather" is the
+    moment it is built (index resident, staging buffer alive)"""
     b_loc, r_loc = total_bases / world, n_reads / world
     reads = 0.25 * b_loc + r_loc + 4 * n_reads
     # distinct k-mers: the genome's (both strands are one canonical k-mer) + those an error makes (a k-mer is error-free with probability (1 - err)^k); a rank counts
@@ -55,5 +60,11 @@ def rank_plan(total_bases: float, n_reads: float, world: int, mz_per_base: float
     hits_pass = hits_per_read * r_loc
     batch = min(batch_hits, hits_pass)
     query = reads + 24 * m_loc + index + 130 * batch
+    if gathered_reads and world > 1:
+        store = 0.25 * total_bases + 9 * n_reads
+        gather = reads + 24 * m_loc + index + store + world * GATHER_CHUNK
+        query += store
+        return {"passes_ft": p, "reads": reads, "ft_gen": ft, "pt_gen": pt, "all_reads_pass": query, "index": index, "seed_hits_per_pass": hits_pass,
+                "batches_per_pass": max(1, round(hits_pass / batch)), "gathered_reads": store, "gather": gather, "peak": max(ft, pt, gather, query), "hbm": HBM_BYTES}
     return {"passes_ft": p, "reads": reads, "ft_gen": ft, "pt_gen": pt, "all_reads_pass": query, "index": index, "seed_hits_per_pass": hits_pass,
             "batches_per_pass": max(1, round(hits_pass / batch)), "peak": max(ft, pt, query), "hbm": HBM_BYTES}

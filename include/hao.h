@@ -97,6 +97,31 @@ int hao_dist_init(hao_ctx *c, const uint8_t id[128], int rank, int world);
 void *hao_loop_create(int world);
 void hao_loop_destroy(void *grp);
 int hao_dist_init_loopback(hao_ctx *c, void *grp, int rank);
+/* The stages beyond the seam - hao_exact_check / HAO_DELIVER_EXACT, hao_window_ed_batch, hao_window_trace_batch, hao_window_ed_grid, hao_window_trace_grid,
+ * hao_window_ed_ref, hao_window_rescue_ref, hao_window_wlist_ref and HAO_DELIVER_ED / TRACE / RESCUE / WLIST - read the bases of BOTH reads of an overlap, and a
+ * sharded engine holds the bases of its own slice only: they return HAO_EUNSUPP there ("single-device mode only"), as their comments below say - until
+ * hao_dist_gather_reads has run.  A collective over the engine's transport (every rank calls it; after hao_set_reads, hao_set_shard and the dist init, in any
+ * order relative to hao_ft_gen / hao_pt_gen): it replicates the read store as hao_pt_gen replicates the index - every rank's packed bytes, pack offsets, N-site
+ * offsets and N sites all-gathered in chunks of bounded size into one GATHERED STORE in global read-id order (packed bytes of all n_total reads + 8 bytes per read,
+ * + 8 bytes per read and 4 per site when a read has N), pack and N-site offsets turned from local to global on the device.  From then on every stage named above
+ * runs in the sharded engine, blocking and streamed, over that store: tasks, x_id and y_id name reads by GLOBAL id there (hao_window_ed_batch /
+ * hao_window_trace_batch take tasks between any two of the n_total reads), batch ranges and the hao_fetch_* read argument stay LOCAL, and the results are bit for
+ * bit the unsharded engine's.  The hao_unpack_* helpers index one `len` array by a delivery's rid_lo-based read ids and by y_id: for a sharded engine's
+ * delivery pass a copy of the view with rid_lo += rid_base, the lengths of all reads and global read ids.
+ *   Calling it again while the store is valid is a no-op (no communication); hao_set_reads and hao_set_shard discard the store (the refusals are back until the
+ *   next gather); an attached context (hao_attach) borrows it.  The ranks fail together (a rank whose allocation failed takes part in the status exchange and
+ *   all return an error).  Shards that are not contiguous slices in rank order: HAO_EINVAL on every rank.  On an unsharded engine: HAO_OK, nothing is allocated -
+ *   the local store is the whole store.  hao_index_save / hao_index_load stay single-device.
+ *   HAO_DBG_TEST=gather_chunk=N: bytes a rank sends per exchange (default 64 MB; a few KB walk the multi-chunk path on a small read set). */
+int hao_dist_gather_reads(hao_ctx *c);
+/* Digest of the reads as the stages above see them - the local store of an unsharded engine, the gathered store of a sharded one (HAO_EUNSUPP without it) -
+ * computed on the device (one wave per read).  With term() as for hao_batch_digest below, for read r (its id in that store) of L bases and m N sites:
+ *   bases(r) = term(5, 0, L) + sum of term(5, j + 1, w_j) over the little-endian 64-bit words w_j of the read's L / 4 + 1 packed bytes, zero-padded to a word
+ *   sites(r) = term(6, 0, m) + sum of term(6, k + 1, site_k) over the read's N sites
+ *   out[0] = sum over r of term(7, r, bases(r)),  out[1] = sum over r of term(8, r, sites(r))      (mod 2^64)
+ * Pack offsets are not part of it: any layout of the same reads gives the same value, so every rank of a sharded engine must report what an unsharded engine
+ * over the same reads reports. */
+int hao_reads_digest(hao_ctx *c, uint64_t out[2]);
 
 /* ha_ft_gen (htab.cpp:1136-1169), exact (-f0) or through the reference's blocked Bloom filter (opt.bf_shift > 12, bit-exact incl. its false
  * positives: see hao_tables.hpp), + ha_opt_update_cov (CommandLines.cpp:411-418). */
