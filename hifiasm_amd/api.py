@@ -20,6 +20,9 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = None
 
 
+SORTDBG_SEQ, SORTDBG_WAVE_LDS, SORTDBG_WAVE_GLOBAL, SORTDBG_BLOCK, SORTDBG_SELECT = range(5)      # hao_dbg_sort_perm's paths (include/hao.h)
+
+
 class HaoError(RuntimeError):
     pass
 
@@ -253,6 +256,7 @@ def lib():
         L.hao_dist_init_loopback.argtypes = [vp, vp, C.c_int]
         L.hao_dist_gather_reads.argtypes = [vp]
         L.hao_reads_digest.argtypes = [vp, u64p]
+        L.hao_dbg_sort_perm.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_uint64, u64p, u64p, C.POINTER(C.c_int32), u32p]
         _LIB = L
     return _LIB
 
@@ -363,6 +367,17 @@ class Engine:
         out = (C.c_uint64 * 2)()
         self._ck(self.L.hao_reads_digest(self.h, out), "hao_reads_digest")
         return int(out[0]), int(out[1])
+
+    def dbg_sort_perm(self, mode, path, arrays, variant=0, off=None):
+        """hao_dbg_sort_perm: one of the selection's sorts alone (path: SORTDBG_*) on key arrays [(xs, sc)]; mode 0 sorts by sc descending, mode 1 by xs ascending.
+        Returns one permutation per array (index within the array of the key at every slot).  off: offsets to pass instead of the arrays' own (tests of the refusals)."""
+        xs = np.ascontiguousarray(np.concatenate([np.asarray(a[0], dtype=np.uint64) for a in arrays] + [np.zeros(1, np.uint64)]))
+        sc = np.ascontiguousarray(np.concatenate([np.asarray(a[1], dtype=np.int32) for a in arrays] + [np.zeros(1, np.int32)]))
+        own = np.concatenate([[0], np.cumsum([len(a[0]) for a in arrays])]).astype(np.uint64)
+        o = own if off is None else np.ascontiguousarray(off, dtype=np.uint64)
+        perm = np.full(int(own[-1]) + 1, 0xffffffff, dtype=np.uint32)
+        self._ck(self.L.hao_dbg_sort_perm(self.h, mode, path, variant, len(o) - 1, *[a.ctypes.data_as(C.POINTER(t)) for a, t in ((o, C.c_uint64), (xs, C.c_uint64), (sc, C.c_int32), (perm, C.c_uint32))]), "hao_dbg_sort_perm")
+        return [perm[int(own[i]):int(own[i + 1])].astype(np.int64) for i in range(len(arrays))]
 
     def delivery_global(self, d):
         """a copy of a sharded engine's Delivery with rid_lo as a GLOBAL read id: what the delivered_* / hao_unpack_* helpers take together with the lengths

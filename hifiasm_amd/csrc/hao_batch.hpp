@@ -635,7 +635,7 @@ static int hao_overlap_run(hao_ctx *c, uint64_t lo, uint64_t hi, const hao_pass_
 	}
 	HIP_TRY(B.q_pos.reserve(nm + 1)); HIP_TRY(B.q_cnt.reserve(nm + 1));
 	HIP_TRY(B.s_start.reserve(nm + 1)); HIP_TRY(B.s_pk.reserve(nm + 1)); HIP_TRY(B.s_n.reserve(nm + 1)); HIP_TRY(B.a_off.reserve(nm + 2)); HIP_TRY(B.seg.reserve(n + 2));
-	HIP_TRY(c->d_err.reserve(2)); HIP_TRY(hipMemsetAsync(c->d_err.p, 0, 4, c->stream));
+	HIP_TRY(c->d_err.reserve(2)); HIP_TRY(hipMemsetAsync(c->d_err.p, 0, 8, c->stream));
 	// Q1: every minimizer's lookup result was computed when the index was built (hao_index_finish_kernel; in sharded mode by the owner of its hash, hao_tables.hpp)
 	if (!c->lk_valid) { hao_set_err(c, "index without per-minimizer lookup results"); return HAO_EINVAL; }
 	hipLaunchKernelGGL(seed_unpack_kernel, dim3((unsigned)((nm + 256) / 256)), dim3(256), 0, c->stream, c->d_ix_lk.p, c->d_ix_mz_info.p, B.mz0, nm, B.wgt.p, B.s_start.p, B.s_n.p, B.q_pos.p, B.q_cnt.p, B.s_pk.p);
@@ -909,24 +909,8 @@ static int hao_overlap_run(hao_ctx *c, uint64_t lo, uint64_t hi, const hao_pass_
 	sa.perm = B.perm.p; sa.n_final = B.n_final.p; sa.fc_final = B.fc_final.p; sa.max_n_chain = par.max_n_chain; sa.ocv_w = par.ocv_w; sa.chain_cutoff = par.chain_cutoff;
 	sa.dbg = nullptr; sa.dbg_seq_prune = c->sw.seq_prune ? 1 : 0;
 	if (c->sw.selphase) { HIP_TRY(B.dbgbuf.reserve(8)); HIP_TRY(hipMemsetAsync(B.dbgbuf.p, 0, 64, c->stream)); sa.dbg = B.dbgbuf.p; }
-	// three launches split by chain count: the common reads (<= 128 chains) need 5 KB of LDS per wave and fill the CUs; 512- and 1024-chain slices for
-	// repeat-rich reads (beyond 1024 chains the keys stay in global scratch)
-	hipLaunchKernelGGL((chain_select_kernel<1, 128>), dim3((unsigned)(n + 1)), dim3(64), 0, c->stream, sa, (int64_t)0, (int64_t)129);
-	HAO_CHECK_LAUNCH();
-	{	// 129 .. 4096 chains: four waves per read share the sorts; beyond: keys in global scratch, one wave
-		hipLaunchKernelGGL((chain_select4_kernel<512>), dim3((unsigned)n), dim3(256), 0, c->stream, sa, (int64_t)129, (int64_t)513);
-		HAO_CHECK_LAUNCH();
-		hipLaunchKernelGGL((chain_select4_kernel<1024>), dim3((unsigned)n), dim3(256), 0, c->stream, sa, (int64_t)513, (int64_t)1025);
-		HAO_CHECK_LAUNCH();
-		// reads that cross repeat families: thousands of chains (250 Mb repeat-rich set: a quarter of the reads have more than 1024).  With the keys in global scratch
-		// and one wave per read those took 17 ms per batch; 64 / 128 KB of LDS per read keeps them on the four-wave path
-		hipLaunchKernelGGL((chain_select4_kernel<2048>), dim3((unsigned)n), dim3(256), 0, c->stream, sa, (int64_t)1025, (int64_t)2049);
-		HAO_CHECK_LAUNCH();
-		hipLaunchKernelGGL((chain_select4_kernel<4096>), dim3((unsigned)n), dim3(256), 0, c->stream, sa, (int64_t)2049, (int64_t)4097);
-		HAO_CHECK_LAUNCH();
-		hipLaunchKernelGGL((chain_select_kernel<1, 1024>), dim3((unsigned)(n + 1)), dim3(64), 0, c->stream, sa, (int64_t)4097, (int64_t)INT64_MAX);
-	}
-	HAO_CHECK_LAUNCH();
+	sa.err = c->d_err.p + 1;      // (word 0: hao_qtab16_kernel's, possibly on the side stream)
+	HIP_TRY(hao_select_launch(sa, n, c->stream));      // one launch per tier of chain counts (hao_chain.cuh)
 	if (int rc = hao_scan_u32(c, B.n_final.p, B.O().fin_off.p, n + 1)) return rc;
 	if (int rc = hao_excl_scan_u64(c, B.fc_final.p, B.fcf_off.p, n + 1)) return rc;
 	if (sa.dbg) { unsigned long long d_[5]; HIP_TRY(hipMemcpy(d_, B.dbgbuf.p, 40, hipMemcpyDeviceToHost)); if (d_[4]) fprintf(stderr, "[select] reads %llu  avg us: score sort %.1f  prune %.1f  position sort %.1f  weak filter %.1f\n", d_[4], d_[0] / 100.0 / d_[4], d_[1] / 100.0 / d_[4], d_[2] / 100.0 / d_[4], d_[3] / 100.0 / d_[4]); }
@@ -956,6 +940,7 @@ static int hao_overlap_run(hao_ctx *c, uint64_t lo, uint64_t hi, const hao_pass_
 		B.seed_left[0] = c->peek_h[26]; B.seed_left[1] = c->peek_h[24]; B.seed_left[2] = c->peek_h[25];      // reads left by the first seed launch / by the 512-slot / by the 1024-slot table
 		if (parts & HAO_DELIVER_CL) { n_exc = c->peek_h[5]; B.n_codes = G ? c->peek_h[6] : 0; }
 		if ((parts & HAO_DELIVER_CL) && (uint32_t)c->peek_h[27]) { hao_set_err(c, "a minimizer position or seed weight that does not fit the packed minimizer table"); return HAO_EUNSUPP; }      // (hao_qtab16_kernel; the host's bounds rule it out)
+		if (c->peek_h[27] >> 32) { hao_set_err(c, "selection sort: more sub-ranges alive in one level than its list holds"); return HAO_EUNSUPP; }      // (hao_block_intro_sort's bound, hao_chain.cuh)
 		if ((parts & HAO_DELIVER_OL) && (c->peek_h[7] >> 63)) { hao_set_err(c, "an overlap without fake-cigar entries: the packed cigar layout holds at least one per overlap"); return HAO_EUNSUPP; }
 		B.n_fcw = (parts & HAO_DELIVER_OL) ? (B.n_fc - B.n_ol) + c->peek_h[7] : 0;      // main region + the raw overlaps' words
 	}

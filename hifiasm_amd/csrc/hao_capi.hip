@@ -218,3 +218,4 @@ int hao_stage_times(hao_ctx *c, const char **names, float *ms, int cap)
 } // extern "C"
 
 #include "hao_capi_rest.hpp"
+#include "hao_sortdbg.hpp"

@@ -1273,18 +1273,22 @@ template<int MODE> __device__ void hao_wave_intro_sort(const hao_sel_ctx &S, int
 // in which they are visited, and the depth budget d travels with each sub-range), so the phase runs level by level: every wave partitions
 // the sub-ranges of the current level assigned to it (stop lists of sub-range [s, t] live at lpos/rasc[s ..]) and appends the children
 // that klib would still partition (> 16 elements) to the next level's list.  The stable finish is data-parallel over all threads.
-#define HAO_BSORT_MAXSEG 64       // > CAP / 18 sub-ranges can never be alive in one level (CAP <= 1024)
-template<int MODE, int NW> __device__ void hao_block_intro_sort(const hao_sel_ctx &S, int64_t n, int32_t *segs /*[2][3 * MAXSEG]*/, uint32_t *segn /*[2]*/, int *flag)
+// Capacity of a level's list: the live sub-ranges of one level are disjoint, each holds at least 17 elements (klib leaves shorter ones to the closing insertion
+// sort) and at least one pivot lies between two neighbours, so k of them need 17 k + (k - 1) <= n: k <= (n + 1) / 18 - 227 at 4096 keys, 28 at 512.  (All-equal keys
+// halve exactly and come close: 128 sub-ranges of 17 at 2304 keys.)  The append is checked all the same: a list that would overflow fails the call (*err) instead
+// of writing past its end.
+#define HAO_BSORT_MAXSEG(CAP) (((CAP) + 1) / 18 + 1)
+template<int MODE, int NW> __device__ void hao_block_intro_sort(const hao_sel_ctx &S, int64_t n, int32_t *segs /*[2][3 * maxseg]*/, const uint32_t maxseg, uint32_t *segn /*[2]*/, int *flag, int *err)
 {
 	const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, NT = NW * 64;
-	if (n < 1) return;
+	if (n < 2) return;      // (klib: nothing to partition; a root range of one element has no median of three)
 	if (n == 2) { if (tid == 0 && hao_lt<MODE>(S, 1, 0)) hao_sw(S, 0, 1); __syncthreads(); return; }
 	if (tid == 0) { int d0; for (d0 = 2; (1ull << d0) < (uint64_t)n; ++d0) {} segs[0] = 0; segs[1] = (int32_t)(n - 1); segs[2] = d0 << 1; segn[0] = 1; segn[1] = 0; }
 	__syncthreads();
 	for (int ci = 0; ; ci ^= 1) {
-		const uint32_t nseg = segn[ci];
+		const uint32_t nseg = segn[ci] < maxseg ? segn[ci] : maxseg;      // (beyond maxseg: the appends were refused and the call fails)
 		if (nseg == 0) break;
-		const int32_t *cur = segs + ci * 3 * HAO_BSORT_MAXSEG; int32_t *nxt = segs + (ci ^ 1) * 3 * HAO_BSORT_MAXSEG;
+		const int32_t *cur = segs + ci * 3 * maxseg; int32_t *nxt = segs + (ci ^ 1) * 3 * maxseg;
 		for (uint32_t e = wv; e < nseg; e += NW) {
 			const int64_t s = cur[3 * e], t = cur[3 * e + 1]; int d = cur[3 * e + 2];
 			int64_t i, j, k;
@@ -1318,8 +1322,8 @@ template<int MODE, int NW> __device__ void hao_block_intro_sort(const hao_sel_ct
 			i = K == 0 ? lpos[0] : (lpos[K] < rasc[nR - K] ? lpos[K] : rasc[nR - K]);
 			if (lane == 0) {
 				hao_sw(S, i, t);
-				if (i - s > 16) { const uint32_t q = atomicAdd(&segn[ci ^ 1], 1u); nxt[3 * q] = (int32_t)s; nxt[3 * q + 1] = (int32_t)(i - 1); nxt[3 * q + 2] = d; }
-				if (t - i > 16) { const uint32_t q = atomicAdd(&segn[ci ^ 1], 1u); nxt[3 * q] = (int32_t)(i + 1); nxt[3 * q + 1] = (int32_t)t; nxt[3 * q + 2] = d; }
+				if (i - s > 16) { const uint32_t q = atomicAdd(&segn[ci ^ 1], 1u); if (q < maxseg) { nxt[3 * q] = (int32_t)s; nxt[3 * q + 1] = (int32_t)(i - 1); nxt[3 * q + 2] = d; } else *err = 1; }
+				if (t - i > 16) { const uint32_t q = atomicAdd(&segn[ci ^ 1], 1u); if (q < maxseg) { nxt[3 * q] = (int32_t)(i + 1); nxt[3 * q + 1] = (int32_t)t; nxt[3 * q + 2] = d; } else *err = 1; }
 			}
 			HAO_WFENCE();
 		}
@@ -1406,6 +1410,7 @@ struct hao_sel_args {
 	uint64_t *key_xs; int32_t *key_sc; uint32_t *key_al, *key_tmp;   // global key scratch (reads with more chains than the LDS slice holds); key_tmp: 5 words per chain
 	uint32_t *perm; uint32_t *n_final; uint64_t *fc_final;        // outputs: permutation (per read slice), kept count, kept fake-cigar entries
 	uint64_t max_n_chain, ocv_w; uint32_t chain_cutoff;
+	int *err;                     // set when a sort's invariant breaks (hao_block_intro_sort's level lists): the call fails
 	int dbg_seq_prune;            // HAO_DBG_FORCE=seq_prune: the one-lane pruning scan
 	unsigned long long *dbg;      // optional phase timers (HAO_DBG_PRINT=sel): wall-clock ticks summed over reads: score sort, prune, position sort, weak filter, reads
 };
@@ -1709,12 +1714,20 @@ __device__ __forceinline__ void hao_select_body(const hao_sel_args &A, const uin
 	if (lane == 0) { A.n_final[r] = (uint32_t)nf; A.fc_final[r] = fct; }
 }
 
+// the LDS of the two selection kernels (hao_sortdbg.hpp runs the sorts alone inside the same declarations)
+#define HAO_SELECT_LDS(WPB, CAP) \
+	__shared__ uint64_t l_xs[WPB][CAP]; __shared__ int32_t l_sc[WPB][CAP]; __shared__ uint32_t l_al[WPB][CAP], l_pm[WPB][CAP], l_pm2[WPB][CAP], l_lp[WPB][CAP], l_rp[WPB][CAP]; __shared__ int32_t l_stack[WPB][3 * 72]; __shared__ uint64_t l_cc[WPB][HAO_SEL_CCAP];
+#define HAO_SELECT4_LDS(CAP) \
+	__shared__ uint64_t l_xs[CAP]; __shared__ int32_t l_sc[CAP]; __shared__ uint32_t l_al[CAP], l_pm[CAP], l_pm2[CAP], l_lp[CAP], l_rp[CAP]; \
+	__shared__ int32_t l_stack[3 * 72]; __shared__ uint64_t l_cc[HAO_SEL_CCAP]; \
+	__shared__ int32_t l_segs[2 * 3 * HAO_BSORT_MAXSEG(CAP)]; __shared__ uint32_t l_segn[2]; __shared__ int l_flag; __shared__ int64_t l_nf; __shared__ int l_lch;
+
 // WPB waves per workgroup, each wave one read; CAP = chains whose keys fit the wave's LDS slice (reads with more chains keep
 // their keys in global scratch).
 template<int WPB, int CAP>
 __global__ __launch_bounds__(WPB * 64) void chain_select_kernel(hao_sel_args A, int64_t n_lo, int64_t n_hi)
 {
-	__shared__ uint64_t l_xs[WPB][CAP]; __shared__ int32_t l_sc[WPB][CAP]; __shared__ uint32_t l_al[WPB][CAP], l_pm[WPB][CAP], l_pm2[WPB][CAP], l_lp[WPB][CAP], l_rp[WPB][CAP]; __shared__ int32_t l_stack[WPB][3 * 72]; __shared__ uint64_t l_cc[WPB][HAO_SEL_CCAP];
+	HAO_SELECT_LDS(WPB, CAP)
 	const int wv = threadIdx.x >> 6, lane = hao_lane();
 	const uint64_t r = (uint64_t)blockIdx.x * WPB + wv;
 	if (r > A.n_sel) return;
@@ -1732,9 +1745,7 @@ __global__ __launch_bounds__(WPB * 64) void chain_select_kernel(hao_sel_args A, 
 template<int CAP>
 __global__ __launch_bounds__(256) void chain_select4_kernel(hao_sel_args A, int64_t n_lo, int64_t n_hi)
 {
-	__shared__ uint64_t l_xs[CAP]; __shared__ int32_t l_sc[CAP]; __shared__ uint32_t l_al[CAP], l_pm[CAP], l_pm2[CAP], l_lp[CAP], l_rp[CAP];
-	__shared__ int32_t l_stack[3 * 72]; __shared__ uint64_t l_cc[HAO_SEL_CCAP];
-	__shared__ int32_t l_segs[2 * 3 * HAO_BSORT_MAXSEG]; __shared__ uint32_t l_segn[2]; __shared__ int l_flag; __shared__ int64_t l_nf; __shared__ int l_lch;
+	HAO_SELECT4_LDS(CAP)
 	const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
 	const uint64_t r = blockIdx.x;
 	if (r >= A.n_sel) return;
@@ -1756,7 +1767,7 @@ __global__ __launch_bounds__(256) void chain_select4_kernel(hao_sel_args A, int6
 	hao_sel_ctx S; S.xs = l_xs; S.sc = l_sc; S.al = l_al; S.pm = l_pm; S.stack = l_stack; S.pm2 = l_pm2; S.lpos = l_lp; S.rasc = l_rp;
 	int64_t nf = n; int lch2 = lch;
 	if ((uint64_t)n > A.max_n_chain) {
-		hao_block_intro_sort<0, 4>(S, n, l_segs, l_segn, &l_flag);
+		hao_block_intro_sort<0, 4>(S, n, l_segs, HAO_BSORT_MAXSEG(CAP), l_segn, &l_flag, A.err);
 		if (wv == 0) {
 			const bool cc_lds = (uint64_t)A.len[A.rid_lo + r] / A.ocv_w + 2 <= HAO_SEL_CCAP;
 			if ((uint64_t)n * A.ocv_w < UINT32_MAX) nf = cc_lds ? hao_select_prune_wave<true>(A, S, n, lch, r, &lch2, l_cc) : hao_select_prune_wave<false>(A, S, n, lch, r, &lch2, l_cc);
@@ -1766,7 +1777,7 @@ __global__ __launch_bounds__(256) void chain_select4_kernel(hao_sel_args A, int6
 		__syncthreads();
 		nf = l_nf; lch2 = l_lch;
 	}
-	hao_block_intro_sort<1, 4>(S, nf, l_segs, l_segn, &l_flag);
+	hao_block_intro_sort<1, 4>(S, nf, l_segs, HAO_BSORT_MAXSEG(CAP), l_segn, &l_flag, A.err);
 	__syncthreads();
 	if (wv != 0) return;
 	if (lch2) nf = hao_select_weak(A, S, nf, rec, A.cd + o0);
@@ -1776,6 +1787,30 @@ __global__ __launch_bounds__(256) void chain_select4_kernel(hao_sel_args A, int6
 #pragma unroll
 	for (int d = 32; d >= 1; d >>= 1) fct += __shfl_xor(fct, d);
 	if (lane == 0) { A.n_final[r] = (uint32_t)nf; A.fc_final[r] = fct; }
+}
+
+// The launches of the selection, split by a read's chain count n: the common reads (<= 128 chains) need 5 KB of LDS per wave and fill the CUs; 129 .. 4096 chains:
+// four waves per read share the sorts, keys in an LDS slice of 512, 1024, 2048 or 4096 chains (reads that cross repeat families have thousands - 250 Mb repeat-rich
+// set: a quarter of the reads more than 1024; with the keys in global scratch and one wave per read those took 17 ms per batch, 64 / 128 KB of LDS per read keeps
+// them on the four-wave path); beyond 4096 the keys stay in global scratch, one wave per read.
+struct hao_sel_tier { int block, cap; int64_t n_lo, n_hi; };      // block: chain_select4_kernel<cap> (else chain_select_kernel<1, cap>), reads with n_lo <= n < n_hi
+static const hao_sel_tier hao_sel_tiers[6] = { { 0, 128, 0, 129 }, { 1, 512, 129, 513 }, { 1, 1024, 513, 1025 }, { 1, 2048, 1025, 2049 }, { 1, 4096, 2049, 4097 }, { 0, 1024, 4097, INT64_MAX } };
+static inline int hao_sel_tier_of(int64_t n) { int t = 0; while (t < 5 && n >= hao_sel_tiers[t].n_hi) ++t; return t; }
+static inline hipError_t hao_select_launch(const hao_sel_args &sa, uint64_t n_reads, hipStream_t st)
+{
+	const hao_sel_tier *T = hao_sel_tiers; hipError_t e;
+	hipLaunchKernelGGL((chain_select_kernel<1, 128>), dim3((unsigned)(n_reads + 1)), dim3(64), 0, st, sa, T[0].n_lo, T[0].n_hi);
+	if ((e = hipGetLastError()) != hipSuccess) return e;
+	hipLaunchKernelGGL((chain_select4_kernel<512>), dim3((unsigned)n_reads), dim3(256), 0, st, sa, T[1].n_lo, T[1].n_hi);
+	if ((e = hipGetLastError()) != hipSuccess) return e;
+	hipLaunchKernelGGL((chain_select4_kernel<1024>), dim3((unsigned)n_reads), dim3(256), 0, st, sa, T[2].n_lo, T[2].n_hi);
+	if ((e = hipGetLastError()) != hipSuccess) return e;
+	hipLaunchKernelGGL((chain_select4_kernel<2048>), dim3((unsigned)n_reads), dim3(256), 0, st, sa, T[3].n_lo, T[3].n_hi);
+	if ((e = hipGetLastError()) != hipSuccess) return e;
+	hipLaunchKernelGGL((chain_select4_kernel<4096>), dim3((unsigned)n_reads), dim3(256), 0, st, sa, T[4].n_lo, T[4].n_hi);
+	if ((e = hipGetLastError()) != hipSuccess) return e;
+	hipLaunchKernelGGL((chain_select_kernel<1, 1024>), dim3((unsigned)(n_reads + 1)), dim3(64), 0, st, sa, T[5].n_lo, T[5].n_hi);
+	return hipGetLastError();
 }
 
 // final gather: records in final order (align_length zeroed, anchor.cpp:2098) + fake cigars in that order. One wave per read.

@@ -559,6 +559,25 @@ int hao_selftest_big(uint64_t n, uint64_t out[3]);
  * be 0), runs the fix-up rewrote (must be > 0 for the test to mean anything), scratch elements used, scratch overflow flag }. */
 int hao_selftest_sortbits(hao_ctx *c, uint64_t n, uint64_t out[4]);
 
+/* HAO_DBG_*: debug entry - the selection's sorts alone, on given keys (hao_sortdbg.hpp; tests/test_gpu_sortperm.py).  The order of ol->list depends on the tie order
+ * of klib's introsort (ksort.h:110-160), which the device replays three ways; this entry runs one of them on n_arr key arrays given as a CSR (off[0] = 0, off[n_arr]
+ * keys in xs / sc) and returns, for array a, perm[off[a] + i] = index within the array of the key at slot i.  mode 0 sorts by sc descending (oreg_ss_lt, anchor.cpp:35),
+ * mode 1 by xs = x_pos_s << 32 | x_pos_e ascending (oreg_xs_lt, anchor.cpp:32).  The paths call the device functions the selection calls:
+ *   HAO_SORTDBG_SEQ          hao_intro_sort on one lane, keys in global memory;
+ *   HAO_SORTDBG_WAVE_LDS     hao_wave_intro_sort, keys in the LDS of chain_select_kernel<1, 128> (variant 0, arrays of at most 128 keys) or <1, 1024> (variant 1, 1024);
+ *   HAO_SORTDBG_WAVE_GLOBAL  hao_wave_intro_sort, keys and work arrays in global scratch as the selection lays them out for reads beyond every LDS tier;
+ *   HAO_SORTDBG_BLOCK        hao_block_intro_sort on four waves in the LDS of chain_select4_kernel, the tier chosen by the array's length as the selection chooses it
+ *                            (arrays below the first four-wave tier run in its slice); at most 4096 keys;
+ *   HAO_SORTDBG_SELECT       mode 1 only: the selection's own launches over one synthetic read per array, without pruning and without the weak-chain filter.
+ * variant is 0 except where named.  Offsets that do not ascend, an array longer than the path holds, mode 0 with HAO_SORTDBG_SELECT: HAO_EINVAL; a sort whose
+ * level list would overflow: HAO_EUNSUPP (as in a batch). */
+#define HAO_SORTDBG_SEQ 0
+#define HAO_SORTDBG_WAVE_LDS 1
+#define HAO_SORTDBG_WAVE_GLOBAL 2
+#define HAO_SORTDBG_BLOCK 3
+#define HAO_SORTDBG_SELECT 4
+int hao_dbg_sort_perm(hao_ctx *c, int mode, int path, int variant, uint64_t n_arr, const uint64_t *off, const uint64_t *xs, const int32_t *sc, uint32_t *perm);
+
 /* per-stage device time of the last call in milliseconds (HIP events on the engine's stream);
  * names[i] points to static strings. Returns the number of stages. */
 int hao_stage_times(hao_ctx *c, const char **names, float *ms, int cap);

@@ -950,6 +950,19 @@ static void intro_sort(srt_t *S, int64_t n, lt_fn lt)
 	}
 }
 
+/* the sort alone, on given keys: mode 0 = by sc descending (lt_score_desc), mode 1 = by xs = x_pos_s << 32 | x_pos_e ascending (lt_xs); perm[i] = input index
+ * of the record at slot i.  tests/test_sortperm_cpu.py pins it to the reference's own ks_introsort_or_ss / _or_xs (tests/golden/sortperm.npz). */
+void hao_or_sort_perm(int mode, int64_t n, const uint64_t *xs, const int32_t *sc, uint32_t *perm)
+{
+	srt_t S; int64_t i;
+	S.r = (hao_or_ovlp_t*)xrealloc(0, (n + 1) * sizeof(hao_or_ovlp_t)); S.fo = (uint64_t*)xrealloc(0, (n + 1) * 8);
+	memset(S.r, 0, (n + 1) * sizeof(hao_or_ovlp_t));
+	for (i = 0; i < n; ++i) { S.r[i].x_pos_s = (uint32_t)(xs[i] >> 32); S.r[i].x_pos_e = (uint32_t)xs[i]; S.r[i].shared_seed = (uint32_t)sc[i]; S.r[i].y_id = (uint32_t)i; S.fo[i] = (uint64_t)i; }
+	intro_sort(&S, n, mode == 0 ? lt_score_desc : lt_xs);
+	for (i = 0; i < n; ++i) perm[i] = S.r[i].y_id;
+	free(S.r); free(S.fo);
+}
+
 /* ------------------------------------------------------------------ */
 /* a13/a14: per-read chain selection + glue                             */
 /* (lchain_qgen_mcopy_fast anchor.cpp:1920-2100; h_ec_lchain :2302-2315; */

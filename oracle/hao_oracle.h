@@ -104,6 +104,8 @@ void hao_or_window_ed(const hao_or_ctx *c, const uint32_t *task, int64_t n, int3
 void hao_or_window_trace(const hao_or_ctx *c, const uint32_t *task, int64_t n, int mode /* 0 global, 1 / 2 forward / backward extension (:3512, :3620), 3 semi-global with absent diagonals (:3778) */, int32_t *out, uint16_t *cig, int64_t cap);
 
 /* ha_analyze_count (hist.cpp:74-157) with m_peak_hom <= 0 (hg_size unset) / with the prior m_peak_hom (adj_m_peak_hom, hist.cpp:46-72) */
+/* the selection's sort (klib introsort, tie order observable) on given keys: mode 0 by sc descending, mode 1 by xs ascending; perm[i] = input index at slot i */
+void hao_or_sort_perm(int mode, int64_t n, const uint64_t *xs, const int32_t *sc, uint32_t *perm);
 int hao_or_analyze_count(int n_cnt, int start_cnt, const int64_t *cnt, int *peak_het);
 int hao_or_analyze_count_m(int n_cnt, int start_cnt, int m_peak_hom, const int64_t *cnt, int *peak_het);
 

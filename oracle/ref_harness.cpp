@@ -30,6 +30,9 @@
 //   -N X / --rl-cut N / --sc-cut N   handed to the reference's own option parser unchanged (CommandLines.cpp:891, :1003-1005): the floor of max_n_chain
 //                      (ha_opt_update_cov raises it to hom_cov * high_factor, :411-418) and the --ont reader's length / quality cuts (htab.cpp:763-764; the
 //                      random workloads of tests/simt_fuzz.py have reads shorter than the default 1000)
+//   --sort-keys FILE   no read set: FILE = records of (uint32 mode, uint32 n, uint64 xs[n], int32 sc[n]); every record becomes an overlap_region array (mode 0: shared_seed = sc,
+//                      mode 1: x_pos_s / x_pos_e = the halves of xs; y_id = the original index) sorted by the reference's own ks_introsort_or_ss (mode 0) / ks_introsort_or_xs
+//                      (mode 1) (anchor.cpp:33, :36); PREFIX.sortperm.u32 = the y_id of every array after its sort, concatenated (tests/golden/make_golden_sortperm.py)
 //   --bw X             bw_thres of the pass (default 0.02 / 0.05 --ont; the final round uses 0.001, ecovlp.cpp:3957)
 #include <stdio.h>
 #include <stdlib.h>
@@ -53,6 +56,9 @@ void h_ec_lchain(ha_abuf_t *ab, uint32_t rid, char* rs, uint64_t rl, uint64_t mz
 				 int max_n_chain, int apend_be, kvec_t_u8_warp* k_flag, kvec_t_u64_warp* dbg_ct, st_mt_t *sp, uint32_t *high_occ, uint32_t *low_occ, uint32_t is_accurate, uint32_t gen_off, int64_t mcopy_num, double mcopy_rate, uint32_t chain_cutoff, uint32_t mcopy_khit_cut, uint64_t ocv_w);
 void minimizers_qgen0(ha_abuf_t *ab, char* rs, int64_t rl, uint64_t mz_w, uint64_t mz_k, Candidates_list *cl, kvec_t_u8_warp* k_flag,
 				 void *ha_flt_tab, ha_pt_t *ha_idx, All_reads* rdb, kvec_t_u64_warp* dbg_ct, st_mt_t *sp, uint32_t *high_occ, uint32_t *low_occ);
+
+void ks_introsort_or_xs(size_t n, overlap_region a[]);      // KSORT_INIT(or_xs, ...) / KSORT_INIT(or_ss, ...), anchor.cpp:33, :36
+void ks_introsort_or_ss(size_t n, overlap_region a[]);
 
 extern "C" uint64_t refdump_ft(void *flt_tab, uint64_t **keys_out, int32_t **vals_out);
 extern "C" uint64_t refdump_pt(ha_pt_t *pt, uint64_t **keys_out, uint64_t **off_out, uint64_t **pos_out, uint64_t *n_pos_out);
@@ -123,6 +129,26 @@ static void worker_pass(void *data, long i, int tid)
 	b->n_ovlp += b->ol.length; b->n_hits += b->cl.length;
 }
 
+static int sort_keys_mode(const char *fn, const std::string &prefix)
+{
+	FILE *fp = fopen(fn, "rb"); if (!fp) { fprintf(stderr, "cannot read %s\n", fn); return 1; }
+	std::vector<uint32_t> out; std::vector<uint64_t> xs; std::vector<int32_t> sc; uint32_t hd[2];
+	while (fread(hd, 4, 2, fp) == 2) {
+		const uint32_t mode = hd[0], n = hd[1];
+		xs.resize(n + 1); sc.resize(n + 1);
+		if (mode > 1 || fread(xs.data(), 8, n, fp) != n || fread(sc.data(), 4, n, fp) != n) { fprintf(stderr, "%s: damaged record\n", fn); fclose(fp); return 1; }
+		overlap_region *a = (overlap_region*)calloc(n + 1, sizeof(overlap_region));
+		for (uint32_t i = 0; i < n; ++i) { a[i].x_pos_s = (uint32_t)(xs[i] >> 32); a[i].x_pos_e = (uint32_t)xs[i]; a[i].shared_seed = sc[i]; a[i].y_id = i; }
+		if (mode == 0) ks_introsort_or_ss(n, a); else ks_introsort_or_xs(n, a);
+		for (uint32_t i = 0; i < n; ++i) out.push_back(a[i].y_id);
+		free(a);
+	}
+	fclose(fp);
+	out.push_back(0);
+	wr(prefix, "sortperm.u32", out.data(), 4 * (out.size() - 1));
+	return 0;
+}
+
 static tbuf_t *tbuf_init(int n)
 {
 	tbuf_t *b = (tbuf_t*)calloc(n, sizeof(tbuf_t));
@@ -136,7 +162,7 @@ static tbuf_t *tbuf_init(int n)
 int main(int argc, char *argv[])
 {
 	int no_tables_hist = 0, ft_tables = 0;
-	int n_thread = 1, is_ont = 0, do_time = 0, dump_hits = 1, k = -1, w = -1, bf_shift = 0, no_hpc = 0, no_tables = 0, do_digest = 0; const char *fa = 0, *list_fn = 0, *hg = 0, *opt_N = 0, *rl_cut = 0, *sc_cut = 0, *ed_fn = 0, *edg_fn = 0, *eds_fn = 0, *ed1_fn = 0, *ed2_fn = 0, *load_pfx = 0, *save_pfx = 0; std::string prefix;
+	int n_thread = 1, is_ont = 0, do_time = 0, dump_hits = 1, k = -1, w = -1, bf_shift = 0, no_hpc = 0, no_tables = 0, do_digest = 0; const char *fa = 0, *list_fn = 0, *hg = 0, *opt_N = 0, *rl_cut = 0, *sc_cut = 0, *ed_fn = 0, *edg_fn = 0, *eds_fn = 0, *ed1_fn = 0, *ed2_fn = 0, *load_pfx = 0, *save_pfx = 0, *sortkeys_fn = 0; std::string prefix;
 	double bw_arg = -1;
 	for (int i = 1; i < argc; ++i) {
 		if (!strcmp(argv[i], "--ont")) is_ont = 1;
@@ -162,10 +188,12 @@ int main(int argc, char *argv[])
 		else if (!strcmp(argv[i], "--eds-tasks")) eds_fn = argv[++i];
 		else if (!strcmp(argv[i], "--ed1-tasks")) ed1_fn = argv[++i];
 		else if (!strcmp(argv[i], "--ed2-tasks")) ed2_fn = argv[++i];
+		else if (!strcmp(argv[i], "--sort-keys")) sortkeys_fn = argv[++i];
 		else if (!strcmp(argv[i], "--load-index")) load_pfx = argv[++i];
 		else if (!strcmp(argv[i], "--save-index")) save_pfx = argv[++i];      // write_pt_index (htab.cpp:1367) after ha_pt_gen: <prefix>.pt_flt, .pt_flt.bin, .pt_flt.paf.bin
 		else fa = argv[i];
 	}
+	if (sortkeys_fn) return prefix.empty() ? 1 : sort_keys_mode(sortkeys_fn, prefix);
 	if (!fa) { fprintf(stderr, "usage: ref_harness [--ont] [-t N] [-k K] [-w W] [-f BLOOM_BITS] [--dump PREFIX] [--time] reads.fa\n"); return 1; }
 	// the reference's own option parser; -f0 (exact counting) unless -f is given (hifiasm's own default is -f37: 16 GB of Bloom filter)
 	std::vector<std::string> av; char tb[32], kb[32], wb[32], fb[32];

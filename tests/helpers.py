@@ -297,3 +297,76 @@ def device_mem_info():
     hip = ctypes.CDLL(so[0]); fr, to = ctypes.c_size_t(0), ctypes.c_size_t(0)
     assert hip.hipMemGetInfo(ctypes.byref(fr), ctypes.byref(to)) == 0
     return fr.value, to.value
+
+
+# ---- key arrays for the direct tests of the selection sorts (tests/golden/make_golden_sortperm.py stores them in sortperm.npz with the reference's permutations) ----
+SORTPERM_SIZES = (0, 1, 2, 3, 16, 17, 18, 63, 64, 65, 128, 129, 512, 513, 1024, 1025, 2047, 2048, 2049, 2304, 3000, 4095, 4096, 4097, 5000)
+
+
+def _sortperm_pattern(rng, pat, n):
+    """n small non-negative integers in the order the pattern names (the caller turns them into scores or positions)"""
+    i = np.arange(n, dtype=np.int64)
+    if pat == "rand":
+        return rng.permutation(n).astype(np.int64)                    # distinct
+    if pat == "equal":
+        return np.full(n, 7, dtype=np.int64)
+    if pat in ("v2", "v3", "v8", "v100"):
+        return rng.integers(0, int(pat[1:]), n).astype(np.int64)
+    if pat == "asc":
+        return i
+    if pat == "desc":
+        return n - 1 - i
+    if pat == "asc1":                                                  # ascending, only the first element out of place (it belongs at the end)
+        return np.where(i == 0, n, i)
+    if pat == "organ":
+        return np.minimum(i, n - 1 - i)
+    if pat == "saw":
+        return i % 37
+    if pat == "family":                                                # scores of a repeat family: a few small integers, most chains at the lowest
+        return np.minimum(rng.geometric(0.45, n), 12).astype(np.int64)
+    raise ValueError(pat)
+
+
+def sortperm_cases():
+    """[(name, mode, xs uint64[n], sc int32[n])]: mode 0 sorts by sc descending, mode 1 by xs ascending (the other array is zero).  Seeded; every pattern at the
+    sizes that matter to it plus the few-valued arrays a scan found to spread the quicksort widest (make_golden_sortperm.py prints what each case exercises)."""
+    rng = np.random.default_rng(20251018)
+    at = {"rand": SORTPERM_SIZES, "v8": SORTPERM_SIZES,
+          "equal": (2, 3, 17, 64, 65, 129, 513, 1025, 2048, 2304, 3000, 4096), "v2": (3, 18, 64, 513, 2048, 4097), "v3": (2047, 4095),
+          "v100": (128, 1024, 4096),
+          "asc": (3, 17, 18, 64, 65, 129, 513, 1025, 2049, 4096), "desc": (17, 64, 129, 1025, 2049), "asc1": (18, 65, 129, 1024, 4096),
+          "organ": (64, 129, 1024, 2049), "saw": (65, 513, 4095)}
+    out = []
+    for mode in (0, 1):
+        for pat, sizes in at.items():
+            for n in sizes:
+                v = _sortperm_pattern(rng, pat, n)
+                if mode == 0:
+                    xs, sc = np.zeros(n, np.uint64), (1 + v).astype(np.int32)
+                else:                                                  # the pattern in x_pos_s, one x_pos_e for all (the cases further down vary x_pos_e)
+                    xs, sc = (v.astype(np.uint64) << np.uint64(32)) | np.uint64(40000), np.zeros(n, np.int32)
+                out.append((f"m{mode}_{pat}_{n}", mode, xs, sc))
+    for n in (129, 512, 1025, 2304, 4096):
+        out.append((f"m0_family_{n}", 0, np.zeros(n, np.uint64), _sortperm_pattern(rng, "family", n).astype(np.int32)))
+    lim = np.array([-2**31, -2**31 + 1, -1, 0, 1, 2**31 - 2, 2**31 - 1], dtype=np.int64)
+    for n in (2, 3, 7, 64, 129, 2049):                                  # scores at both ends of int32 (n == 7: each limit once, no ties)
+        sc = rng.permutation(lim) if n == 7 else lim[rng.integers(0, 7, n)] if n < 100 else np.where(rng.integers(0, 4, n) == 0, lim[rng.integers(0, 7, n)], rng.integers(-2**31, 2**31, n))
+        out.append((f"m0_limits_{n}", 0, np.zeros(n, np.uint64), sc.astype(np.int32)))
+    for n in (3, 64, 129, 2049):
+        e = rng.permutation(n).astype(np.uint64)
+        out.append((f"m1_eonly_{n}", 1, (np.uint64(12345) << np.uint64(32)) | e, np.zeros(n, np.int32)))                       # equal x_pos_s: x_pos_e decides
+        out.append((f"m1_sonly_{n}", 1, (e << np.uint64(32)) | np.uint64(777), np.zeros(n, np.int32)))                          # equal x_pos_e: only bits 32 and up differ
+        out.append((f"m1_smax_{n}", 1, (np.uint64(0xffffffff) << np.uint64(32)) | (np.uint64(0xffffffff) - e // np.uint64(2)), np.zeros(n, np.int32)))      # x_pos_s = 0xffffffff, pairs of ties, up to the largest key
+    out.append(("m1_smax_2", 1, np.array([0xffffffffffffffff, 0xffffffff00000000], dtype=np.uint64), np.zeros(2, np.int32)))
+    out.append(("m1_top_64", 1, (rng.permutation(64).astype(np.uint64) << np.uint64(58)) | np.uint64(5), np.zeros(64, np.int32)))      # keys that differ in the top bits only
+    return out
+
+
+def load_sortperm():
+    """tests/golden/sortperm.npz as [(name, mode, xs, sc, perm)] (perm = the reference's own ks_introsort_or_ss / _or_xs)"""
+    if "sortperm" not in _CACHE:
+        z = np.load(os.path.join(GOLDEN, "sortperm.npz"))
+        off = z["off"].astype(np.int64)
+        _CACHE["sortperm"] = [(str(nm), int(m), z["xs"][off[i]:off[i + 1]], z["sc"][off[i]:off[i + 1]], z["perm"][off[i]:off[i + 1]].astype(np.int64))
+                              for i, (nm, m) in enumerate(zip(z["names"], z["mode"]))]
+    return _CACHE["sortperm"]

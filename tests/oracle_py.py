@@ -50,8 +50,17 @@ def lib():
         L.hao_or_window_ed.argtypes = [vp, vp, C.c_int64, vp]
         L.hao_or_window_trace.argtypes = [vp, vp, C.c_int64, C.c_int, vp, vp, C.c_int64]
         L.hao_or_analyze_count.argtypes = [C.c_int, C.c_int, i64p, C.POINTER(C.c_int)]; L.hao_or_analyze_count.restype = C.c_int
+        L.hao_or_sort_perm.argtypes = [C.c_int, C.c_int64, u64p, C.POINTER(C.c_int32), C.POINTER(C.c_uint32)]; L.hao_or_sort_perm.restype = None
         _LIB = L
     return _LIB
+
+
+def sort_perm(mode, xs, sc):
+    """the oracle's klib introsort on given keys (mode 0: by sc descending, mode 1: by xs ascending): input index of the record at every slot"""
+    xs = np.ascontiguousarray(xs, dtype=np.uint64); sc = np.ascontiguousarray(sc, dtype=np.int32); n = len(xs)
+    perm = np.zeros(n + 1, dtype=np.uint32)
+    lib().hao_or_sort_perm(mode, n, xs.ctypes.data_as(C.POINTER(C.c_uint64)), sc.ctypes.data_as(C.POINTER(C.c_int32)), perm.ctypes.data_as(C.POINTER(C.c_uint32)))
+    return perm[:n].astype(np.int64)
 
 
 def _arr(ptr, n, dtype):
