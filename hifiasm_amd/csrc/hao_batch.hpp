@@ -1,6 +1,5 @@
 // Host orchestration of one query batch: h_ec_lchain for reads [lo, hi) (part of libhao.so).
 #pragma once
-#include <sys/mman.h>
 #include "hao_tables.hpp"
 #include "hao_query.cuh"
 #include "hao_query3.cuh"
@@ -21,7 +20,7 @@ struct hao_ctx::Batch {
 	DevBuf<hao_chain_rec> rec; DevBuf<hao_ovlp_t> ol; DevBuf<hao_cdesc> cd; bool cl_valid = false;
 	DevBuf<uint16_t> hq, ohq; DevBuf<uint8_t> hcode;      // delivery path: query minimizer index / wire code of every seed hit (seed kernel, chain_group_kernel)
 	DevBuf<uint32_t> pk_cnt, pk_ecnt, pk_erank; uint64_t n_codes = 0;      // one code byte per chained hit (device only) before it is split into bits + code bytes
-	// Results of a batch that leave the device.  Two sets (+ two pinned host arenas): while the copy stream drains the set of batch i, batch i + 1
+	// Results of a batch that leave the device.  Two sets, one per delivery slot: while the copy stream drains the set of batch i, batch i + 1
 	// computes into the other one (hao_overlap_batch_async).  The blocking API keeps using the current set.
 	struct OutSet {
 		DevBuf<hao_ovlp_t> ol_out; DevBuf<hao_ovlp_wire_t> ol_wire; DevBuf<uint64_t> fin_off, fc_out, fc_out_off, ch_off, cl_off, qm_off, fcw_off; DevBuf<uint32_t> fcw;      // (fcw*: the fake cigars as they travel, hao_deliver.cuh)
@@ -33,21 +32,30 @@ struct hao_ctx::Batch {
 		DevBuf<uint64_t> wl_woff, wl_cigoff; DevBuf<hao_rs_win> wl_wins; DevBuf<uint16_t> wl_cig;      // HAO_DELIVER_WLIST: record offsets per overlap, the records, entry offsets per record, the entries (hao_wlist.cuh)
 		DevBuf<hao_rs_ovlp> rs_ovlp; DevBuf<uint64_t> rs_off; DevBuf<hao_rs_win> rs_wins;                // HAO_DELIVER_RESCUE: per-overlap results, record offsets per overlap, the records (hao_rescue.cuh)
 		DevBuf<uint64_t> tr_off; DevBuf<uint16_t> tr_ps, tr_ncig, tr_cig;                            // HAO_DELIVER_TRACE: cigar entries per read, ps and entry count per pair, the entries (hao_trace_grid.cuh)
-	} out[2];
+	};
+	// One delivery slot: the output set its batch computes into, the pinned host arena the copy stream drains that set into, and what the caller sees of it
+	// (members: hao_deliver_host.hpp)
+	struct Slot {
+		OutSet out;
+		unsigned char *arena = nullptr; size_t arena_cap = 0; bool arena_reg = false, arena_bad = false; int arena_retry = 0;      // arena_reg: mmap + mbind + hipHostRegister (hao_arena_alloc_bound); arena_bad / arena_retry: hao_deliver_wait saw a slow copy - allocated again for the next batch, once
+		hipEvent_t ev_ready = nullptr, ev_done = nullptr, ev_cstart = nullptr;      // compute stream: the batch's results are complete; copy stream: the copy has landed / starts
+		bool pending = false;      // a copy is queued that nobody has waited for
+		uint32_t parts = 0;        // the HAO_DELIVER_* bits the slot's last streamed batch asked for
+		hao_delivery_t dl = {}; hao_ed_delivery_t ed = {}; hao_trace_delivery_t tr = {}; hao_rescue_delivery_t rs = {}; hao_wlist_delivery_t wl = {};      // the views (ed.window 0: the batch did not ask for HAO_DELIVER_ED)
+		void begin(uint32_t parts_, uint64_t lo, uint64_t n, const hao_ctx *c);
+		void arena_free();
+	} slot[2];
 	int cur = 0;
-	OutSet &O() { return out[cur]; }
-	// delivery state: pinned host arenas, copy stream, per-slot completion events
-	unsigned char *arena[2] = { nullptr, nullptr }; size_t arena_cap[2] = { 0, 0 }; bool arena_reg[2] = { false, false };      // arena_reg: mmap + mbind + hipHostRegister (hao_arena_alloc)
-	void arena_free(int x) { if (!arena[x]) return; if (arena_reg[x]) { (void)hipHostUnregister(arena[x]); (void)munmap(arena[x], arena_cap[x]); } else (void)hipHostFree(arena[x]); arena[x] = nullptr; arena_cap[x] = 0; arena_reg[x] = false; } hipStream_t copy_stream = nullptr; hipEvent_t ev_ready[2], ev_done[2], ev_cstart[2]; bool arena_bad[2] = { false, false }; int arena_retry[2] = { 0, 0 }, arena_node = -1;      /* arena_node: the NUMA node a probe found best (a box of round 6 reported the GPU on node 0 and copied at 30 GB/s into node 0, 56 into node 1) */ bool dl_ready = false, dl_pending[2] = { false, false };
+	OutSet &O() { return slot[cur].out; }
+	hipStream_t copy_stream = nullptr; int arena_node = -1; bool dl_ready = false;      // delivery state shared by the slots (hao_deliver_init); arena_node: the NUMA node a probe found best (a box of round 6 reported the GPU on node 0 and copied at 30 GB/s into node 0, 56 into node 1)
 	uint32_t wgt_hi = 0xffffffffu, wgt_lo = 0xffffffffu, wgt_max = 0xffffffffu;      // (wgt_max: the largest k_mer_hit::cnt the pass's weight table can give)
 	double t_evsync = 0, t_enq = 0, t_alloc = 0, t_s1 = 0, t_s2 = 0, t_s3 = 0, t_run = 0, t_pre = 0; uint64_t t_n = 0, t_nrun = 0;      // host-side time spent in the delivery plumbing (HAO_DBG_PRINT=dl)
 	uint64_t ed_unres = 0;      // HAO_DELIVER_ED in reference placement: windows of the batch whose start resolved to no cigar entry
 	DevBuf<uint64_t> ed_nwin, ed_wbase, ed_wcnt, ed_woff; DevBuf<hao_ed_pair> ed_pairs; uint64_t ed_n = 0;      // HAO_DELIVER_ED scratch (compute stream only: not per output set); ed_n = pairs of the batch
-	hao_ed_delivery_t ed_dl[2] = {};      // the ED view of each slot (window 0: the slot's batch did not ask for HAO_DELIVER_ED)
-	uint64_t wl_cnt[5] = { 0, 0, 0, 0, 0 }; hao_wlist_delivery_t wl_dl[2] = {}; bool wl_on[2] = { false, false };      // HAO_DELIVER_WLIST: hao_al_wlist's five counts of the batch; the view of each slot
-	uint64_t rs_nw = 0, rs_nres = 0, rs_wc = 0; hao_rescue_delivery_t rs_dl[2] = {}; bool rs_on[2] = { false, false };      // HAO_DELIVER_RESCUE: window records and rescued windows of the batch, its covered windows; the view of each slot
-	uint64_t tr_n = 0, tr_ncig = 0; hao_trace_delivery_t tr_dl[2] = {}; bool tr_on[2] = { false, false };      // HAO_DELIVER_TRACE: traced pairs and cigar entries of the batch; the view of each slot (tr_on: the slot's batch asked for it)
-	hao_delivery_t dl[2]; uint64_t dl_seq = 0, n_exc = 0; uint32_t dl_parts = 0; bool exact_valid = false; std::vector<uint8_t> h_exact;
+	uint64_t wl_cnt[5] = { 0, 0, 0, 0, 0 };      // HAO_DELIVER_WLIST: hao_al_wlist's five counts of the batch
+	uint64_t rs_nw = 0, rs_nres = 0, rs_wc = 0;      // HAO_DELIVER_RESCUE: window records and rescued windows of the batch, its covered windows
+	uint64_t tr_n = 0, tr_ncig = 0;      // HAO_DELIVER_TRACE: traced pairs and cigar entries of the batch
+	uint64_t dl_seq = 0, n_exc = 0; uint32_t dl_parts = 0; bool exact_valid = false; std::vector<uint8_t> h_exact;
 	// host copies for fetch
 	std::vector<uint64_t> h_seg, h_fin_off, h_cl_off, h_fc_out_off; std::vector<hao_hit_t> h_hits, h_cl; std::vector<hao_ovlp_t> h_ol; std::vector<uint64_t> h_fc;
 	std::vector<uint64_t> fetch_fc_off, h_cco;
@@ -55,7 +63,7 @@ struct hao_ctx::Batch {
 	~Batch() {
 		if (ev_pk0) { (void)hipEventDestroy(ev_pk0); (void)hipEventDestroy(ev_pk1); }
 		if (side_ready) { for (int x = 0; x < HAO_NCLS; ++x) { (void)hipStreamDestroy(side[x]); (void)hipEventDestroy(ev_qc[x]); (void)hipEventDestroy(ev_dp[x]); } }
-		if (dl_ready) { (void)hipStreamSynchronize(copy_stream); (void)hipStreamDestroy(copy_stream); for (int x = 0; x < 2; ++x) { (void)hipEventDestroy(ev_ready[x]); (void)hipEventDestroy(ev_done[x]); (void)hipEventDestroy(ev_cstart[x]); arena_free(x); } }
+		if (dl_ready) { (void)hipStreamSynchronize(copy_stream); (void)hipStreamDestroy(copy_stream); for (Slot &s : slot) { (void)hipEventDestroy(s.ev_ready); (void)hipEventDestroy(s.ev_done); (void)hipEventDestroy(s.ev_cstart); s.arena_free(); } }
 	}
 };
 
@@ -77,88 +85,8 @@ __global__ void hao_fclen_kernel(const hao_chain_rec *rec, const uint32_t *nch, 
 }
 
 #include <chrono>
-#include <sys/syscall.h>
-#include <unistd.h>
-// The delivery arenas should live on the NUMA node the GPU hangs off: on a two-socket host a pinned buffer on the far socket costs the DMA ~40 % of its
-// rate (measured: 29-35 GB/s instead of 51-56).  The pages of a hipHostMalloc are placed by the calling thread's memory policy, so the allocation is
-// bracketed by set_mempolicy(MPOL_PREFERRED, gpu node) / MPOL_DEFAULT (raw syscalls: no libnuma in the image; failures - seccomp, no sysfs - are ignored).
-static int hao_gpu_numa_node(int device)
-{
-	char bus[64] = {0};
-	if (hipDeviceGetPCIBusId(bus, sizeof(bus), device) != hipSuccess) return -1;
-	for (char *p = bus; *p; ++p) if (*p >= 'A' && *p <= 'F') *p = (char)(*p - 'A' + 'a');
-	char path[160]; snprintf(path, sizeof(path), "/sys/bus/pci/devices/%s/numa_node", bus);
-	FILE *fp = fopen(path, "r"); int node = -1;
-	if (fp) { if (fscanf(fp, "%d", &node) != 1) node = -1; fclose(fp); }
-	return node;
-}
-// The calling thread's NUMA memory policy around one allocation.  The caller may be a thread of a host application (the shim inside hifiasm) that runs under a policy
-// of its own (numactl --interleave ...): the policy found is saved and put back, never reset to the default.
-struct hao_mempolicy_guard {
-	int old_mode = 0; unsigned long old_mask[16]; bool saved = false, applied = false;
-	// mode: 1 = MPOL_PREFERRED, 2 = MPOL_BIND
-	hao_mempolicy_guard(int node, int mode) {
-		memset(old_mask, 0, sizeof(old_mask));
-		if (node < 0 || node >= 1024) return;
-		saved = syscall(SYS_get_mempolicy, &old_mode, old_mask, 1024UL, nullptr, 0UL) == 0;
-		if (!saved) return;      // cannot restore what cannot be read: leave the policy alone
-		unsigned long mask[16]; memset(mask, 0, sizeof(mask)); mask[node / 64] |= 1UL << (node % 64);
-		applied = syscall(SYS_set_mempolicy, mode, mask, 1024UL) == 0;
-	}
-	~hao_mempolicy_guard() {
-		if (!applied) return;
-		bool any = false; for (int i = 0; i < 16; ++i) any |= old_mask[i] != 0;
-		(void)syscall(SYS_set_mempolicy, old_mode, any ? old_mask : (unsigned long*)nullptr, any ? 1024UL : 0UL);
-	}
-};
-// how many of 32 sampled pages of [p, p + bytes) lie on `node` (move_pages with no target nodes only reports); -1: cannot tell
-static int hao_pages_on_node(const void *p, size_t bytes, int node)
-{
-	const long ps = sysconf(_SC_PAGESIZE); if (ps <= 0 || bytes < (size_t)ps) return -1;
-	void *pg[32]; int st[32]; const size_t np = bytes / (size_t)ps;
-	for (int i = 0; i < 32; ++i) { pg[i] = (void*)(((uintptr_t)p + (np - 1) * (size_t)i / 31 * (size_t)ps) & ~(uintptr_t)(ps - 1)); st[i] = -1; }
-	if (syscall(SYS_move_pages, 0, 32UL, pg, (const int*)nullptr, st, 0) != 0) return -1;
-	int on = 0; for (int i = 0; i < 32; ++i) on += st[i] == node;
-	return on;
-}
-// A pinned host buffer whose pages are ON `node`, whatever the allocator of hipHostMalloc does: anonymous mapping, mbind(MPOL_BIND) before the first touch (the kernel
-// then reclaims that node's page cache instead of falling over to the far socket), touched, registered with the runtime.  nullptr when any step fails.
-static unsigned char *hao_arena_alloc_bound(size_t bytes, int node)
-{
-	if (node < 0 || node >= 1024) return nullptr;
-	// (2 MB-aligned and advised as huge pages: what round 6's slow arenas had in common was not their node - a fresh mapping on the SAME node copied at 56 GB/s where the
-	// hipHostMalloc'ed one gave 30 - which leaves the page size the DMA translates through.  The caller passes a multiple of 2 MB.)
-	const size_t HP = (size_t)2 << 20;
-	void *m0 = mmap(nullptr, bytes + HP, PROT_READ | PROT_WRITE, MAP_PRIVATE | MAP_ANONYMOUS, -1, 0);
-	if (m0 == MAP_FAILED) return nullptr;
-	void *m = (void*)(((uintptr_t)m0 + HP - 1) & ~(uintptr_t)(HP - 1));
-	if (m != m0) (void)munmap(m0, (size_t)((uintptr_t)m - (uintptr_t)m0));
-	{ const uintptr_t end0 = (uintptr_t)m0 + bytes + HP, end = (uintptr_t)m + ((bytes + 4095) & ~(size_t)4095); if (end0 > end) (void)munmap((void*)end, (size_t)(end0 - end)); }
-	(void)madvise(m, bytes, MADV_HUGEPAGE);
-	unsigned long mask[16]; memset(mask, 0, sizeof(mask)); mask[node / 64] |= 1UL << (node % 64);
-	if (syscall(SYS_mbind, m, bytes, 2 /* MPOL_BIND */, mask, 1024UL, 0U) != 0) { (void)munmap(m, bytes); return nullptr; }
-	const long ps = sysconf(_SC_PAGESIZE);
-	for (size_t o = 0; o < bytes; o += (size_t)(ps > 0 ? ps : 4096)) ((volatile unsigned char*)m)[o] = 0;
-	if (hipHostRegister(m, bytes, hipHostRegisterMapped | hipHostRegisterPortable) != hipSuccess) { (void)hipGetLastError(); (void)munmap(m, bytes); return nullptr; }
-	return (unsigned char*)m;
-}
-// the NUMA node a probe found best for a device's delivery arenas, kept for the process (every engine and batch context of the device starts from it)
-static int hao_arena_node_of[64] = { -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1,
-	-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1 };
-// GB/s of one device-to-host copy of nb bytes into `host` on the batch's copy stream (HIP events around it); -1 when it cannot be measured
-static double hao_arena_rate(hipStream_t st, unsigned char *host, const void *dsrc, size_t nb)
-{
-	hipEvent_t e0 = nullptr, e1 = nullptr; double r = -1;
-	if (hipEventCreate(&e0) == hipSuccess && hipEventCreate(&e1) == hipSuccess &&
-		hipEventRecord(e0, st) == hipSuccess && hipMemcpyAsync(host, dsrc, nb, hipMemcpyDeviceToHost, st) == hipSuccess && hipEventRecord(e1, st) == hipSuccess && hipEventSynchronize(e1) == hipSuccess) {
-		float ms = 0; if (hipEventElapsedTime(&ms, e0, e1) == hipSuccess && ms > 0) r = (double)nb / ((double)ms * 1e6);
-	}
-	if (e0) (void)hipEventDestroy(e0);
-	if (e1) (void)hipEventDestroy(e1);
-	(void)hipGetLastError();
-	return r;
-}
 static inline double hao_now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+#include "hao_deliver_host.hpp"
 
 static int hao_scan_u32(hao_ctx *c, const uint32_t *in, uint64_t *out, uint64_t n_plus1)
 {
@@ -448,152 +376,6 @@ static int hao_trace_grid_run(hao_ctx *c, uint32_t wl, uint32_t thre, uint64_t o
 	return HAO_OK;
 }
 
-// Queue the copy of the current batch's results into the slot's pinned arena (copy stream, after everything on the compute stream so far).
-static int hao_deliver_enqueue(hao_ctx *c)
-{
-	hao_ctx::Batch &B = *c->batch; const int s = B.cur; hao_ctx::Batch::OutSet &O = B.O(); const uint64_t n = B.n; const uint32_t parts = B.dl_parts;
-	auto al = [](size_t v) { return (v + 63) & ~(size_t)63; };
-	const bool ol = parts & HAO_DELIVER_OL, cl = parts & HAO_DELIVER_CL, ex = parts & HAO_DELIVER_EXACT, ed = parts & HAO_DELIVER_ED, tr = parts & HAO_DELIVER_TRACE, rsq = parts & HAO_DELIVER_RESCUE, wlq = parts & HAO_DELIVER_WLIST;
-	size_t o_oloff = 0, o_ol = o_oloff + (ol ? al((n + 1) * 8) : 0), o_fcoff = o_ol + (ol ? al(B.n_ol * sizeof(hao_ovlp_wire_t)) : 0), o_fc = o_fcoff + (ol ? al((B.n_ol + 1) * 8) : 0);
-	size_t o_choff = o_fc + (ol ? al(B.n_fcw * 4) : 0), o_cloff = o_choff + (cl ? al((n + 1) * 8) : 0), o_qmoff = o_cloff + (cl ? al((n + 1) * 8) : 0), o_hdr = o_qmoff + (cl ? al((n + 1) * 8) : 0);
-	const bool q16 = O.qmz16;      // the minimizer tables in 2 + 2 bytes per minimizer (hao_qtab16_kernel) instead of 8
-	size_t o_qmz = o_hdr + (cl ? al(B.n_chains * sizeof(hao_chain_hdr_t)) : 0), o_qmc = o_qmz + (cl ? al(B.n_mz * (q16 ? 2 : sizeof(hao_qmz_t))) : 0), o_bits = o_qmc + (cl && q16 ? al(B.n_mz * 2) : 0);
-	const uint64_t nw_ = cl ? (B.n_anchor + 63) / 64 : 0;      // 64-position words of the batch's bit stream (positions = seed hits)
-	const uint64_t nr4_ = cl ? nw_ / 4 + 1 : 0;      // rank directory entries on the wire: one per 256 positions
-	size_t o_rank = o_bits + (cl ? al(nw_ * 8) : 0), o_codes = o_rank + (cl ? al(nr4_ * 4) : 0), o_exc = o_codes + (cl ? al(B.n_codes) : 0);
-	size_t o_ex = o_exc + (cl ? al(B.n_exc * sizeof(hao_exc_t)) : 0), o_edoff = o_ex + (ex ? al(B.n_ol) : 0);
-	const bool edref = ed && B.ed_dl[s].placement == HAO_PLACE_REF;      // (reference placement: the per-overlap summaries travel after the pairs' records)
-	size_t o_ederr = o_edoff + (ed ? al((n + 1) * 8) : 0), o_edpe = o_ederr + (ed ? al(B.ed_n) : 0), o_edsum = o_edpe + (ed ? al(B.ed_n * 2) : 0), o_troff = o_edsum + (edref ? al(B.n_ol * sizeof(hao_ed_ovlp_sum)) : 0);      // (without HAO_DELIVER_ED: o_troff = o_edoff, the layout of before; in diagonal placement o_troff = o_edsum)
-	size_t o_trps = o_troff + (tr ? al((n + 1) * 8) : 0), o_trnc = o_trps + (tr ? al(B.ed_n * 2) : 0), o_trcig = o_trnc + (tr ? al(B.ed_n * 2) : 0), o_rsov = o_trcig + (tr ? al(B.tr_ncig * 2) : 0);      // (without HAO_DELIVER_TRACE: o_rsov = o_troff)
-	size_t o_rsoff = o_rsov + (rsq ? al(B.n_ol * sizeof(hao_rs_ovlp)) : 0), o_rswin = o_rsoff + (rsq ? al((B.n_ol + 1) * 8) : 0), o_wloff = o_rswin + (rsq ? al(B.rs_nw * sizeof(hao_rs_win)) : 0);      // (without HAO_DELIVER_RESCUE: o_wloff = o_rsov, the layout of before)
-	size_t o_wlwin = o_wloff + (wlq ? al((B.n_ol + 1) * 8) : 0), o_wlcoff = o_wlwin + (wlq ? al(B.wl_cnt[0] * sizeof(hao_rs_win)) : 0), o_wlcig = o_wlcoff + (wlq ? al((B.wl_cnt[0] + 1) * 8) : 0), total = o_wlcig + (wlq ? al(B.wl_cnt[3] * 2) : 0);      // (without HAO_DELIVER_WLIST: total = o_wloff)
-	if (total > B.arena_cap[s] || B.arena_bad[s]) {
-		const bool redo_ = B.arena_bad[s]; B.arena_bad[s] = false;      // (hao_deliver_wait saw this slot's last batch copied at less than 40 GB/s: the probe below tries every NUMA node)
-		B.arena_free(s);
-		const size_t want = (total + total / 4 + (1 << 20) + (((size_t)2 << 20) - 1)) & ~(((size_t)2 << 20) - 1);      // (a multiple of 2 MB: hao_arena_alloc_bound)
-		const double t0_ = hao_now();
-		const int node_ = c->sw.arena_numa ? hao_gpu_numa_node(c->device) : -1;
-		// MPOL_BIND first: "preferred" silently falls over to the far socket when the GPU's node is short of FREE pages (a process that has just generated or
-		// parsed gigabytes of reads leaves it full of page cache) - the same box then delivers at 36 instead of 52 GB/s; bound, the kernel reclaims instead.
-		// If the bound allocation fails, once more with the preference only.
-		hipError_t he_ = hipErrorOutOfMemory; const char *how_ = "default policy";
-		if (B.arena_node >= 0) if (unsigned char *m_ = hao_arena_alloc_bound(want, B.arena_node)) { B.arena[s] = m_; B.arena_reg[s] = true; he_ = hipSuccess; how_ = "by hand on the node an earlier probe chose"; }
-		if (he_ != hipSuccess && node_ >= 0 && c->sw.arena_numa != 1) {
-			hao_mempolicy_guard g_(node_, 2 /* MPOL_BIND */);
-			if (g_.applied) {
-				he_ = hipHostMalloc((void**)&B.arena[s], want, (c->sw.arena_numa == 2) ? hipHostMallocNumaUser : hipHostMallocDefault);
-				if (he_ != hipSuccess) { B.arena[s] = nullptr; (void)hipGetLastError(); } else how_ = "bound";
-			}
-		}
-		if (he_ != hipSuccess) {
-			hao_mempolicy_guard g_(node_, 1 /* MPOL_PREFERRED */);
-			he_ = hipHostMalloc((void**)&B.arena[s], want, (c->sw.arena_numa == 2 && g_.applied) ? hipHostMallocNumaUser : hipHostMallocDefault);
-			if (he_ == hipSuccess && g_.applied) how_ = "preferred";
-		}
-		// where did the pages land?  hipHostMalloc does not always honour the calling thread's policy (one run of round 6 delivered configs[2] at 28.6 GB/s and, with
-		// arenas allocated later in the same process, at 53.5): if fewer than 28 of 32 sampled pages are on the GPU's node, the arena is allocated again by hand
-		int on_ = -1;
-		if (he_ == hipSuccess && node_ >= 0) {
-			on_ = hao_pages_on_node(B.arena[s], want, node_);
-			if (!B.arena_reg[s] && ((on_ >= 0 && on_ < 28) || c->sw.arena_numa == 4)) {      // (HAO_ARENA_NUMA=4: always by hand - tests)
-				if (unsigned char *m_ = hao_arena_alloc_bound(want, node_)) { (void)hipHostFree(B.arena[s]); B.arena[s] = m_; B.arena_reg[s] = true; how_ = "mmap + mbind + hipHostRegister"; on_ = hao_pages_on_node(m_, want, node_); }
-			}
-		}
-		// What the placement is worth is MEASURED: one run in eight of round 6 still delivered at 28.7 instead of 50 GB/s (same box, next process: 49.8) with every page
-		// reported on the GPU's node.  A 128 MB copy into the new arena is timed; below 50 GB/s a 128 MB buffer bound to each NUMA node in turn gets the same copy and the
-		// arena moves to the best node when that is 10 % faster.  (Arenas of 64 MB and more; HAO_DBG_TEST=arena_probe=1: always and whatever the size - tests.)
-		if (he_ == hipSuccess && c->sw.arena_numa && (want >= ((size_t)64 << 20) || c->sw.arena_probe) && B.hits.p) {
-			const size_t nb = std::min<size_t>(std::min<size_t>(want, (size_t)128 << 20), B.hits.cap * sizeof(hao_hit_t)) & ~(size_t)4095;
-			if (nb >= 4096) {
-				(void)hao_arena_rate(B.copy_stream, B.arena[s], B.hits.p, nb);      // (first touch of the mapping)
-				const double r0 = hao_arena_rate(B.copy_stream, B.arena[s], B.hits.p, nb);
-				if ((r0 >= 0 && r0 < 50.0) || c->sw.arena_probe || redo_) {      // (a good arena: 55 - 57 GB/s with the device otherwise idle, as it is here)
-					int best_k = -1; double best = r0;
-					for (int k = 0; k < 16; ++k) {
-						unsigned char *m_ = hao_arena_alloc_bound(nb, k); if (!m_) continue;
-						(void)hao_arena_rate(B.copy_stream, m_, B.hits.p, nb);
-						const double rk = hao_arena_rate(B.copy_stream, m_, B.hits.p, nb);
-						(void)hipHostUnregister(m_); (void)munmap(m_, nb);
-						if (c->sw.dltime || c->sw.arena_probe) fprintf(stderr, "[deliver] arena %d probe: NUMA node %d %.1f GB/s\n", s, k, rk);
-						if (rk > best * 1.1) { best = rk; best_k = k; }
-					}
-					if (best_k >= 0) if (unsigned char *m_ = hao_arena_alloc_bound(want, best_k)) { B.arena_cap[s] = want; B.arena_free(s); B.arena[s] = m_; B.arena_reg[s] = true; B.arena_node = best_k; if (c->device >= 0 && c->device < 64) hao_arena_node_of[c->device] = best_k; how_ = "moved after the probe"; }      // (arena_free unmaps arena_cap bytes of a registered arena)
-					fprintf(stderr, "[hao] delivery arena %d: %.1f GB/s from the device as allocated (GPU NUMA node %d, %s)%s\n", s, r0, node_, how_, best_k >= 0 ? "" : "; no NUMA node does better");
-					if (best_k >= 0) fprintf(stderr, "[hao] delivery arena %d: moved to NUMA node %d (%.1f GB/s)\n", s, best_k, best);
-				}
-			}
-		}
-		if (c->sw.dltime) fprintf(stderr, "[deliver] arena %d: %zu MB, GPU NUMA node %d (requested mode %d, allocated %s, %d of 32 sampled pages on the node)\n", s, want >> 20, node_, c->sw.arena_numa, he_ == hipSuccess ? how_ : "FAILED", on_);
-		HIP_TRY(he_);
-		B.arena_cap[s] = want; B.t_alloc += hao_now() - t0_;
-	}
-	unsigned char *a = B.arena[s];
-	HIP_TRY(hipEventRecord(B.ev_ready[s], c->stream));
-	HIP_TRY(hipStreamWaitEvent(B.copy_stream, B.ev_ready[s], 0));
-	HIP_TRY(hipEventRecord(B.ev_cstart[s], B.copy_stream));      // (the copy itself, without the wait behind the previous batch's: hao_deliver_wait checks its rate)
-	auto cp = [&](size_t off, const void *src, size_t bytes) -> hipError_t { return bytes ? hipMemcpyAsync(a + off, src, bytes, hipMemcpyDeviceToHost, B.copy_stream) : hipSuccess; };
-	hao_delivery_t &d = B.dl[s];
-	d.rid_lo = B.lo; d.n_reads = n; d.n_ol = d.n_fc = d.n_chains = d.n_cl = d.n_exc = d.n_codes = d.n_pos = 0; d.bytes = 0;
-	if (ol && n) {
-		HIP_TRY(cp(o_oloff, O.fin_off.p, (n + 1) * 8)); HIP_TRY(cp(o_ol, O.ol_wire.p, B.n_ol * sizeof(hao_ovlp_wire_t)));
-		HIP_TRY(cp(o_fcoff, O.fcw_off.p, B.n_ol * 8)); HIP_TRY(cp(o_fc, O.fcw.p, B.n_fcw * 4));
-		((uint64_t*)(a + o_fcoff))[B.n_ol] = B.n_fcw;      // end of the last cigar (a host-side word next to, not inside, the region the copy writes)
-		d.n_ol = B.n_ol; d.n_fc = B.n_fcw; d.ol_off = (const uint64_t*)(a + o_oloff); d.ol = (const hao_ovlp_wire_t*)(a + o_ol); d.fc_off = (const uint64_t*)(a + o_fcoff); d.fc = (const uint32_t*)(a + o_fc);
-		d.bytes += (n + 1) * 8 + B.n_ol * (sizeof(hao_ovlp_wire_t) + 8) + B.n_fcw * 4;
-	}
-	if (cl && n) {
-		HIP_TRY(cp(o_choff, O.ch_off.p, (n + 1) * 8)); HIP_TRY(cp(o_cloff, O.cl_off.p, (n + 1) * 8)); HIP_TRY(cp(o_qmoff, O.qm_off.p, (n + 1) * 8));
-		HIP_TRY(cp(o_hdr, O.hdr.p, B.n_chains * sizeof(hao_chain_hdr_t))); if (q16) { HIP_TRY(cp(o_qmz, O.qmz_pos.p, B.n_mz * 2)); HIP_TRY(cp(o_qmc, O.qmz_cnt.p, B.n_mz * 2)); } else HIP_TRY(cp(o_qmz, O.qmz.p, B.n_mz * sizeof(hao_qmz_t))); HIP_TRY(cp(o_exc, O.exc.p, B.n_exc * sizeof(hao_exc_t)));
-		HIP_TRY(cp(o_bits, O.bits.p, nw_ * 8)); HIP_TRY(cp(o_rank, O.rank4.p, nr4_ * 4));
-		HIP_TRY(cp(o_codes, O.codes.p, B.n_codes));
-		d.n_chains = B.n_chains; d.n_cl = B.n_cl; d.n_exc = B.n_exc; d.n_codes = B.n_codes; d.n_pos = B.n_anchor; d.ch_off = (const uint64_t*)(a + o_choff); d.cl_off = (const uint64_t*)(a + o_cloff); d.qm_off = (const uint64_t*)(a + o_qmoff);
-		d.chains = (const hao_chain_hdr_t*)(a + o_hdr); d.qmz = q16 ? nullptr : (const hao_qmz_t*)(a + o_qmz); d.qmz_pos = q16 ? (const uint16_t*)(a + o_qmz) : nullptr; d.qmz_cnt = q16 ? (const uint16_t*)(a + o_qmc) : nullptr; d.cl_bits = (const uint64_t*)(a + o_bits); d.cl_rank = (const uint32_t*)(a + o_rank); d.cl_codes = a + o_codes; d.cl_exc = (const hao_exc_t*)(a + o_exc);
-		d.bytes += 3 * (n + 1) * 8 + B.n_chains * sizeof(hao_chain_hdr_t) + B.n_mz * (q16 ? 4 : sizeof(hao_qmz_t)) + nw_ * 8 + nr4_ * 4 + B.n_codes + B.n_exc * sizeof(hao_exc_t);
-	}
-	if (ex && n) { HIP_TRY(cp(o_ex, O.exact.p, B.n_ol)); d.exact = a + o_ex; d.n_ol = B.n_ol; d.bytes += B.n_ol; }
-	if (ed && n) {
-		HIP_TRY(cp(o_edoff, O.ed_off.p, (n + 1) * 8)); HIP_TRY(cp(o_ederr, O.ed_err.p, B.ed_n)); HIP_TRY(cp(o_edpe, O.ed_pe.p, B.ed_n * 2));
-		hao_ed_delivery_t &e = B.ed_dl[s];
-		e.n_pairs = B.ed_n; e.ed_off = (const uint64_t*)(a + o_edoff); e.err = a + o_ederr; e.pe = (const uint16_t*)(a + o_edpe);
-		d.bytes += (n + 1) * 8 + B.ed_n * 3;
-		if (edref) { HIP_TRY(cp(o_edsum, O.ed_sum.p, B.n_ol * sizeof(hao_ed_ovlp_sum))); e.ovlp = (const hao_ed_ovlp_t*)(a + o_edsum); e.unresolved = B.ed_unres; d.bytes += B.n_ol * sizeof(hao_ed_ovlp_sum); }
-	}
-	if (tr && n) {
-		HIP_TRY(cp(o_troff, O.tr_off.p, (n + 1) * 8)); HIP_TRY(cp(o_trps, O.tr_ps.p, B.ed_n * 2)); HIP_TRY(cp(o_trnc, O.tr_ncig.p, B.ed_n * 2));
-		if (B.tr_ncig) HIP_TRY(cp(o_trcig, O.tr_cig.p, B.tr_ncig * 2));
-		hao_trace_delivery_t &t = B.tr_dl[s];
-		t.n_traced = B.tr_n; t.n_cigar = B.tr_ncig; t.cg_off = (const uint64_t*)(a + o_troff); t.ps = (const uint16_t*)(a + o_trps); t.n_cig = (const uint16_t*)(a + o_trnc); t.cigar = (const uint16_t*)(a + o_trcig);
-		d.bytes += (n + 1) * 8 + B.ed_n * 4 + B.tr_ncig * 2;
-	}
-	if (rsq && n) {
-		HIP_TRY(cp(o_rsov, O.rs_ovlp.p, B.n_ol * sizeof(hao_rs_ovlp))); HIP_TRY(cp(o_rsoff, O.rs_off.p, (B.n_ol + 1) * 8)); HIP_TRY(cp(o_rswin, O.rs_wins.p, B.rs_nw * sizeof(hao_rs_win)));
-		hao_rescue_delivery_t &r = B.rs_dl[s];
-		r.n_ol = B.n_ol; r.n_wins = B.rs_nw; r.n_rescued = B.rs_nres; r.ovlp = (const hao_rescue_ovlp_t*)(a + o_rsov); r.win_off = (const uint64_t*)(a + o_rsoff); r.wins = (const hao_rescue_win_t*)(a + o_rswin);
-		d.bytes += B.n_ol * sizeof(hao_rs_ovlp) + (B.n_ol + 1) * 8 + B.rs_nw * sizeof(hao_rs_win);
-	}
-	if (wlq && n) {
-		const uint64_t N = B.wl_cnt[0], E = B.wl_cnt[3];
-		HIP_TRY(cp(o_wloff, O.wl_woff.p, (B.n_ol + 1) * 8)); HIP_TRY(cp(o_wlwin, O.wl_wins.p, N * sizeof(hao_rs_win))); HIP_TRY(cp(o_wlcoff, O.wl_cigoff.p, (N + 1) * 8)); HIP_TRY(cp(o_wlcig, O.wl_cig.p, E * 2));
-		hao_wlist_delivery_t &w = B.wl_dl[s];
-		w.n_ol = B.n_ol; w.n_wins = N; w.n_cigar = E; w.n_swept = B.wl_cnt[1]; w.n_replace = B.wl_cnt[2]; w.n_untraced = B.wl_cnt[4];
-		w.win_off = (const uint64_t*)(a + o_wloff); w.wins = (const hao_wlist_win_t*)(a + o_wlwin); w.cig_off = (const uint64_t*)(a + o_wlcoff); w.cigars = (const uint16_t*)(a + o_wlcig);
-		d.bytes += (B.n_ol + 1) * 8 + N * sizeof(hao_rs_win) + (N + 1) * 8 + E * 2;
-	}
-	HIP_TRY(hipEventRecord(B.ev_done[s], B.copy_stream));
-	B.dl_pending[s] = true;
-	return HAO_OK;
-}
-
-static int hao_deliver_init(hao_ctx *c, hao_ctx::Batch &B)
-{
-	if (B.dl_ready) return HAO_OK;
-	HIP_TRY(hipStreamCreateWithFlags(&B.copy_stream, hipStreamNonBlocking));
-	for (int x = 0; x < 2; ++x) { HIP_TRY(hipEventCreate(&B.ev_ready[x])); HIP_TRY(hipEventCreate(&B.ev_done[x])); HIP_TRY(hipEventCreate(&B.ev_cstart[x])); }
-	if (c->device >= 0 && c->device < 64) B.arena_node = hao_arena_node_of[c->device];
-	B.dl_ready = true;
-	return HAO_OK;
-}
-
 // parts = 0: results stay in HBM (blocking API).  parts != 0 (hao_overlap_batch_async): the batch computes into output set `dl_seq & 1`, packs cl->list
 // into the wire format and queues the copy of everything asked for into that slot's pinned arena on the copy stream.
 static int hao_overlap_run(hao_ctx *c, uint64_t lo, uint64_t hi, const hao_pass_t &ps, uint32_t parts = 0, int *slot_out = nullptr)
@@ -612,12 +394,9 @@ static int hao_overlap_run(hao_ctx *c, uint64_t lo, uint64_t hi, const hao_pass_
 		if (slot_out) *slot_out = B.cur;
 	}
 	// the output set about to be written may still be feeding a copy (its previous async batch): wait for that copy, never for the other slot's
-	if (B.dl_ready && B.dl_pending[B.cur]) { const double t0_ = hao_now(); HIP_TRY(hipEventSynchronize(B.ev_done[B.cur])); B.dl_pending[B.cur] = false; B.t_evsync += hao_now() - t0_; }
-	if (parts) { memset(&B.dl[B.cur], 0, sizeof(hao_delivery_t)); B.dl[B.cur].rid_lo = lo; B.dl[B.cur].n_reads = n;
-		memset(&B.ed_dl[B.cur], 0, sizeof(hao_ed_delivery_t)); if (parts & HAO_DELIVER_ED) { B.ed_dl[B.cur].window = c->ded_window; B.ed_dl[B.cur].thre = c->ded_thre; B.ed_dl[B.cur].placement = c->ded_place; B.ed_dl[B.cur].e_rate = c->ded_place == HAO_PLACE_REF ? c->ded_erate : 0; }
-		memset(&B.tr_dl[B.cur], 0, sizeof(hao_trace_delivery_t)); B.tr_on[B.cur] = (parts & HAO_DELIVER_TRACE) != 0;
-		memset(&B.rs_dl[B.cur], 0, sizeof(hao_rescue_delivery_t)); B.rs_on[B.cur] = (parts & HAO_DELIVER_RESCUE) != 0;
-		memset(&B.wl_dl[B.cur], 0, sizeof(hao_wlist_delivery_t)); B.wl_on[B.cur] = (parts & HAO_DELIVER_WLIST) != 0; }
+	hao_ctx::Batch::Slot &S = B.slot[B.cur];
+	if (B.dl_ready && S.pending) { const double t0_ = hao_now(); HIP_TRY(hipEventSynchronize(S.ev_done)); S.pending = false; B.t_evsync += hao_now() - t0_; }
+	if (parts) S.begin(parts, lo, n, c);
 	if (n == 0) { B.n_anchor = B.n_groups = B.n_chains = B.n_cl = B.n_ol = B.n_fc = B.n_fcw = B.n_mz = 0; B.valid = true; return HAO_OK; }      // (an empty delivery: nothing to copy, the view stays zeroed)
 	// minimizer range of the batch (host knows the per-read offsets? keep a host copy once)
 	if (c->h_ix_mz_off.size() != c->n_reads + 1) {

@@ -147,18 +147,18 @@ int hao_deliver_wait(hao_ctx *c, int slot, hao_delivery_t *out)
 {
 	if (!c || !out || slot < 0 || slot > 1 || !c->batch || !c->batch->dl_ready) return HAO_EINVAL;
 	HIP_TRY(hipSetDevice(c->device));
-	hao_ctx::Batch &B = *c->batch;
-	if (B.dl_pending[slot]) { HIP_TRY(hipEventSynchronize(B.ev_done[slot])); B.dl_pending[slot] = false; float ms = 0; if (hipEventElapsedTime(&ms, B.ev_ready[slot], B.ev_done[slot]) == hipSuccess) B.dl[slot].copy_ms = ms;
+	hao_ctx::Batch::Slot &S = c->batch->slot[slot];
+	if (S.pending) { HIP_TRY(hipEventSynchronize(S.ev_done)); S.pending = false; float ms = 0; if (hipEventElapsedTime(&ms, S.ev_ready, S.ev_done) == hipSuccess) S.dl.copy_ms = ms;
 		// the rate of the copy itself: a big batch that crossed at less than 40 GB/s (a good arena gives 50 - 56 beside the next batch's kernels) gets its arena allocated again
 		// before the slot's next batch, with a timed copy into every NUMA node (batches of 256 MB and more: smaller ones pay per-copy overheads that say nothing about the arena) (once per slot; round 6 saw arenas that passed the probe at allocation and then copied at 30 GB/s for the whole run)
-		float cms = 0; const double mb_ = (double)B.dl[slot].bytes / 1e6;
-		if (hipEventElapsedTime(&cms, B.ev_cstart[slot], B.ev_done[slot]) == hipSuccess && cms > 0 && B.arena_retry[slot] < 1 && ((mb_ >= 256.0 && mb_ / cms < 40.0) || (c->sw.arena_probe && mb_ > 0))) {
-			B.arena_bad[slot] = true; ++B.arena_retry[slot];
+		float cms = 0; const double mb_ = (double)S.dl.bytes / 1e6;
+		if (hipEventElapsedTime(&cms, S.ev_cstart, S.ev_done) == hipSuccess && cms > 0 && S.arena_retry < 1 && ((mb_ >= 256.0 && mb_ / cms < 40.0) || (c->sw.arena_probe && mb_ > 0))) {
+			S.arena_bad = true; ++S.arena_retry;
 			fprintf(stderr, "[hao] delivery arena %d: a batch of %.0f MB was copied at %.1f GB/s; the arena is allocated again for the slot's next batch, every NUMA node tried\n", slot, mb_, mb_ / cms);
 		}
 	}
-	if (B.dl[slot].n_ol && B.dl[slot].fc_off) ((uint64_t*)B.dl[slot].fc_off)[B.dl[slot].n_ol] = B.dl[slot].n_fc;      // end of the last cigar: a host-side word next to the region the copy wrote, set once the copy has landed
-	*out = B.dl[slot];
+	if (S.dl.n_ol && S.dl.fc_off) ((uint64_t*)S.dl.fc_off)[S.dl.n_ol] = S.dl.n_fc;      // end of the last cigar: a host-side word next to the region the copy wrote, set once the copy has landed
+	*out = S.dl;
 	return HAO_OK;
 }
 
@@ -372,15 +372,21 @@ int hao_fetch_trace_grid(hao_ctx *c, hao_ed_task_t *tasks, hao_trace_result_t *r
 	return done(HAO_OK);
 }
 
-int hao_deliver_trace(hao_ctx *c, int slot, hao_trace_delivery_t *out)
+// The view of one more part of a waited-for slot: the one body of hao_deliver_ed, hao_deliver_trace, hao_deliver_rescue and hao_deliver_wlist
+// (a template: C++ linkage inside this file's extern "C")
+extern "C++" {
+template <class V> static int hao_deliver_part(hao_ctx *c, int slot, V *out, V hao_ctx::Batch::Slot::*view, uint32_t part, const char *fn, const char *flag)
 {
 	if (!c || !out || slot < 0 || slot > 1 || !c->batch || !c->batch->dl_ready) return HAO_EINVAL;
-	hao_ctx::Batch &B = *c->batch;
-	if (!B.tr_on[slot]) { hao_set_err(c, "hao_deliver_trace: the slot's batch did not ask for HAO_DELIVER_TRACE"); return HAO_EINVAL; }
-	if (B.dl_pending[slot]) { hao_set_err(c, "hao_deliver_trace: hao_deliver_wait has not been called on the slot"); return HAO_EINVAL; }
-	*out = B.tr_dl[slot];
+	const hao_ctx::Batch::Slot &S = c->batch->slot[slot];
+	if (!(S.parts & part)) { hao_set_err(c, std::string(fn) + ": the slot's batch did not ask for " + flag); return HAO_EINVAL; }
+	if (S.pending) { hao_set_err(c, std::string(fn) + ": hao_deliver_wait has not been called on the slot"); return HAO_EINVAL; }
+	*out = S.*view;
 	return HAO_OK;
 }
+}
+
+int hao_deliver_trace(hao_ctx *c, int slot, hao_trace_delivery_t *out) { return hao_deliver_part(c, slot, out, &hao_ctx::Batch::Slot::tr, HAO_DELIVER_TRACE, "hao_deliver_trace", "HAO_DELIVER_TRACE"); }
 
 // pure function of the three views of a delivered batch: read rid's pairs and distance-only results as hao_unpack_ed gives them, with the traced part added
 uint64_t hao_unpack_trace(const hao_trace_delivery_t *t, const hao_ed_delivery_t *e, const hao_delivery_t *d, const uint32_t *len, uint64_t rid,
@@ -546,15 +552,7 @@ int hao_fetch_wlist(hao_ctx *c, uint64_t rid, uint64_t *n_ol, const uint64_t **w
 	return HAO_OK;
 }
 
-int hao_deliver_wlist(hao_ctx *c, int slot, hao_wlist_delivery_t *out)
-{
-	if (!c || !out || slot < 0 || slot > 1 || !c->batch || !c->batch->dl_ready) return HAO_EINVAL;
-	hao_ctx::Batch &B = *c->batch;
-	if (!B.wl_on[slot]) { hao_set_err(c, "hao_deliver_wlist: the slot's batch did not ask for HAO_DELIVER_WLIST"); return HAO_EINVAL; }
-	if (B.dl_pending[slot]) { hao_set_err(c, "hao_deliver_wlist: hao_deliver_wait has not been called on the slot"); return HAO_EINVAL; }
-	*out = B.wl_dl[slot];
-	return HAO_OK;
-}
+int hao_deliver_wlist(hao_ctx *c, int slot, hao_wlist_delivery_t *out) { return hao_deliver_part(c, slot, out, &hao_ctx::Batch::Slot::wl, HAO_DELIVER_WLIST, "hao_deliver_wlist", "HAO_DELIVER_WLIST"); }
 
 uint64_t hao_unpack_wlist(const hao_delivery_t *d, const hao_ed_delivery_t *e, const hao_rescue_delivery_t *r, const hao_wlist_delivery_t *w, const uint32_t *len, uint64_t rid,
 		uint64_t *win_off, hao_wlist_win_t *wins, uint64_t *cig_off, uint16_t *cigars, uint64_t cap_ovlp, uint64_t cap_wins, uint64_t cap_cigars)
@@ -599,15 +597,7 @@ int hao_rescue_task(const hao_ovlp_t *z, uint32_t win, uint32_t window, int64_t 
 	return hao_rescue_pair(*z, win, window, toff, tab, target_len, out) ? 1 : 0;
 }
 
-int hao_deliver_rescue(hao_ctx *c, int slot, hao_rescue_delivery_t *out)
-{
-	if (!c || !out || slot < 0 || slot > 1 || !c->batch || !c->batch->dl_ready) return HAO_EINVAL;
-	hao_ctx::Batch &B = *c->batch;
-	if (!B.rs_on[slot]) { hao_set_err(c, "hao_deliver_rescue: the slot's batch did not ask for HAO_DELIVER_RESCUE"); return HAO_EINVAL; }
-	if (B.dl_pending[slot]) { hao_set_err(c, "hao_deliver_rescue: hao_deliver_wait has not been called on the slot"); return HAO_EINVAL; }
-	*out = B.rs_dl[slot];
-	return HAO_OK;
-}
+int hao_deliver_rescue(hao_ctx *c, int slot, hao_rescue_delivery_t *out) { return hao_deliver_part(c, slot, out, &hao_ctx::Batch::Slot::rs, HAO_DELIVER_RESCUE, "hao_deliver_rescue", "HAO_DELIVER_RESCUE"); }
 
 uint64_t hao_unpack_rescue(const hao_delivery_t *d, const hao_ed_delivery_t *e, const hao_rescue_delivery_t *r, const uint32_t *len, uint64_t rid,
 		hao_rescue_ovlp_t *ovlp, uint64_t *win_off, hao_rescue_win_t *wins, uint64_t cap_ovlp, uint64_t cap_wins)
@@ -640,15 +630,7 @@ uint64_t hao_unpack_rescue(const hao_delivery_t *d, const hao_ed_delivery_t *e, 
 	return n;
 }
 
-int hao_deliver_ed(hao_ctx *c, int slot, hao_ed_delivery_t *out)
-{
-	if (!c || !out || slot < 0 || slot > 1 || !c->batch || !c->batch->dl_ready) return HAO_EINVAL;
-	hao_ctx::Batch &B = *c->batch;
-	if (!B.ed_dl[slot].window) { hao_set_err(c, "hao_deliver_ed: the slot's batch did not ask for HAO_DELIVER_ED"); return HAO_EINVAL; }
-	if (B.dl_pending[slot]) { hao_set_err(c, "hao_deliver_ed: hao_deliver_wait has not been called on the slot"); return HAO_EINVAL; }
-	*out = B.ed_dl[slot];
-	return HAO_OK;
-}
+int hao_deliver_ed(hao_ctx *c, int slot, hao_ed_delivery_t *out) { return hao_deliver_part(c, slot, out, &hao_ctx::Batch::Slot::ed, HAO_DELIVER_ED, "hao_deliver_ed", "HAO_DELIVER_ED"); }
 
 // pure function of the two views of a delivered batch: read rid's grid pairs rebuilt from its delivered overlaps with the device's own hao_grid_pair, in the
 // device's order (grid window, then position in ol->list), and their results widened

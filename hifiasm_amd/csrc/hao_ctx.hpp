@@ -108,7 +108,7 @@ struct hao_switches {
 			if (in_kv(v, "fc_raw_every", x)) fc_raw_every = (int)x;       // every n-th overlap's fake cigar travels raw (the fallback of the packed wire form)
 			if (in_kv(v, "exc_every", x)) exc_every = (int)x;             // every n-th hit of a chain travels verbatim (the exception list)
 			if (in_kv(v, "qmz_raw", x)) qmz_raw = x != 0;                   // the delivered minimizer tables in their 8-byte form whatever the read lengths (the form of batches with a read of 65 536 bases or more)
-			if (in_kv(v, "arena_probe", x)) arena_probe = x != 0;           // the delivery arenas' placement probe (hao_deliver_enqueue) whatever their size and rate
+			if (in_kv(v, "arena_probe", x)) arena_probe = x != 0;           // the delivery arenas' placement probe (hao_arena_ensure) whatever their size and rate
 			if (in_kv(v, "ft_chunk_slots", x)) ft_chunk_slots = (long long)x;      // k-mer slots hashed per chunk of reads in ha_ft_gen's pass mode
 			if (in_kv(v, "gather_chunk", x)) gather_chunk = std::max<unsigned long long>(x, 64);      // bytes a rank contributes per exchange of hao_dist_gather_reads (default 64 MB: a few KB walk the multi-chunk path on a small read set)
 		}
