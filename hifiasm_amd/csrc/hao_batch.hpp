@@ -52,8 +52,6 @@ struct hao_ctx::Batch {
 	double t_evsync = 0, t_enq = 0, t_alloc = 0, t_s1 = 0, t_s2 = 0, t_s3 = 0, t_run = 0, t_pre = 0; uint64_t t_n = 0, t_nrun = 0;      // host-side time spent in the delivery plumbing (HAO_DBG_PRINT=dl)
 	uint64_t ed_unres = 0;      // HAO_DELIVER_ED in reference placement: windows of the batch whose start resolved to no cigar entry
 	DevBuf<uint64_t> ed_nwin, ed_wbase, ed_wcnt, ed_woff; DevBuf<hao_ed_pair> ed_pairs; uint64_t ed_n = 0;      // HAO_DELIVER_ED scratch (compute stream only: not per output set); ed_n = pairs of the batch
-	uint64_t wl_cnt[5] = { 0, 0, 0, 0, 0 };      // HAO_DELIVER_WLIST: hao_al_wlist's five counts of the batch
-	uint64_t rs_nw = 0, rs_nres = 0, rs_wc = 0;      // HAO_DELIVER_RESCUE: window records and rescued windows of the batch, its covered windows
 	uint64_t tr_n = 0, tr_ncig = 0;      // HAO_DELIVER_TRACE: traced pairs and cigar entries of the batch
 	uint64_t dl_seq = 0, n_exc = 0; uint32_t dl_parts = 0; bool exact_valid = false; std::vector<uint8_t> h_exact;
 	// host copies for fetch
@@ -198,14 +196,14 @@ static int hao_ed_grid_pairs(hao_ctx *c, const char *who, uint32_t place, uint32
 int hao_al_ed_resident(hao_ctx *c, uint64_t n_tasks, uint32_t nword);      // (hao_f3.hip)
 static int hao_ed_grid_run(hao_ctx *c, uint32_t wl, uint32_t thre, uint64_t *n_tasks)
 {
-	hao_ctx::Batch &B = *c->batch; *n_tasks = 0; c->al_grid_n = 0;
+	hao_ctx::Batch &B = *c->batch; *n_tasks = 0; c->win.on_grid(0);      // (the scratch is this call's from here on, whatever becomes of it)
 	{ HAO_STAGE_VIEW(c, V, "hao_window_ed_grid needs the bases of both reads"); (void)V; }
 	if (wl == 0 || thre > HAO_ED_MAX_THRE) { hao_set_err(c, "hao_window_ed_grid: window length 0 or threshold beyond the widest band"); return HAO_EINVAL; }
 	const uint32_t nword = (2 * thre + 1 + 63) / 64;
 	if (B.n == 0 || B.n_ol == 0) return HAO_OK;
 	hao_grid_list L;
 	if (int rc = hao_ed_grid_pairs(c, "hao_window_ed_grid", HAO_PLACE_DIAG, wl, thre, nword, nullptr, &c->al_task, nullptr, &L)) return rc;
-	*n_tasks = L.T; c->al_grid_n = L.T;
+	*n_tasks = L.T; c->win.on_grid(L.T);
 	return L.T ? hao_al_ed_resident(c, L.T, nword) : HAO_OK;
 }
 
@@ -213,10 +211,10 @@ static int hao_ed_grid_run(hao_ctx *c, uint32_t wl, uint32_t thre, uint64_t *n_t
 // the per-overlap summaries (c->rf_sum) and the count of unresolved windows
 static int hao_ed_ref_run(hao_ctx *c, uint32_t wl, double e_rate, uint64_t *n_tasks, uint64_t *unresolved)
 {
-	hao_ctx::Batch &B = *c->batch; *n_tasks = 0; if (unresolved) *unresolved = 0; c->al_grid_n = 0; c->rf_valid = false; c->rf_hvalid = false; c->rf_unres = 0; c->rs_valid = false; c->wl_valid = false; c->rf_T = 0;
+	hao_ctx::Batch &B = *c->batch; *n_tasks = 0; if (unresolved) *unresolved = 0; c->win.on_ref_begin(WinResident::ED); c->rf_unres = 0; c->rs_wc = 0;
 	{ HAO_STAGE_VIEW(c, V, "hao_window_ed_ref needs the bases of both reads"); (void)V; }
 	if (!hao_ed_ref_args_ok(wl, e_rate)) { hao_set_err(c, "hao_window_ed_ref: window length 0, window + 62 beyond 16 bits, or e_rate outside (0, 1)"); return HAO_EINVAL; }
-	if (B.n == 0 || B.n_ol == 0) { c->rf_valid = true; return HAO_OK; }
+	if (B.n == 0 || B.n_ol == 0) { c->win.on_ref_done(WinResident::ED); return HAO_OK; }
 	if (B.n_ol >= (1ULL << 32)) { hao_set_err(c, "hao_window_ed_ref: more than 2^32 overlaps in one batch"); return HAO_EUNSUPP; }
 	if (c->rf_tab_wl != wl || c->rf_tab_erate != e_rate) { c->rf_tab_wl = 0; if (int rc = hao_ed_ref_upload(c, wl, e_rate, c->rf_tab)) return rc; c->rf_tab_wl = wl; c->rf_tab_erate = e_rate; }
 	hao_ctx::Batch::OutSet &O = B.O();
@@ -224,49 +222,74 @@ static int hao_ed_ref_run(hao_ctx *c, uint32_t wl, double e_rate, uint64_t *n_ta
 	if (int rc = hao_ed_grid_pairs(c, "hao_window_ed_ref", HAO_PLACE_REF, wl, 0, 1, c->rf_tab.p, &c->al_task, &c->rf.pairs, &L)) return rc;
 	HIP_TRY(c->rf_sum.reserve(B.n_ol + 1));
 	const uint64_t T = L.T;
-	*n_tasks = T; c->al_grid_n = T; c->rf_T = T; c->rf_unres = L.UR; if (unresolved) *unresolved = L.UR;
+	*n_tasks = T; c->rf_unres = L.UR; c->rs_wc = L.Wc; if (unresolved) *unresolved = L.UR;
 	if (T) {
 		if (int rc = hao_al_ed_resident(c, T, 1)) return rc;
 		hipLaunchKernelGGL(ed_ref_scatter_kernel, dim3((unsigned)((T + 255) / 256)), dim3(256), 0, c->stream, O.ol_out.p, c->rf.pairs.p, c->al_res.p, T, wl, L.A.win_off, c->rf.werr.p); HAO_CHECK_LAUNCH();
 	}
 	hipLaunchKernelGGL(ed_ref_summary_kernel, dim3((unsigned)((B.n_ol + 255) / 256)), dim3(256), 0, c->stream, O.ol_out.p, B.n_ol, wl, L.A.win_off, c->rf.werr.p, c->rf_sum.p); HAO_CHECK_LAUNCH();
-	c->rf_valid = true;
+	c->win.on_ref_done(WinResident::ED, T);
 	return HAO_OK;
 }
 
-// hao_window_rescue_ref: the rescue stage (hao_rescue.cuh) over what hao_ed_ref_run left - the CSR, shifts and error bytes in c->rf, the pair list and the
-// results per pair in c->al_res
-int hao_al_rescue(hao_ctx *c, const hao_ovlp_t *ol, uint64_t n_ol, uint32_t wl, hao_ref_args RA, const uint8_t *werr, const hao_ed_pair *pairs, const hao_ed_result_t *res, uint64_t n_pairs, uint64_t n_slots,
-		const uint8_t *err8 = nullptr, const uint16_t *pe16 = nullptr, hao_rs_ovlp *out = nullptr, DevBuf<uint64_t> *d_off = nullptr, DevBuf<hao_rs_win> *d_wins = nullptr, uint64_t *n_wins = nullptr);      // (hao_f3.hip)
+// ---- the rescue stage (hao_rescue.cuh) and the window lists (hao_wlist.cuh): one runner each under the blocking calls and the streamed parts ----
+int hao_al_rescue(hao_ctx *c, const hao_ref_io &io);      // (hao_f3.hip)
+int hao_al_wlist(hao_ctx *c, const hao_ref_io &io);
+// the batch as the blocking chain has it: hao_ed_ref_run's table, pair list and results per pair (c->al_res); results into the context's own buffers
+static hao_ref_io hao_ref_io_ctx(hao_ctx *c)
+{
+	hao_ctx::Batch &B = *c->batch; hao_ref_io io;
+	io.ol = B.O().ol_out.p; io.n_ol = B.n_ol; io.wl = c->rf_tab_wl; io.tab = c->rf_tab.p; io.pairs = c->rf.pairs.p; io.n_pairs = c->win.scratch_pairs(); io.n_slots = c->rs_wc;
+	io.res = c->al_res.p; io.err8 = nullptr; io.pe16 = nullptr;
+	io.rs_ovlp = &c->rs.ovlp; io.rs_off = &c->rs.off; io.rs_wins = &c->rs.wins; io.wl_woff = &c->wl.woff; io.wl_wins = &c->wl.wins; io.wl_cigoff = &c->wl.cig_off; io.wl_cig = &c->wl.cig;
+	return io;
+}
+// the batch as the streamed parts have it: hao_ed_deliver_run's table, pair list and compact records; results into the current output set (its copy runs under the next batch's compute, which reuses the scratch in c->rs / c->wl)
+static hao_ref_io hao_ref_io_out(hao_ctx *c)
+{
+	hao_ctx::Batch &B = *c->batch; hao_ctx::Batch::OutSet &O = B.O(); hao_ref_io io;
+	io.ol = O.ol_out.p; io.n_ol = B.n_ol; io.wl = c->ded_window; io.tab = c->ded_tab.p; io.pairs = B.ed_pairs.p; io.n_pairs = B.ed_n; io.n_slots = c->rs_wc;
+	io.res = nullptr; io.err8 = O.ed_err.p; io.pe16 = O.ed_pe.p;
+	io.rs_ovlp = &O.rs_ovlp; io.rs_off = &O.rs_off; io.rs_wins = &O.rs_wins; io.wl_woff = &O.wl_woff; io.wl_wins = &O.wl_wins; io.wl_cigoff = &O.wl_cigoff; io.wl_cig = &O.wl_cig;
+	return io;
+}
+// the rescue stage over io: per-overlap results, the records compacted on the device into a CSR by overlap (a batch without overlaps: one offset, 0), the counts in c->rs_*
+static int hao_rescue_run(hao_ctx *c, const hao_ref_io &io)
+{
+	c->rs_slots = c->rs_rounds = c->rs_active = c->rs_total = c->rs_nw = 0;
+	HIP_TRY(io.rs_ovlp->reserve(io.n_ol + 1)); HIP_TRY(io.rs_off->reserve(io.n_ol + 2)); HIP_TRY(io.rs_wins->reserve(1));
+	if (io.n_ol == 0) { HIP_TRY(hipMemsetAsync(io.rs_off->p, 0, 8, c->stream)); return HAO_OK; }
+	return hao_al_rescue(c, io);
+}
+// the window lists over io and the rescue stage's results in it (which they do not change); the five counts in c->wl_out.  Two count reads: the stage's sizes, and its totals
+static int hao_wlist_run(hao_ctx *c, const hao_ref_io &io)
+{
+	for (int k = 0; k < 5; ++k) c->wl_out[k] = 0;
+	HIP_TRY(io.wl_woff->reserve(io.n_ol + 2)); HIP_TRY(io.wl_wins->reserve(1)); HIP_TRY(io.wl_cigoff->reserve(2)); HIP_TRY(io.wl_cig->reserve(1));
+	if (io.n_ol == 0 || io.n_slots == 0) { HIP_TRY(hipMemsetAsync(io.wl_woff->p, 0, (io.n_ol + 1) * 8, c->stream)); HIP_TRY(hipMemsetAsync(io.wl_cigoff->p, 0, 8, c->stream)); return HAO_OK; }
+	return hao_al_wlist(c, io);
+}
+
+// hao_window_rescue_ref: over what hao_ed_ref_run left - the CSR, shifts and error bytes in c->rf, the pair list, and the results per pair in the shared scratch
 static int hao_rescue_ref_run(hao_ctx *c, uint64_t *n_rescued)
 {
-	hao_ctx::Batch &B = *c->batch; *n_rescued = 0; c->rs_valid = false; c->rs_hvalid = false; c->wl_valid = false;
-	if (!c->rf_valid || c->al_grid_n != c->rf_T) { hao_set_err(c, "hao_window_rescue_ref: hao_window_ed_ref has not run on this batch (or another window-alignment call has run since)"); return HAO_EINVAL; }
+	*n_rescued = 0; c->win.on_ref_begin(WinResident::RESCUE);
+	if (!c->win.ref_input_resident()) { hao_set_err(c, "hao_window_rescue_ref: hao_window_ed_ref has not run on this batch (or another window-alignment call has run since)"); return HAO_EINVAL; }
 	{ HAO_STAGE_VIEW(c, V, "hao_window_rescue_ref needs the bases of both reads"); (void)V; }      // (the gathered store has gone since hao_window_ed_ref)
-	if (B.n == 0 || B.n_ol == 0) { c->rs_total = c->rs_rounds = c->rs_active = c->rs_slots = 0; c->rs_valid = true; return HAO_OK; }
-	hao_ref_args A; A.win_off = c->rf.woff.p; A.shift = c->rf.shift.p; A.tab = c->rf_tab.p;
-	uint64_t Wc = 0; HIP_TRY(hipMemcpyAsync(&Wc, c->rf.woff.p + B.n_ol, 8, hipMemcpyDeviceToHost, c->stream)); HIP_TRY(hipStreamSynchronize(c->stream));
-	if (int rc = hao_al_rescue(c, B.O().ol_out.p, B.n_ol, c->rf_tab_wl, A, c->rf.werr.p, c->rf.pairs.p, c->al_res.p, c->rf_T, Wc)) return rc;
-	*n_rescued = c->rs_total; c->rs_wc = Wc; c->rs_valid = true;
+	if (int rc = hao_rescue_run(c, hao_ref_io_ctx(c))) return rc;
+	*n_rescued = c->rs_total; c->win.on_ref_done(WinResident::RESCUE);
 	return HAO_OK;
 }
 
-// hao_window_wlist_ref: the window lists (hao_wlist.cuh) over what hao_rescue_ref_run left - the CSR, shifts and error bytes in c->rf, pe per slot, the rescue
-// records and the verdicts in c->rs, none of which it changes
-int hao_al_wlist(hao_ctx *c, const hao_ovlp_t *ol, uint64_t n_ol, uint32_t wl, hao_ref_args RA, const uint8_t *werr, const hao_rs_ovlp *ov, uint64_t n_slots, uint64_t out[5],
-		DevBuf<uint64_t> &o_woff, DevBuf<hao_rs_win> &o_wins, DevBuf<uint64_t> &o_cigoff, DevBuf<uint16_t> &o_cig);      // (hao_f3.hip)
+// hao_window_wlist_ref: over what hao_ed_ref_run and hao_rescue_ref_run left
 static int hao_wlist_ref_run(hao_ctx *c, uint64_t out[5])
 {
-	hao_ctx::Batch &B = *c->batch; c->wl_valid = false; c->wl_hvalid = false;
-	for (int k = 0; k < 5; ++k) out[k] = 0;
+	for (int k = 0; k < 5; ++k) out[k] = 0; c->win.on_ref_begin(WinResident::WLIST);
 	{ HAO_STAGE_VIEW(c, V, "hao_window_wlist_ref needs the bases of both reads"); (void)V; }
-	if (!c->rf_valid || !c->rs_valid || c->al_grid_n != c->rf_T) { hao_set_err(c, "hao_window_wlist_ref: hao_window_ed_ref and hao_window_rescue_ref have not both run on this batch (or another window-alignment call has run since)"); return HAO_EINVAL; }
-	if (B.n && B.n_ol && c->rs_wc) {
-		hao_ref_args A; A.win_off = c->rf.woff.p; A.shift = c->rf.shift.p; A.tab = c->rf_tab.p;
-		if (int rc = hao_al_wlist(c, B.O().ol_out.p, B.n_ol, c->rf_tab_wl, A, c->rf.werr.p, c->rs.ovlp.p, c->rs_wc, out, c->wl.woff, c->wl.wins, c->wl.cig_off, c->wl.cig)) return rc;
-	}
-	for (int k = 0; k < 5; ++k) c->wl_out[k] = out[k];
-	c->wl_valid = true;
+	if (!c->win.wlist_input_resident()) { hao_set_err(c, "hao_window_wlist_ref: hao_window_ed_ref and hao_window_rescue_ref have not both run on this batch (or another window-alignment call has run since)"); return HAO_EINVAL; }
+	if (int rc = hao_wlist_run(c, hao_ref_io_ctx(c))) return rc;
+	for (int k = 0; k < 5; ++k) out[k] = c->wl_out[k];
+	c->win.on_ref_done(WinResident::WLIST);
 	return HAO_OK;
 }
 
@@ -289,7 +312,7 @@ static int hao_ed_deliver_run(hao_ctx *c)
 	HIP_TRY(O.ed_off.reserve(n + 2)); if (ref) HIP_TRY(O.ed_sum.reserve(B.n_ol + 1));
 	hao_grid_list L;
 	if (int rc = hao_ed_grid_pairs(c, "HAO_DELIVER_ED", c->ded_place, wl, thre, nword, c->ded_tab.p, nullptr, &B.ed_pairs, &L)) return rc;
-	const uint64_t T = L.T; B.ed_unres = L.UR; if (ref) B.rs_wc = L.Wc;
+	const uint64_t T = L.T; B.ed_unres = L.UR; c->rs_wc = L.Wc;
 	HIP_TRY(O.ed_err.reserve(T + 64)); HIP_TRY(O.ed_pe.reserve(T + 64));
 	hipLaunchKernelGGL(ed_read_off_kernel, dim3((unsigned)((n + 256) / 256)), dim3(256), 0, c->stream, L.wbase, L.woff, n, O.ed_off.p); HAO_CHECK_LAUNCH();
 	c->timer.mark("ed_grid");
@@ -320,47 +343,17 @@ static int hao_trace_deliver_run(hao_ctx *c)
 	return HAO_OK;
 }
 
-// HAO_DELIVER_RESCUE: the rescue stage over the slots, pairs and records HAO_DELIVER_ED has just written in reference placement (c->rf: CSR, shifts, error
-// bytes; the output set's err / pe per pair), into the output set's own buffers - the copy of this batch runs under the next batch's compute, which reuses
-// the stage's scratch in c->rs
-static int hao_rescue_deliver_run(hao_ctx *c)
-{
-	hao_ctx::Batch &B = *c->batch; hao_ctx::Batch::OutSet &O = B.O();
-	B.rs_nw = 0; B.rs_nres = 0;
-	HIP_TRY(O.rs_ovlp.reserve(B.n_ol + 1)); HIP_TRY(O.rs_off.reserve(B.n_ol + 2)); HIP_TRY(O.rs_wins.reserve(1));
-	if (B.n_ol == 0) { HIP_TRY(hipMemsetAsync(O.rs_off.p, 0, 8, c->stream)); c->timer.mark("rescue"); return HAO_OK; }
-	hao_ref_args A; A.win_off = c->rf.woff.p; A.shift = c->rf.shift.p; A.tab = c->ded_tab.p;
-	if (int rc = hao_al_rescue(c, O.ol_out.p, B.n_ol, c->ded_window, A, c->rf.werr.p, B.ed_pairs.p, nullptr, B.ed_n, B.rs_wc, O.ed_err.p, O.ed_pe.p, O.rs_ovlp.p, &O.rs_off, &O.rs_wins, &B.rs_nw)) return rc;
-	B.rs_nres = c->rs_total;
-	c->timer.mark("rescue");
-	return HAO_OK;
-}
-
-// HAO_DELIVER_WLIST: the window lists over what the batch's ED and rescue stages have just left (c->rf, c->rs, the output set's verdicts), into the output set's
-// own buffers.  Two count reads: the stage's sizes, and its totals, which size the arena part
-static int hao_wlist_deliver_run(hao_ctx *c)
-{
-	hao_ctx::Batch &B = *c->batch; hao_ctx::Batch::OutSet &O = B.O();
-	for (int k = 0; k < 5; ++k) B.wl_cnt[k] = 0;
-	HIP_TRY(O.wl_woff.reserve(B.n_ol + 2)); HIP_TRY(O.wl_wins.reserve(1)); HIP_TRY(O.wl_cigoff.reserve(2)); HIP_TRY(O.wl_cig.reserve(1));
-	if (B.n_ol == 0 || B.rs_wc == 0) { HIP_TRY(hipMemsetAsync(O.wl_woff.p, 0, (B.n_ol + 1) * 8, c->stream)); HIP_TRY(hipMemsetAsync(O.wl_cigoff.p, 0, 8, c->stream)); c->timer.mark("wlist"); return HAO_OK; }
-	hao_ref_args A; A.win_off = c->rf.woff.p; A.shift = c->rf.shift.p; A.tab = c->ded_tab.p;
-	if (int rc = hao_al_wlist(c, O.ol_out.p, B.n_ol, c->ded_window, A, c->rf.werr.p, O.rs_ovlp.p, B.rs_wc, B.wl_cnt, O.wl_woff, O.wl_wins, O.wl_cigoff, O.wl_cig)) return rc;
-	c->timer.mark("wlist");
-	return HAO_OK;
-}
-
 // hao_window_trace_grid: the grid pairs of the current batch (hao_window_ed_grid's), their distance-only alignment (the delivery path's kernel, into the
 // context's own buffers) and the traced stage; everything stays resident for hao_fetch_trace_grid.  out: pairs, traced pairs, cigar entries, aligned but untraced pairs.
 static int hao_trace_grid_run(hao_ctx *c, uint32_t wl, uint32_t thre, uint64_t out[4])
 {
 	hao_ctx::Batch &B = *c->batch; hao_ctx::Batch::OutSet &O = B.O(); const uint64_t n = B.n;
-	c->tg_valid = false; out[0] = out[1] = out[2] = out[3] = 0;
+	c->win.on_trace_grid(false); out[0] = out[1] = out[2] = out[3] = 0;
 	{ HAO_STAGE_VIEW(c, V, "hao_window_trace_grid needs the bases of both reads"); (void)V; }
 	if (wl == 0 || thre > HAO_ED_MAX_THRE || (uint64_t)wl + 2 * (uint64_t)thre >= 0xffff) { hao_set_err(c, "hao_window_trace_grid: window length 0, threshold beyond the widest band, or window + 2 thre beyond 16 bits"); return HAO_EINVAL; }
 	const uint32_t nword = (2 * thre + 1 + 63) / 64;
 	c->tg_wl = wl; c->tg_thre = thre; c->tg_n = c->tg_nsel = c->tg_ncig = c->tg_nuntr = 0;
-	if (n == 0 || B.n_ol == 0) { c->tg_valid = true; return HAO_OK; }
+	if (n == 0 || B.n_ol == 0) { c->win.on_trace_grid(true); return HAO_OK; }
 	if (B.n_ol >= (1ULL << 32)) { hao_set_err(c, "hao_window_trace_grid: more than 2^32 overlaps in one batch"); return HAO_EUNSUPP; }
 	hao_grid_list L;      // (the pair list as the delivery path forms it, into the context's own list)
 	if (int rc = hao_ed_grid_pairs(c, "hao_window_trace_grid", HAO_PLACE_DIAG, wl, thre, nword, nullptr, nullptr, &c->tg_pairs, &L)) return rc;
@@ -371,8 +364,22 @@ static int hao_trace_grid_run(hao_ctx *c, uint32_t wl, uint32_t thre, uint64_t o
 	c->timer.mark("ed_align");
 	uint64_t nt = 0, nc = 0, nu = 0;
 	if (int rc = hao_al_trace_grid(c, O.ol_out.p, c->tg_pairs.p, T, wl, thre, c->tg_err.p, c->tg_ps.p, c->tg_ncig16.p, c->tg_cig, &nt, &nc, &nu)) return rc;
-	c->tg_n = T; c->tg_nsel = nt; c->tg_ncig = nc; c->tg_nuntr = nu; c->tg_valid = true;
+	c->tg_n = T; c->tg_nsel = nt; c->tg_ncig = nc; c->tg_nuntr = nu; c->win.on_trace_grid(true);
 	out[0] = T; out[1] = nt; out[2] = nc; out[3] = nu;
+	return HAO_OK;
+}
+
+// The one body of the blocking window stages over the resident batch (include/hao.h: hao_window_ed_ref, hao_window_rescue_ref, hao_window_wlist_ref, hao_window_trace_grid): view, device, timer, the stage, its end awaited, the stage times collected
+template <class Run> static int hao_window_stage(hao_ctx *c, const char *mark, Run run)
+{
+	if (!c->batch || !c->batch->valid) return HAO_EINVAL;
+	if (int rc = hao_view_refresh(c)) return rc;
+	HIP_TRY(hipSetDevice(c->device));
+	c->timer.begin(c->stream);
+	if (int rc = run()) return rc;
+	HIP_TRY(hipStreamSynchronize(c->stream));
+	if (mark) c->timer.mark(mark);
+	c->timer.collect(c->stage_ms);
 	return HAO_OK;
 }
 
@@ -385,7 +392,7 @@ static int hao_overlap_run(hao_ctx *c, uint64_t lo, uint64_t hi, const hao_pass_
 	if (!c->has_pt) { hao_set_err(c, "hao_pt_gen must run before hao_overlap_batch"); return HAO_EINVAL; }
 	if (!c->batch) c->batch = new hao_ctx::Batch();
 	hao_ctx::Batch &B = *c->batch; const double t_run0 = hao_now();
-	c->al_grid_n = 0; c->tg_valid = false; c->rf_valid = false; c->rs_valid = false; c->wl_valid = false;      // (the window-alignment grid of the previous batch's overlaps is stale)
+	c->win.on_new_batch();      // (the window-alignment results of the previous batch's overlaps are stale)
 	B.valid = false; B.host_valid = false; B.cl_valid = false; B.exact_valid = false; B.h_exact.clear(); B.lo = lo; B.n = hi - lo; B.dl_parts = parts; B.n_exc = 0;
 	const uint64_t n = B.n;
 	if (parts) {
@@ -743,8 +750,9 @@ static int hao_overlap_run(hao_ctx *c, uint64_t lo, uint64_t hi, const hao_pass_
 	if (parts & HAO_DELIVER_EXACT) { if (int rc = hao_exact_run(c)) return rc; }
 	if (parts & HAO_DELIVER_ED) { if (int rc = hao_ed_deliver_run(c)) return rc; }
 	if (parts & HAO_DELIVER_TRACE) { if (int rc = hao_trace_deliver_run(c)) return rc; }
-	if (parts & HAO_DELIVER_RESCUE) { if (int rc = hao_rescue_deliver_run(c)) return rc; }
-	if (parts & HAO_DELIVER_WLIST) { if (int rc = hao_wlist_deliver_run(c)) return rc; }
+	// HAO_DELIVER_RESCUE / HAO_DELIVER_WLIST: the blocking calls' runners over what HAO_DELIVER_ED has just left, into the output set; their counts (c->rs_nw, c->rs_total, c->wl_out) size the arena parts
+	if (parts & HAO_DELIVER_RESCUE) { if (int rc = hao_rescue_run(c, hao_ref_io_out(c))) return rc; c->timer.mark("rescue"); }
+	if (parts & HAO_DELIVER_WLIST) { if (int rc = hao_wlist_run(c, hao_ref_io_out(c))) return rc; c->timer.mark("wlist"); }
 	if (parts) { const double t0_ = hao_now(); const int rc_ = hao_deliver_enqueue(c); B.t_enq += hao_now() - t0_; ++B.t_n; if (c->sw.dltime && (B.t_n & 15) == 0) fprintf(stderr, "[deliver] %llu batches: slot wait %.1f ms, enqueue %.1f ms (arena alloc %.1f ms)\n", (unsigned long long)B.t_n, B.t_evsync * 1e3, B.t_enq * 1e3, B.t_alloc * 1e3); return rc_; }
 	return HAO_OK;
 }

@@ -324,9 +324,9 @@ int hao_window_ed_grid(hao_ctx *c, uint32_t window, uint32_t thre, uint64_t *n_t
 int hao_fetch_ed_grid(hao_ctx *c, hao_ed_task_t *tasks, hao_ed_result_t *res, uint64_t cap)
 {
 	if (!c) return HAO_EINVAL;
-	if (!c->batch || !c->batch->valid || (c->al_grid_n == 0 && cap)) { hao_set_err(c, "hao_fetch_ed_grid: no pairs of hao_window_ed_grid are resident (a new batch or another window-alignment call has reused the scratch)"); return HAO_EINVAL; }
+	if (!c->batch || !c->batch->valid || (c->win.scratch_pairs() == 0 && cap)) { hao_set_err(c, "hao_fetch_ed_grid: no pairs of hao_window_ed_grid are resident (a new batch or another window-alignment call has reused the scratch)"); return HAO_EINVAL; }
 	HIP_TRY(hipSetDevice(c->device));
-	const uint64_t n = std::min<uint64_t>(cap, c->al_grid_n);
+	const uint64_t n = std::min<uint64_t>(cap, c->win.scratch_pairs());
 	if (n && tasks) HIP_TRY(hipMemcpyAsync(tasks, c->al_task.p, n * sizeof(hao_ed_task_t), hipMemcpyDeviceToHost, c->stream));
 	if (n && res) HIP_TRY(hipMemcpyAsync(res, c->al_res.p, n * sizeof(hao_ed_result_t), hipMemcpyDeviceToHost, c->stream));
 	HIP_TRY(hipStreamSynchronize(c->stream));
@@ -335,21 +335,16 @@ int hao_fetch_ed_grid(hao_ctx *c, hao_ed_task_t *tasks, hao_ed_result_t *res, ui
 
 int hao_window_trace_grid(hao_ctx *c, uint32_t window, uint32_t thre, uint64_t out[4])
 {
-	if (!c || !out || !c->batch || !c->batch->valid) return HAO_EINVAL;
-	if (int rc = hao_view_refresh(c)) return rc;
-	HIP_TRY(hipSetDevice(c->device));
-	c->timer.begin(c->stream);
-	if (int rc = hao_trace_grid_run(c, window, thre, out)) return rc;
-	HIP_TRY(hipStreamSynchronize(c->stream));
-	c->timer.collect(c->stage_ms);      // (hao_stage_times: ed_grid, ed_align, trace_sel, trace_align)
-	if (c->tg.path.cap > (1ULL << 27)) c->tg.path.release();      // (more than 1 GB of column scratch is not kept between blocking calls)
-	return HAO_OK;
+	if (!c || !out) return HAO_EINVAL;
+	const int rc = hao_window_stage(c, nullptr, [&] { return hao_trace_grid_run(c, window, thre, out); });      // (hao_stage_times: ed_grid, ed_align, trace_sel, trace_align)
+	if (!rc && c->tg.path.cap > (1ULL << 27)) c->tg.path.release();      // (more than 1 GB of column scratch is not kept between blocking calls)
+	return rc;
 }
 
 int hao_fetch_trace_grid(hao_ctx *c, hao_ed_task_t *tasks, hao_trace_result_t *res, uint64_t *cig_off, uint16_t *cigars, uint64_t cap_pairs, uint64_t cap_cigars)
 {
 	if (!c) return HAO_EINVAL;
-	if (!c->batch || !c->batch->valid || !c->tg_valid) { hao_set_err(c, "hao_fetch_trace_grid: no results of hao_window_trace_grid are resident (a new batch or another window-alignment call has reused the scratch)"); return HAO_EINVAL; }
+	if (!c->batch || !c->batch->valid || !c->win.trace_resident()) { hao_set_err(c, "hao_fetch_trace_grid: no results of hao_window_trace_grid are resident (a new batch or another window-alignment call has reused the scratch)"); return HAO_EINVAL; }
 	if (c->tg_n == 0) { if (cig_off) cig_off[0] = 0; return HAO_OK; }      // (an empty grid: nothing resident to read)
 	HIP_TRY(hipSetDevice(c->device));
 	const uint64_t n = std::min<uint64_t>(cap_pairs, c->tg_n);
@@ -373,7 +368,7 @@ int hao_fetch_trace_grid(hao_ctx *c, hao_ed_task_t *tasks, hao_trace_result_t *r
 }
 
 // The view of one more part of a waited-for slot: the one body of hao_deliver_ed, hao_deliver_trace, hao_deliver_rescue and hao_deliver_wlist
-// (a template: C++ linkage inside this file's extern "C")
+// (this and the next are templates: C++ linkage inside this file's extern "C")
 extern "C++" {
 template <class V> static int hao_deliver_part(hao_ctx *c, int slot, V *out, V hao_ctx::Batch::Slot::*view, uint32_t part, const char *fn, const char *flag)
 {
@@ -383,6 +378,33 @@ template <class V> static int hao_deliver_part(hao_ctx *c, int slot, V *out, V h
 	if (S.pending) { hao_set_err(c, std::string(fn) + ": hao_deliver_wait has not been called on the slot"); return HAO_EINVAL; }
 	*out = S.*view;
 	return HAO_OK;
+}
+// The front hao_unpack_wlist and hao_unpack_rescue share (part_ok: the part's own view checks; win_off / wins / n_wins: its records by overlap): read rid's overlaps [*o0, *o0 + n) and their records lie
+// inside the part, every record in a window its overlap covers, in ascending window order, inside the read's grid.  Returns n; 0: a read outside the batch or without overlaps; UINT64_MAX: malformed views.
+template <class W> static uint64_t hao_unpack_records_ok(const hao_delivery_t *d, const hao_ed_delivery_t *e, const uint32_t *len, uint64_t rid, bool part_ok, uint64_t part_n_ol,
+		const uint64_t *win_off, const W *wins, uint64_t n_wins, uint64_t *o0_out)
+{
+	if (rid < d->rid_lo || rid >= d->rid_lo + d->n_reads) return 0;
+	if (!e->window || e->placement != HAO_PLACE_REF || !d->ol_off || !d->ol || part_n_ol != d->n_ol || !part_ok) return UINT64_MAX;
+	const uint64_t q = rid - d->rid_lo, o0 = d->ol_off[q], o1 = d->ol_off[q + 1];
+	if (o0 > o1 || o1 > part_n_ol) return UINT64_MAX;
+	const uint64_t n = o1 - o0;
+	if (n == 0) return 0;
+	const uint64_t w1 = win_off[o1];
+	if (win_off[o0] > w1 || w1 > n_wins) return UINT64_MAX;
+	std::vector<hao_ovlp_t> zs(n);
+	if (hao_unpack_overlaps(d, rid, zs.data(), n) != n) return UINT64_MAX;
+	const uint32_t wl = e->window; const uint64_t nwin = ((uint64_t)len[rid] + wl - 1) / wl;
+	for (uint64_t i = 0; i < n; ++i) {
+		const uint64_t a = win_off[o0 + i], b = win_off[o0 + i + 1];
+		if (a > b || b > w1) return UINT64_MAX;
+		for (uint64_t k = a; k < b; ++k) {
+			const uint32_t x = wins[k].win;
+			if (x < zs[i].x_pos_s / wl || x > zs[i].x_pos_e / wl || x >= nwin || (k > a && wins[k - 1].win >= x)) return UINT64_MAX;
+		}
+	}
+	*o0_out = o0;
+	return n;
 }
 }
 
@@ -435,28 +457,22 @@ void hao_ref_thresholds(uint32_t window, double e_rate, uint8_t *out) { if (out)
 
 int hao_window_ed_ref(hao_ctx *c, uint32_t window, double e_rate, uint64_t *n_tasks, uint64_t *unresolved)
 {
-	if (!c || !n_tasks || !c->batch || !c->batch->valid) return HAO_EINVAL;
-	if (int rc = hao_view_refresh(c)) return rc;
-	HIP_TRY(hipSetDevice(c->device));
-	c->timer.begin(c->stream);
-	if (int rc = hao_ed_ref_run(c, window, e_rate, n_tasks, unresolved)) return rc;
-	HIP_TRY(hipStreamSynchronize(c->stream));
-	c->timer.mark("ed_ref"); c->timer.collect(c->stage_ms);
-	return HAO_OK;
+	if (!c || !n_tasks) return HAO_EINVAL;
+	return hao_window_stage(c, "ed_ref", [&] { return hao_ed_ref_run(c, window, e_rate, n_tasks, unresolved); });
 }
 
 int hao_fetch_ed_ovlp(hao_ctx *c, uint64_t rid, const hao_ed_ovlp_t **summary, uint64_t *n)
 {
 	if (!c || !summary || !n) return HAO_EINVAL;
-	if (!c->batch || !c->batch->valid || !c->rf_valid) { hao_set_err(c, "hao_fetch_ed_ovlp: no summaries of hao_window_ed_ref are resident (a new batch has run since)"); return HAO_EINVAL; }
+	if (!c->batch || !c->batch->valid || !c->win.ed_resident()) { hao_set_err(c, "hao_fetch_ed_ovlp: no summaries of hao_window_ed_ref are resident (a new batch has run since)"); return HAO_EINVAL; }
 	hao_ctx::Batch &B = *c->batch;
 	if (rid < B.lo || rid >= B.lo + B.n) return HAO_EINVAL;
 	HIP_TRY(hipSetDevice(c->device));
 	if (int rc = hao_batch_download(c)) return rc;
-	if (!c->rf_hvalid) {
+	if (!c->win.host_current(WinResident::ED)) {
 		c->rf_hsum.assign(B.n_ol + 1, hao_ed_ovlp_sum{0, 0, 0, 0});
 		if (B.n_ol) HIP_TRY(hipMemcpy(c->rf_hsum.data(), c->rf_sum.p, B.n_ol * sizeof(hao_ed_ovlp_sum), hipMemcpyDeviceToHost));
-		c->rf_hvalid = true;
+		c->win.on_host_copy(WinResident::ED);
 	}
 	const uint64_t r = rid - B.lo, s_ = B.h_fin_off[r], e_ = B.h_fin_off[r + 1];
 	*summary = (const hao_ed_ovlp_t*)(c->rf_hsum.data() + s_); *n = e_ - s_;
@@ -465,46 +481,28 @@ int hao_fetch_ed_ovlp(hao_ctx *c, uint64_t rid, const hao_ed_ovlp_t **summary, u
 
 int hao_window_rescue_ref(hao_ctx *c, uint64_t *n_rescued)
 {
-	if (!c || !n_rescued || !c->batch || !c->batch->valid) return HAO_EINVAL;
-	if (int rc = hao_view_refresh(c)) return rc;
-	HIP_TRY(hipSetDevice(c->device));
-	c->timer.begin(c->stream);
-	if (int rc = hao_rescue_ref_run(c, n_rescued)) return rc;
-	HIP_TRY(hipStreamSynchronize(c->stream));
-	c->timer.mark("rescue_ref"); c->timer.collect(c->stage_ms);
-	return HAO_OK;
+	if (!c || !n_rescued) return HAO_EINVAL;
+	return hao_window_stage(c, "rescue_ref", [&] { return hao_rescue_ref_run(c, n_rescued); });
 }
 
 int hao_fetch_rescue(hao_ctx *c, uint64_t rid, const hao_rescue_ovlp_t **ovlp, uint64_t *n, const uint64_t **win_off, const hao_rescue_win_t **wins)
 {
 	if (!c || !ovlp || !n || !win_off || !wins) return HAO_EINVAL;
-	if (!c->batch || !c->batch->valid || !c->rs_valid) { hao_set_err(c, "hao_fetch_rescue: no results of hao_window_rescue_ref are resident (a new batch has run since)"); return HAO_EINVAL; }
+	if (!c->batch || !c->batch->valid || !c->win.rescue_resident()) { hao_set_err(c, "hao_fetch_rescue: no results of hao_window_rescue_ref are resident (a new batch has run since)"); return HAO_EINVAL; }
 	hao_ctx::Batch &B = *c->batch;
 	if (rid < B.lo || rid >= B.lo + B.n) return HAO_EINVAL;
 	HIP_TRY(hipSetDevice(c->device));
 	if (int rc = hao_batch_download(c)) return rc;
 	hao_ctx::Rescue &G = c->rs;
-	if (!c->rs_hvalid) {      // the whole batch once: the per-overlap results, and the record regions compacted into a CSR by overlap (slots without a record dropped)
+	if (!c->win.host_current(WinResident::RESCUE)) {      // the whole batch once: the per-overlap results, the record offsets per overlap and the records, as the stage left them
 		const uint64_t m = B.n_ol;
-		G.h_ovlp.assign(m + 1, hao_rs_ovlp{0, 0, 0, 0, 0}); G.h_win_off.assign(m + 1, 0); G.h_wins.clear();
+		G.h_ovlp.assign(m + 1, hao_rs_ovlp{0, 0, 0, 0, 0}); G.h_win_off.assign(m + 1, 0); G.h_wins.assign(c->rs_nw + 1, hao_rs_win{0, 0, 0, 0});      // (never empty: the pointers handed out are valid)
 		if (m) {
-			std::vector<uint64_t> rb(m), wo(m + 1); std::vector<hao_rs_win> rec((size_t)c->rs_slots + 1);
 			HIP_TRY(hipMemcpy(G.h_ovlp.data(), G.ovlp.p, m * sizeof(hao_rs_ovlp), hipMemcpyDeviceToHost));
-			HIP_TRY(hipMemcpy(rb.data(), G.rbase.p, m * 8, hipMemcpyDeviceToHost));
-			HIP_TRY(hipMemcpy(wo.data(), c->rf.woff.p, (m + 1) * 8, hipMemcpyDeviceToHost));
-			if (c->rs_slots) HIP_TRY(hipMemcpy(rec.data(), G.rec.p, c->rs_slots * sizeof(hao_rs_win), hipMemcpyDeviceToHost));
-			for (uint64_t i = 0; i < m; ++i) {
-				G.h_win_off[i] = G.h_wins.size();
-				if (rb[i] == UINT64_MAX) continue;
-				for (uint64_t k = 0, nw = wo[i + 1] - wo[i]; k < nw && rb[i] + k < c->rs_slots; ++k) {
-					hao_rs_win r = rec[rb[i] + k];
-					if (r.info & HAO_RS_VALID) { r.info &= ~(HAO_RS_VALID | HAO_RS_UNTRACED_BIT); G.h_wins.push_back(r); }
-				}
-			}
-			G.h_win_off[m] = G.h_wins.size();
+			HIP_TRY(hipMemcpy(G.h_win_off.data(), G.off.p, (m + 1) * 8, hipMemcpyDeviceToHost));
+			if (c->rs_nw) HIP_TRY(hipMemcpy(G.h_wins.data(), G.wins.p, c->rs_nw * sizeof(hao_rs_win), hipMemcpyDeviceToHost));
 		}
-		G.h_wins.push_back(hao_rs_win{0, 0, 0, 0});      // (never empty: the pointer handed out is valid)
-		c->rs_hvalid = true;
+		c->win.on_host_copy(WinResident::RESCUE);
 	}
 	const uint64_t r = rid - B.lo, s_ = B.h_fin_off[r], e_ = B.h_fin_off[r + 1];
 	*ovlp = (const hao_rescue_ovlp_t*)(G.h_ovlp.data() + s_); *n = e_ - s_;
@@ -514,26 +512,20 @@ int hao_fetch_rescue(hao_ctx *c, uint64_t rid, const hao_rescue_ovlp_t **ovlp, u
 
 int hao_window_wlist_ref(hao_ctx *c, uint64_t out[5])
 {
-	if (!c || !out || !c->batch || !c->batch->valid) return HAO_EINVAL;
-	if (int rc = hao_view_refresh(c)) return rc;
-	HIP_TRY(hipSetDevice(c->device));
-	c->timer.begin(c->stream);
-	if (int rc = hao_wlist_ref_run(c, out)) return rc;
-	HIP_TRY(hipStreamSynchronize(c->stream));
-	c->timer.mark("wlist_ref"); c->timer.collect(c->stage_ms);
-	return HAO_OK;
+	if (!c || !out) return HAO_EINVAL;
+	return hao_window_stage(c, "wlist_ref", [&] { return hao_wlist_ref_run(c, out); });
 }
 
 int hao_fetch_wlist(hao_ctx *c, uint64_t rid, uint64_t *n_ol, const uint64_t **win_off, const hao_wlist_win_t **wins, const uint64_t **cig_off, const uint16_t **cigars)
 {
 	if (!c || !n_ol || !win_off || !wins || !cig_off || !cigars) return HAO_EINVAL;
-	if (!c->batch || !c->batch->valid || !c->rf_valid || !c->rs_valid || !c->wl_valid || c->al_grid_n != c->rf_T) { hao_set_err(c, "hao_fetch_wlist: no results of hao_window_wlist_ref are resident (a new batch or another window-alignment stage has run since)"); return HAO_EINVAL; }
+	if (!c->batch || !c->batch->valid || !c->win.wlist_resident()) { hao_set_err(c, "hao_fetch_wlist: no results of hao_window_wlist_ref are resident (a new batch or another window-alignment stage has run since)"); return HAO_EINVAL; }
 	hao_ctx::Batch &B = *c->batch;
 	if (rid < B.lo || rid >= B.lo + B.n) return HAO_EINVAL;
 	HIP_TRY(hipSetDevice(c->device));
 	if (int rc = hao_batch_download(c)) return rc;
 	hao_ctx::Wlist &G = c->wl;
-	if (!c->wl_hvalid) {      // the whole batch once
+	if (!c->win.host_current(WinResident::WLIST)) {      // the whole batch once
 		const uint64_t m = B.n_ol, N = c->wl_out[0], E = c->wl_out[3];
 		G.h_woff.assign(m + 1, 0); G.h_wins.assign(N + 1, hao_rs_win{0, 0, 0, 0}); G.h_cig_off.assign(N + 1, 0); G.h_cig.assign(E + 1, 0);
 		if (N) {
@@ -542,7 +534,7 @@ int hao_fetch_wlist(hao_ctx *c, uint64_t rid, uint64_t *n_ol, const uint64_t **w
 			HIP_TRY(hipMemcpy(G.h_cig_off.data(), G.cig_off.p, (N + 1) * 8, hipMemcpyDeviceToHost));
 			if (E) HIP_TRY(hipMemcpy(G.h_cig.data(), G.cig.p, E * 2, hipMemcpyDeviceToHost));
 		}
-		c->wl_hvalid = true;
+		c->win.on_host_copy(WinResident::WLIST);
 	}
 	const uint64_t r = rid - B.lo, s_ = B.h_fin_off[r], e_ = B.h_fin_off[r + 1], n = e_ - s_, g0 = G.h_woff[s_], g1 = G.h_woff[e_];
 	G.r_woff.resize(n + 1); G.r_cig_off.resize(g1 - g0 + 1);
@@ -558,29 +550,15 @@ uint64_t hao_unpack_wlist(const hao_delivery_t *d, const hao_ed_delivery_t *e, c
 		uint64_t *win_off, hao_wlist_win_t *wins, uint64_t *cig_off, uint16_t *cigars, uint64_t cap_ovlp, uint64_t cap_wins, uint64_t cap_cigars)
 {
 	if (!d || !e || !r || !w || !len) return UINT64_MAX;
-	if (rid < d->rid_lo || rid >= d->rid_lo + d->n_reads) return 0;
-	if (!e->window || e->placement != HAO_PLACE_REF || !d->ol_off || !d->ol || r->n_ol != d->n_ol || w->n_ol != d->n_ol || (w->n_ol && (!w->win_off || !r->ovlp)) || (w->n_wins && (!w->wins || !w->cig_off)) ||
-		(w->n_cigar && !w->cigars)) return UINT64_MAX;
-	const uint64_t q = rid - d->rid_lo, o0 = d->ol_off[q], o1 = d->ol_off[q + 1];
-	if (o0 > o1 || o1 > w->n_ol) return UINT64_MAX;
-	const uint64_t n = o1 - o0;
-	if (n == 0) return 0;
+	uint64_t o0 = 0;
+	const uint64_t n = hao_unpack_records_ok(d, e, len, rid, r->n_ol == d->n_ol && (!w->n_ol || (w->win_off && r->ovlp)) && (!w->n_wins || (w->wins && w->cig_off)) && (!w->n_cigar || w->cigars),
+		w->n_ol, w->win_off, w->wins, w->n_wins, &o0);
+	if (n == 0 || n == UINT64_MAX) return n;
+	const uint64_t o1 = o0 + n, g0 = w->win_off[o0], g1 = w->win_off[o1];
 	if (w->win_off[w->n_ol] != w->n_wins || (w->n_wins ? w->cig_off[w->n_wins] : 0) != w->n_cigar) return UINT64_MAX;      // (the counts add up)
-	const uint64_t g0 = w->win_off[o0], g1 = w->win_off[o1];
-	if (g0 > g1 || g1 > w->n_wins) return UINT64_MAX;
-	// every record in a window its overlap covers, in ascending window order, inside the read's grid, in an overlap that passed; entry offsets ascend
-	std::vector<hao_ovlp_t> zs(n);
-	if (hao_unpack_overlaps(d, rid, zs.data(), n) != n) return UINT64_MAX;
-	const uint32_t wl = e->window; const uint64_t nwin = ((uint64_t)len[rid] + wl - 1) / wl;
-	for (uint64_t i = 0; i < n; ++i) {
-		const uint64_t a = w->win_off[o0 + i], b = w->win_off[o0 + i + 1];
-		if (a > b || b > g1) return UINT64_MAX;
-		if (b > a && !r->ovlp[o0 + i].verdict) return UINT64_MAX;
-		for (uint64_t k = a; k < b; ++k) {
-			const uint32_t x = w->wins[k].win;
-			if (x < zs[i].x_pos_s / wl || x > zs[i].x_pos_e / wl || x >= nwin || (k > a && w->wins[k - 1].win >= x)) return UINT64_MAX;
-			if (w->cig_off[k] > w->cig_off[k + 1] || w->cig_off[k + 1] > w->n_cigar) return UINT64_MAX;
-		}
+	for (uint64_t i = o0; i < o1; ++i) {      // every record in an overlap that passed; entry offsets ascend
+		if (w->win_off[i + 1] > w->win_off[i] && !r->ovlp[i].verdict) return UINT64_MAX;
+		for (uint64_t k = w->win_off[i]; k < w->win_off[i + 1]; ++k) if (w->cig_off[k] > w->cig_off[k + 1] || w->cig_off[k + 1] > w->n_cigar) return UINT64_MAX;
 	}
 	const uint64_t c0 = g1 > g0 ? w->cig_off[g0] : 0, c1 = g1 > g0 ? w->cig_off[g1] : 0;
 	if (n > cap_ovlp || g1 - g0 > cap_wins || c1 - c0 > cap_cigars || !win_off || !wins || !cig_off || !cigars) return n;
@@ -603,26 +581,10 @@ uint64_t hao_unpack_rescue(const hao_delivery_t *d, const hao_ed_delivery_t *e, 
 		hao_rescue_ovlp_t *ovlp, uint64_t *win_off, hao_rescue_win_t *wins, uint64_t cap_ovlp, uint64_t cap_wins)
 {
 	if (!d || !e || !r || !len) return UINT64_MAX;
-	if (rid < d->rid_lo || rid >= d->rid_lo + d->n_reads) return 0;
-	if (!e->window || e->placement != HAO_PLACE_REF || !d->ol_off || !d->ol || r->n_ol != d->n_ol || (r->n_ol && (!r->ovlp || !r->win_off)) || (r->n_wins && !r->wins)) return UINT64_MAX;
-	const uint64_t q = rid - d->rid_lo, o0 = d->ol_off[q], o1 = d->ol_off[q + 1];
-	if (o0 > o1 || o1 > r->n_ol) return UINT64_MAX;
-	const uint64_t n = o1 - o0;
-	if (n == 0) return 0;
-	const uint64_t w0 = r->win_off[o0], w1 = r->win_off[o1];
-	if (w0 > w1 || w1 > r->n_wins) return UINT64_MAX;
-	// every record in a window its overlap covers, in ascending window order, inside the read's grid
-	std::vector<hao_ovlp_t> zs(n);
-	if (hao_unpack_overlaps(d, rid, zs.data(), n) != n) return UINT64_MAX;
-	const uint32_t wl = e->window; const uint64_t nwin = ((uint64_t)len[rid] + wl - 1) / wl;
-	for (uint64_t i = 0; i < n; ++i) {
-		const uint64_t a = r->win_off[o0 + i], b = r->win_off[o0 + i + 1];
-		if (a > b || b > w1) return UINT64_MAX;
-		for (uint64_t k = a; k < b; ++k) {
-			const uint32_t w = r->wins[k].win;
-			if (w < zs[i].x_pos_s / wl || w > zs[i].x_pos_e / wl || w >= nwin || (k > a && r->wins[k - 1].win >= w)) return UINT64_MAX;
-		}
-	}
+	uint64_t o0 = 0;
+	const uint64_t n = hao_unpack_records_ok(d, e, len, rid, r->n_ol == d->n_ol && (!r->n_ol || (r->ovlp && r->win_off)) && (!r->n_wins || r->wins), r->n_ol, r->win_off, r->wins, r->n_wins, &o0);
+	if (n == 0 || n == UINT64_MAX) return n;
+	const uint64_t o1 = o0 + n, w0 = r->win_off[o0], w1 = r->win_off[o1];
 	if (n > cap_ovlp || w1 - w0 > cap_wins || !ovlp || !win_off || !wins) return n;
 	for (uint64_t i = 0; i < n; ++i) { ovlp[i] = r->ovlp[o0 + i]; win_off[i] = r->win_off[o0 + i] - w0; }
 	win_off[n] = w1 - w0;

@@ -126,6 +126,42 @@ struct hao_switches {
 static __global__ void hao_peek_kernel(const unsigned long long *src, int n, unsigned long long *dst)
 { if ((int)threadIdx.x < n) dst[threadIdx.x] = src[threadIdx.x]; }
 
+// What the window-alignment calls have left resident on the current batch.  Every write is a transition, every read a predicate: nothing outside assigns a member.
+//   owner, n   whose pairs lie in the shared scratch al_task / al_res: nobody's (a new batch or a host-fed call), hao_window_ed_grid's n, or hao_window_ed_ref's n
+//   chain      how far hao_window_ed_ref -> hao_window_rescue_ref -> hao_window_wlist_ref has got; a stage that starts (again) drops itself and the later ones until
+//              it completes.  Summaries and rescue results lie in buffers of their own; the rescue stage READS the scratch, and the lists ask for its owner too
+//   host       bit s: stage s's fetch call holds host copies of the current results (cleared where the device side is)
+//   trace      hao_window_trace_grid's results are resident (buffers of their own)
+struct WinResident {
+	enum Stage { NONE, ED, RESCUE, WLIST };
+	void on_new_batch() { *this = WinResident(); }
+	void on_host_fed() { owner = NOBODY; n = 0; trace = false; }
+	void on_grid(uint64_t pairs) { owner = GRID; n = pairs; }
+	void on_ref_begin(Stage s) { if (chain >= s) chain = (Stage)(s - 1); host &= (1u << s) - 1; if (s == ED) { owner = NOBODY; n = 0; } }
+	void on_ref_done(Stage s, uint64_t pairs = 0) { chain = s; if (s == ED) { owner = REF; n = pairs; } }
+	void on_host_copy(Stage s) { host |= 1u << s; }
+	void on_trace_grid(bool done) { trace = done; }
+	uint64_t scratch_pairs() const { return owner == NOBODY ? 0 : n; }      // what hao_fetch_ed_grid serves (either grid call's)
+	bool ed_resident() const { return chain >= ED; } bool rescue_resident() const { return chain >= RESCUE; } bool trace_resident() const { return trace; }
+	bool ref_input_resident() const { return chain >= ED && owner == REF; }      // + hao_window_ed_ref's results per pair in al_res: the rescue stage's input
+	bool wlist_input_resident() const { return chain >= RESCUE && owner == REF; }
+	bool wlist_resident() const { return chain >= WLIST && owner == REF; }
+	bool host_current(Stage s) const { return (host >> s) & 1u; }
+private:
+	enum Owner { NOBODY, GRID, REF } owner = NOBODY; uint64_t n = 0; Stage chain = NONE; uint32_t host = 0; bool trace = false;
+};
+
+// A reference-placed batch whose ED stage has run, as hao_al_rescue and hao_al_wlist (hao_f3.hip) take it: filled from the context's own buffers by the blocking calls, from the
+// output set's by the streamed parts (hao_batch.hpp); the CSR of covered windows, the shifts and the error byte per slot are the ED stage's scratch in c->rf on both paths.
+struct hao_ref_io {
+	const hao_ovlp_t *ol; uint64_t n_ol;                                        // the batch's final ol->list
+	uint32_t wl; const uint8_t *tab;                                            // window length, threshold table (on the device)
+	const hao_ed_pair *pairs; uint64_t n_pairs, n_slots;                        // the pair list, its length, the covered windows (CSR slots)
+	const hao_ed_result_t *res; const uint8_t *err8; const uint16_t *pe16;      // the primary results per pair: res, or (res == NULL) the compact records err8 / pe16
+	DevBuf<hao_rs_ovlp> *rs_ovlp; DevBuf<uint64_t> *rs_off; DevBuf<hao_rs_win> *rs_wins;                          // rescue: per-overlap results, record offsets per overlap, the records
+	DevBuf<uint64_t> *wl_woff; DevBuf<hao_rs_win> *wl_wins; DevBuf<uint64_t> *wl_cigoff; DevBuf<uint16_t> *wl_cig;      // window lists: record offsets per overlap, the records, entry offsets per record, the entries
+};
+
 struct hao_ctx {
 	int device = 0; hao_opt_t opt; std::string err; hipStream_t stream = nullptr; hao_switches sw;
 	// hao_attach: a second batch context over this engine's reads and index (own stream, scratch, results); index_gen counts the owner's rebuilds
@@ -169,43 +205,44 @@ struct hao_ctx {
 	std::vector<uint64_t> h_ix_keys, h_ix_off, h_ix_pos, h_ix_mz_off; bool h_ix_valid = false;
 	// ---- query batch ----
 	// f3 (hao_align.cuh): scratch of the window-alignment batches, kept between calls (a hipMalloc / hipFree pair per buffer and call cost more than the kernels)
-	uint64_t al_grid_n = 0;      // pairs hao_window_ed_grid left in al_task / al_res
+	WinResident win;      // who owns al_task / al_res, and which results of the window-alignment calls are resident
 	DevBuf<hao_ed_task_t> al_task; DevBuf<uint64_t> al_k1, al_k2, al_path; DevBuf<uint32_t> al_i1, al_order, al_sel; DevBuf<hao_ed_result_t> al_res; DevBuf<hao_trace_result_t> al_tres;
 	DevBuf<uint8_t> al_want; DevBuf<uint16_t> al_cig;
 	uint32_t ded_window = 0, ded_thre = 0;      // hao_deliver_ed_config: the grid of HAO_DELIVER_ED (window 0: not configured); per context, a view has its own
 	// reference placement (hao_grid_pair.cuh: hao_ref_pair).  ded_place / ded_erate / ded_tab: hao_deliver_ed_config_ref (the table is uploaded at configuration
 	// time: no host-to-device copy inside a batch).  rf: the stage's scratch, compute stream only (the blocking call and HAO_DELIVER_ED share it) - covered windows
 	// per overlap and their scan, the shifts, the error byte per CSR slot, the pair list, the unresolved counter; rf_tab / rf_sum / rf_*: what hao_window_ed_ref
-	// leaves for hao_fetch_ed_ovlp (rf_valid: it belongs to the current batch)
+	// leaves for hao_fetch_ed_ovlp (resident while win.ed_resident()); rs_wc: the covered windows (CSR slots) of the batch the ED stage - blocking or streamed - last ran on
 	uint32_t ded_place = 0; double ded_erate = 0; DevBuf<uint8_t> ded_tab;
 	struct RefGrid {
 		DevBuf<uint64_t> cnt, woff; DevBuf<int16_t> shift; DevBuf<uint8_t> werr; DevBuf<hao_ed_pair> pairs; DevBuf<unsigned long long> ctr;
 	} rf;
-	DevBuf<uint8_t> rf_tab; uint32_t rf_tab_wl = 0; double rf_tab_erate = 0; DevBuf<hao_ed_ovlp_sum> rf_sum; std::vector<hao_ed_ovlp_sum> rf_hsum; bool rf_valid = false, rf_hvalid = false; uint64_t rf_unres = 0;
-	// the rescue stage (hao_rescue.cuh; hao_window_rescue_ref): pe per CSR slot, record region start per overlap, the states of the overlaps with an open
-	// window, their record regions, the per-overlap results, the column scratch, six counters; rs_valid: the results belong to the current batch (rf_T: the
-	// pairs hao_window_ed_ref left in al_res, which the stage reads); h_*: hao_fetch_rescue's host copies and the compacted records
+	DevBuf<uint8_t> rf_tab; uint32_t rf_tab_wl = 0; double rf_tab_erate = 0; DevBuf<hao_ed_ovlp_sum> rf_sum; std::vector<hao_ed_ovlp_sum> rf_hsum; uint64_t rf_unres = 0, rs_wc = 0;
+	// the rescue stage (hao_rescue.cuh; hao_window_rescue_ref and HAO_DELIVER_RESCUE): pe per CSR slot, record region start per overlap, the states of the overlaps
+	// with an open window, their record regions, the column scratch, six counters - scratch of both paths; ovlp / off / wins: the blocking path's results (per-overlap
+	// results and the records compacted on the device into a CSR by overlap, resident while win.rescue_resident()); h_*: hao_fetch_rescue's plain copies of the three
 	struct Rescue {
-		DevBuf<uint16_t> wpe; DevBuf<uint64_t> rbase, path; DevBuf<hao_rs_state> st; DevBuf<hao_rs_win> rec; DevBuf<hao_rs_ovlp> ovlp; DevBuf<unsigned long long> ctr;
+		DevBuf<uint16_t> wpe; DevBuf<uint64_t> rbase, path, off; DevBuf<hao_rs_state> st; DevBuf<hao_rs_win> rec, wins; DevBuf<hao_rs_ovlp> ovlp; DevBuf<unsigned long long> ctr;
 		std::vector<hao_rs_ovlp> h_ovlp; std::vector<uint64_t> h_win_off; std::vector<hao_rs_win> h_wins;
 	} rs;
-	bool rs_valid = false, rs_hvalid = false; uint64_t rf_T = 0, rs_slots = 0, rs_rounds = 0, rs_active = 0, rs_total = 0;
+	uint64_t rs_slots = 0, rs_rounds = 0, rs_active = 0, rs_total = 0, rs_nw = 0;      // the last rescue stage's record slots, rounds, overlaps with an open window, rescued windows, records kept
 	// the window lists (hao_wlist.cuh; hao_window_wlist_ref): records per overlap and their scan, the plan, the records, entry counts and their scan (the CSR
 	// offsets), sort keys and record indices (sel: the records that need a sweep, in text order), the column scratch, two rows per swept record, the compact
-	// cigars, five counters; wl_valid: the results belong to the current batch's rescue results; h_*: hao_fetch_wlist's host copies and the read it last served
+	// cigars, five counters; woff / wins / cig_off / cig: the blocking path's results (resident while win.wlist_resident()); h_*: hao_fetch_wlist's host copies and
+	// the read it last served; wl_out: the last stage's five counts
 	struct Wlist {
 		DevBuf<uint64_t> cnt, woff, ncig, cig_off, key, key2, path; DevBuf<hao_wl_plan> plan; DevBuf<hao_rs_win> wins; DevBuf<uint32_t> idx, sel, rowof; DevBuf<uint16_t> rows, cig; DevBuf<unsigned long long> ctr;
 		std::vector<uint64_t> h_woff, h_cig_off, r_woff, r_cig_off; std::vector<hao_rs_win> h_wins; std::vector<uint16_t> h_cig;
 	} wl;
-	bool wl_valid = false, wl_hvalid = false; uint64_t rs_wc = 0, wl_out[5] = { 0, 0, 0, 0, 0 };
+	uint64_t wl_out[5] = { 0, 0, 0, 0, 0 };
 	// f3 with traceback on the grid (hao_trace_grid.cuh): the stage's scratch, compute stream only (hao_window_trace_grid and HAO_DELIVER_TRACE share it) -
 	// flags and selected pairs, entry counts and their scans, the compact array's offsets, the column scratch, the rows of one slice, two counters
 	struct TraceGrid {
 		DevBuf<uint8_t> want; DevBuf<uint32_t> sel; DevBuf<uint64_t> cnt, loc, off, path; DevBuf<uint16_t> rows; DevBuf<unsigned long long> ctr;
 	} tg;
-	// hao_window_trace_grid's results, kept for hao_fetch_trace_grid (tg_valid: they belong to the current batch and no window-alignment batch has run since):
+	// hao_window_trace_grid's results, kept for hao_fetch_trace_grid (resident while win.trace_resident(): until a new batch or a host-fed window-alignment call):
 	// the pair list, the distance-only err / pe, ps and entry count per pair, the compact cigars; pairs, traced pairs, entries, aligned but untraced pairs
-	bool tg_valid = false; uint32_t tg_wl = 0, tg_thre = 0; uint64_t tg_n = 0, tg_nsel = 0, tg_ncig = 0, tg_nuntr = 0;
+	uint32_t tg_wl = 0, tg_thre = 0; uint64_t tg_n = 0, tg_nsel = 0, tg_ncig = 0, tg_nuntr = 0;
 	DevBuf<hao_ed_pair> tg_pairs; DevBuf<uint8_t> tg_err; DevBuf<uint16_t> tg_pe, tg_ps, tg_ncig16, tg_cig;
 	struct Batch;
 	Batch *batch = nullptr;

@@ -240,13 +240,13 @@ static int hao_deliver_enqueue(hao_ctx *c)
 		L.put(t.cigar, O.tr_cig.p, B.tr_ncig * 2);
 	}
 	if (parts & HAO_DELIVER_RESCUE) {
-		r.n_ol = m; r.n_wins = B.rs_nw; r.n_rescued = B.rs_nres;
+		r.n_ol = m; r.n_wins = c->rs_nw; r.n_rescued = c->rs_total;
 		L.put(r.ovlp, O.rs_ovlp.p, m * sizeof(hao_rs_ovlp));
 		L.put(r.win_off, O.rs_off.p, (m + 1) * 8);
-		L.put(r.wins, O.rs_wins.p, B.rs_nw * sizeof(hao_rs_win));
+		L.put(r.wins, O.rs_wins.p, c->rs_nw * sizeof(hao_rs_win));
 	}
 	if (parts & HAO_DELIVER_WLIST) {
-		w.n_ol = m; w.n_wins = B.wl_cnt[0]; w.n_swept = B.wl_cnt[1]; w.n_replace = B.wl_cnt[2]; w.n_cigar = B.wl_cnt[3]; w.n_untraced = B.wl_cnt[4];
+		w.n_ol = m; w.n_wins = c->wl_out[0]; w.n_swept = c->wl_out[1]; w.n_replace = c->wl_out[2]; w.n_cigar = c->wl_out[3]; w.n_untraced = c->wl_out[4];
 		L.put(w.win_off, O.wl_woff.p, (m + 1) * 8);
 		L.put(w.wins, O.wl_wins.p, w.n_wins * sizeof(hao_rs_win));
 		L.put(w.cig_off, O.wl_cigoff.p, (w.n_wins + 1) * 8);

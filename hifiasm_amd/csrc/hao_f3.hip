@@ -170,25 +170,20 @@ int hao_al_trace_grid_expand(hao_ctx *c, const hao_ovlp_t *ol, uint64_t n, hao_e
 	return HAO_OK;
 }
 
-// the rescue stage (hao_rescue.cuh; hao_window_rescue_ref, hao_batch.hpp): over the n_ol overlaps of the batch whose reference-placed ED stage has just run -
-// RA = its CSR and shifts, werr / res = its error bytes per slot and results per pair (n_pairs, pair list `pairs`), n_slots = its covered windows.  Leaves the
-// per-overlap results in c->rs.ovlp, the record regions in c->rs.rec (c->rs.rbase[i]: overlap i's), and the counts in c->rs_*.  Host round trips: one for the
-// two sizes, one count per round, one for the total.
-// res == NULL: the delivery path's records err8 / pe16 per pair instead.  out: where the per-overlap results go (NULL: c->rs.ovlp).  d_off / d_wins / n_wins
-// (the delivery path, all three or none): the records compacted on the device - d_off[n_ol + 1] offsets, the records, their number (one more round trip).
-int hao_al_rescue(hao_ctx *c, const hao_ovlp_t *ol, uint64_t n_ol, uint32_t wl, hao_ref_args RA, const uint8_t *werr, const hao_ed_pair *pairs, const hao_ed_result_t *res, uint64_t n_pairs, uint64_t n_slots,
-		const uint8_t *err8, const uint16_t *pe16, hao_rs_ovlp *out, DevBuf<uint64_t> *d_off, DevBuf<hao_rs_win> *d_wins, uint64_t *n_wins)
+// the rescue stage (hao_rescue.cuh; hao_rescue_run, hao_batch.hpp): over the overlaps of a batch whose reference-placed ED stage has just run (io; at least one
+// overlap) - its CSR, shifts and error bytes per slot in c->rf.  Leaves the per-overlap results in io.rs_ovlp, the records compacted by overlap in io.rs_off /
+// io.rs_wins (in window order, the device-only bits stripped), the record regions in c->rs.rec (c->rs.rbase[i]: overlap i's) for the window lists, and the counts
+// in c->rs_*.  Host round trips: one for the two sizes, one count per round, one for the number of records, one for the total.
+int hao_al_rescue(hao_ctx *c, const hao_ref_io &io)
 {
-	hao_ctx::Rescue &G = c->rs;
-	c->rs_rounds = c->rs_active = c->rs_total = 0; c->rs_slots = 0;
-	HIP_TRY(G.ovlp.reserve(n_ol + 1)); HIP_TRY(G.rbase.reserve(n_ol + 1)); HIP_TRY(G.wpe.reserve(n_slots + 1)); HIP_TRY(G.ctr.reserve(8));
-	if (n_wins) *n_wins = 0;
-	if (n_ol == 0) return HAO_OK;
+	hao_ctx::Rescue &G = c->rs; const hao_ovlp_t *ol = io.ol; const uint64_t n_ol = io.n_ol, n_pairs = io.n_pairs, n_slots = io.n_slots; const uint32_t wl = io.wl;
+	hao_ref_args RA; RA.win_off = c->rf.woff.p; RA.shift = c->rf.shift.p; RA.tab = io.tab;
+	HIP_TRY(G.rbase.reserve(n_ol + 1)); HIP_TRY(G.wpe.reserve(n_slots + 1)); HIP_TRY(G.ctr.reserve(8));
 	HIP_TRY(hipMemsetAsync(G.ctr.p, 0, 64, c->stream));
 	const dim3 b_(256), go((unsigned)((n_ol + 255) / 256));
-	if (n_pairs && res) { hipLaunchKernelGGL(hao_rs_scatter_pe_kernel, dim3((unsigned)((n_pairs + 255) / 256)), b_, 0, c->stream, ol, pairs, res, n_pairs, wl, RA.win_off, G.wpe.p); HAO_CHECK_LAUNCH(); }
-	else if (n_pairs) { hipLaunchKernelGGL(hao_rs_scatter_pe16_kernel, dim3((unsigned)((n_pairs + 255) / 256)), b_, 0, c->stream, ol, pairs, err8, pe16, n_pairs, wl, RA.win_off, G.wpe.p); HAO_CHECK_LAUNCH(); }
-	hao_rs_args A; A.ol = ol; A.n_ol = n_ol; A.wl = wl; A.win_off = RA.win_off; A.shift = RA.shift; A.tab = RA.tab; A.werr = werr; A.wpe = G.wpe.p; A.len = hao_al_reads_of(c).len;
+	if (n_pairs && io.res) { hipLaunchKernelGGL(hao_rs_scatter_pe_kernel, dim3((unsigned)((n_pairs + 255) / 256)), b_, 0, c->stream, ol, io.pairs, io.res, n_pairs, wl, RA.win_off, G.wpe.p); HAO_CHECK_LAUNCH(); }
+	else if (n_pairs) { hipLaunchKernelGGL(hao_rs_scatter_pe16_kernel, dim3((unsigned)((n_pairs + 255) / 256)), b_, 0, c->stream, ol, io.pairs, io.err8, io.pe16, n_pairs, wl, RA.win_off, G.wpe.p); HAO_CHECK_LAUNCH(); }
+	hao_rs_args A; A.ol = ol; A.n_ol = n_ol; A.wl = wl; A.win_off = RA.win_off; A.shift = RA.shift; A.tab = RA.tab; A.werr = c->rf.werr.p; A.wpe = G.wpe.p; A.len = hao_al_reads_of(c).len;
 	hipLaunchKernelGGL((hao_rs_gap_kernel<false>), go, b_, 0, c->stream, A, G.ctr.p, (uint64_t*)nullptr, (hao_rs_state*)nullptr, (hao_rs_win*)nullptr); HAO_CHECK_LAUNCH();
 	hipLaunchKernelGGL(hao_peek_kernel, dim3(1), dim3(64), 0, c->stream, (const unsigned long long*)G.ctr.p, 2, c->peek_d + 40); HAO_CHECK_LAUNCH();
 	HIP_TRY(hipStreamSynchronize(c->stream));
@@ -215,41 +210,39 @@ int hao_al_rescue(hao_ctx *c, const hao_ovlp_t *ol, uint64_t n_ol, uint32_t wl, 
 			}
 		}
 	}
-	hipLaunchKernelGGL(hao_rs_verdict_kernel, go, b_, 0, c->stream, A, G.rbase.p, G.rec.p, out ? out : G.ovlp.p, G.ctr.p + 5); HAO_CHECK_LAUNCH();
-	if (d_off) {
-		HIP_TRY(d_off->reserve(n_ol + 2)); HIP_TRY(c->al_k1.reserve(n_ol + 2));      // (al_k1: the upload path's key buffer, free here)
-		hipLaunchKernelGGL(hao_rs_count_kernel, dim3((unsigned)((n_ol + 256) / 256)), b_, 0, c->stream, n_ol, RA.win_off, G.rbase.p, G.rec.p, c->al_k1.p); HAO_CHECK_LAUNCH();
-		if (int rc = hao_excl_scan_u64(c, c->al_k1.p, d_off->p, n_ol + 1)) return rc;
-		hipLaunchKernelGGL(hao_peek_kernel, dim3(1), dim3(64), 0, c->stream, (const unsigned long long*)(d_off->p + n_ol), 1, c->peek_d + 44); HAO_CHECK_LAUNCH();
-		HIP_TRY(hipStreamSynchronize(c->stream));
-		*n_wins = c->peek_h[44];
-		HIP_TRY(d_wins->reserve(*n_wins + 1));
-		if (*n_wins) { hipLaunchKernelGGL(hao_rs_compact_kernel, go, b_, 0, c->stream, n_ol, RA.win_off, G.rbase.p, G.rec.p, d_off->p, d_wins->p); HAO_CHECK_LAUNCH(); }
-	}
+	hipLaunchKernelGGL(hao_rs_verdict_kernel, go, b_, 0, c->stream, A, G.rbase.p, G.rec.p, io.rs_ovlp->p, G.ctr.p + 5); HAO_CHECK_LAUNCH();
+	HIP_TRY(c->al_k1.reserve(n_ol + 2));      // (al_k1: the upload path's key buffer, free here)
+	hipLaunchKernelGGL(hao_rs_count_kernel, dim3((unsigned)((n_ol + 256) / 256)), b_, 0, c->stream, n_ol, RA.win_off, G.rbase.p, G.rec.p, c->al_k1.p); HAO_CHECK_LAUNCH();
+	if (int rc = hao_excl_scan_u64(c, c->al_k1.p, io.rs_off->p, n_ol + 1)) return rc;
+	hipLaunchKernelGGL(hao_peek_kernel, dim3(1), dim3(64), 0, c->stream, (const unsigned long long*)(io.rs_off->p + n_ol), 1, c->peek_d + 44); HAO_CHECK_LAUNCH();
+	HIP_TRY(hipStreamSynchronize(c->stream));
+	const uint64_t n_wins = c->peek_h[44];
+	HIP_TRY(io.rs_wins->reserve(n_wins + 1));
+	if (n_wins) { hipLaunchKernelGGL(hao_rs_compact_kernel, go, b_, 0, c->stream, n_ol, RA.win_off, G.rbase.p, G.rec.p, io.rs_off->p, io.rs_wins->p); HAO_CHECK_LAUNCH(); }
 	hipLaunchKernelGGL(hao_peek_kernel, dim3(1), dim3(64), 0, c->stream, (const unsigned long long*)(G.ctr.p + 5), 1, c->peek_d + 43); HAO_CHECK_LAUNCH();
 	HIP_TRY(hipStreamSynchronize(c->stream));
-	c->rs_total = c->peek_h[43]; c->rs_rounds = rounds; c->rs_active = na; c->rs_slots = ns;
+	c->rs_total = c->peek_h[43]; c->rs_rounds = rounds; c->rs_active = na; c->rs_slots = ns; c->rs_nw = n_wins;
 	if (G.path.cap > (1ULL << 27)) G.path.release();      // (more than 1 GB of column scratch is not kept between calls)
 	return HAO_OK;
 }
 
-// the window lists (hao_wlist.cuh; hao_window_wlist_ref and HAO_DELIVER_WLIST, hao_batch.hpp): over the n_ol overlaps of the batch whose rescue stage has just
-// run - RA, werr as for hao_al_rescue; pe per slot, the rescue records and their region starts in c->rs; ov = the per-overlap results; n_slots = the batch's
-// covered windows (the bound of the records, so that nothing the plan writes is sized by a count read).  Results into o_woff (records per overlap, scanned),
-// o_wins, o_cigoff and o_cig: the context's own buffers (blocking) or the output set's (streamed: its copy runs under the next batch's compute, which reuses the
-// scratch in c->wl).  out: records, windows swept, re-placement sweeps, cigar entries, untraced windows.  Host round trips: one for the sizes of the sort,
-// the rows and the cigar array, one for the totals at the end (which the streamed path needs to size its arena part).
-int hao_al_wlist(hao_ctx *c, const hao_ovlp_t *ol, uint64_t n_ol, uint32_t wl, hao_ref_args RA, const uint8_t *werr, const hao_rs_ovlp *ov, uint64_t n_slots, uint64_t out[5],
-		DevBuf<uint64_t> &o_woff, DevBuf<hao_rs_win> &o_wins, DevBuf<uint64_t> &o_cigoff, DevBuf<uint16_t> &o_cig)
+// the window lists (hao_wlist.cuh; hao_wlist_run, hao_batch.hpp): over the overlaps of a batch whose rescue stage has just run (io; at least one overlap and one
+// covered window) - the CSR, shifts and error bytes in c->rf; pe per slot, the rescue records and their region starts in c->rs; the per-overlap results in
+// io.rs_ovlp; io.n_slots bounds the records, so that nothing the plan writes is sized by a count read.  Results into io.wl_woff (records per overlap, scanned),
+// io.wl_wins, io.wl_cigoff and io.wl_cig; c->wl_out: records, windows swept, re-placement sweeps, cigar entries, untraced windows.  Host round trips: one for the
+// sizes of the sort, the rows and the cigar array, one for the totals at the end (which the streamed path needs to size its arena part).
+int hao_al_wlist(hao_ctx *c, const hao_ref_io &io)
 {
+	const hao_ovlp_t *ol = io.ol; const uint64_t n_ol = io.n_ol, n_slots = io.n_slots; const uint32_t wl = io.wl; uint64_t *out = c->wl_out;
+	DevBuf<uint64_t> &o_woff = *io.wl_woff, &o_cigoff = *io.wl_cigoff; DevBuf<hao_rs_win> &o_wins = *io.wl_wins; DevBuf<uint16_t> &o_cig = *io.wl_cig;
 	hao_ctx::Wlist &G = c->wl;
 	if (n_slots >= (1ULL << 28)) { hao_set_err(c, "window lists: more than 2^28 covered windows in one batch"); return HAO_EUNSUPP; }
 	HIP_TRY(G.cnt.reserve(n_ol + 2)); HIP_TRY(o_woff.reserve(n_ol + 2)); HIP_TRY(G.plan.reserve(n_slots + 1)); HIP_TRY(o_wins.reserve(n_slots + 1)); HIP_TRY(G.ncig.reserve(n_slots + 2));
 	HIP_TRY(o_cigoff.reserve(n_slots + 2)); HIP_TRY(G.key.reserve(n_slots + 1)); HIP_TRY(G.key2.reserve(n_slots + 1)); HIP_TRY(G.idx.reserve(n_slots + 1)); HIP_TRY(G.sel.reserve(n_slots + 1));
 	HIP_TRY(G.rowof.reserve(n_slots + 1)); HIP_TRY(G.ctr.reserve(8));
 	HIP_TRY(hipMemsetAsync(G.ctr.p, 0, 64, c->stream));
-	hao_wl_args W; W.A.ol = ol; W.A.n_ol = n_ol; W.A.wl = wl; W.A.win_off = RA.win_off; W.A.shift = RA.shift; W.A.tab = RA.tab; W.A.werr = werr; W.A.wpe = c->rs.wpe.p; W.A.len = hao_al_reads_of(c).len;
-	W.rbase = c->rs.rbase.p; W.rec = c->rs.rec.p; W.ov = ov;
+	hao_wl_args W; W.A.ol = ol; W.A.n_ol = n_ol; W.A.wl = wl; W.A.win_off = c->rf.woff.p; W.A.shift = c->rf.shift.p; W.A.tab = io.tab; W.A.werr = c->rf.werr.p; W.A.wpe = c->rs.wpe.p; W.A.len = hao_al_reads_of(c).len;
+	W.rbase = c->rs.rbase.p; W.rec = c->rs.rec.p; W.ov = io.rs_ovlp->p;
 	// sort key of a record that needs a sweep: query read << wbits | grid window (a read has fewer than 2^32 / wl windows)
 	uint32_t wbits = 32; while (wbits > 1 && (wl >> (32 - wbits + 1))) --wbits;
 	hao_read_view V; (void)hao_reads_view(c, &V);
@@ -304,8 +297,7 @@ int hao_window_ed_batch(hao_ctx *c, const hao_ed_task_t *tasks, uint64_t n_tasks
 	if (!c || (!tasks && n_tasks) || (!out && n_tasks)) return HAO_EINVAL;
 	if (int rc = hao_view_refresh(c)) return rc;
 	HAO_STAGE_VIEW(c, V, "hao_window_ed_batch needs the bases of both reads");
-	c->al_grid_n = 0;      // (the task / result scratch is shared with hao_window_ed_grid: what that call left is gone)
-	c->tg_valid = false;      // (and hao_window_trace_grid's results follow the same rule)
+	c->win.on_host_fed();      // (the task / result scratch is shared with the grid calls: what they left is gone, and hao_window_trace_grid's results follow the same rule)
 	if (n_tasks == 0) return HAO_OK;
 	if (n_tasks >= (1ULL << 32)) { hao_set_err(c, "hao_window_ed_batch: more than 2^32 tasks in one call"); return HAO_EUNSUPP; }
 	uint32_t words = 0;      // bit (nword - 1): some band needs nword 64-bit words (the reference's cal_exz_infi picks nword = ceil((2 thre + 1) / 64), Correct.cpp:14508-14565)
@@ -338,7 +330,7 @@ int hao_window_trace_batch(hao_ctx *c, int mode, const hao_ed_task_t *tasks, uin
 	if (!c || (mode < HAO_ALIGN_GLOBAL || mode > HAO_ALIGN_SEMI) || (!tasks && n_tasks) || (!out && n_tasks) || (!cigars && n_tasks && cigar_cap)) return HAO_EINVAL;
 	if (int rc = hao_view_refresh(c)) return rc;
 	HAO_STAGE_VIEW(c, V, "hao_window_trace_batch needs the bases of both reads");
-	c->al_grid_n = 0; c->tg_valid = false;
+	c->win.on_host_fed();
 	if (n_tasks == 0) return HAO_OK;
 	if (n_tasks >= (1ULL << 32)) { hao_set_err(c, "hao_window_trace_batch: more than 2^32 tasks in one call"); return HAO_EUNSUPP; }
 	uint64_t tn_max = 1; uint32_t words = 0;      // bit (nword - 1): some band needs nword 64-bit words

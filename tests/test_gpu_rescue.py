@@ -6,8 +6,9 @@ fail at first placement), none left out:
   * on the sampled reads of five cases they equal tests/golden/rescue.npz, recorded from the reference's own functions;
   * the categories of the rescue a case is known to hold are met (EXPECT: forward and backward windows, a failed backward step, backward runs stopped by cs and by
     ys < 0, a leading gap, an early exit, a verdict 0 without an exit, a verdict 1 that the rescue made); each case prints what it met;
-  * the blocking contract: HAO_EINVAL without hao_window_ed_ref on the batch, after another window-alignment call, after a new batch; fetch argument errors;
-    HAO_DELIVER_TRACE on a reference-placed context still fails with HAO_EUNSUPP.
+  * the blocking contract: HAO_EINVAL without hao_window_ed_ref on the batch, after another window-alignment call - host-fed, or hao_window_ed_grid whatever
+    its pair count - after a new batch; fetch argument errors; HAO_DELIVER_TRACE on a reference-placed context still fails with HAO_EUNSUPP;
+  * the residency table of the window-alignment calls, row by row on one engine.
 Streamed (HAO_DELIVER_OL | HAO_DELIVER_ED | HAO_DELIVER_RESCUE after hao_deliver_ed_config_ref, batches of 64 and 257 reads): what hao_unpack_rescue hands back equals
 the blocking path's results over the same ranges; a batch without the part, before and after one with it, has the byte count and contents it has without
 the feature, and the part adds exactly 16 bytes per overlap, the offsets and 16 bytes per record; HAO_DELIVER_RESCUE without HAO_DELIVER_ED or on a
@@ -34,6 +35,8 @@ EXPECT = {("hifi", 775, 0.004): ("forward", "backward", "backward_failed", "back
           ("fz2", 1500, 0.006): ("forward_failed", "backward", "exit")}           # (more than 31 errors in a full window: the only way a forward step fails)
 # cases that tests/golden/rescue.npz (the reference's own functions, make_golden_rescue.py) holds on a sample of their reads
 GOLD = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "rescue.npz"))
+# hao_window_ed_grid(775, GRID_THRE) forms as many pairs on the hifi set as hao_window_ed_ref(775, 0.04): the count a stale-input check by pair count cannot tell apart
+GRID_THRE = 31
 GOLD_KEY = {("hifi", 775, 0.04): "hifi", ("ont", 375, 0.07): "ont", ("hifi", 775, 0.004): "hifi004", ("ont", 375, 0.015): "ont015", ("fz2", 1500, 0.006): "fz2w"}
 
 
@@ -81,6 +84,10 @@ def test_rescue_blocking_equals_the_model(name, wl, e_rate):
             got_total += a; n_ol += b; k += m
         assert k == n and got_total == total
         assert n_ol > 100
+        ends = [rs.n - 1] + [r for r in range(rs.n) if e.h_ec_lchain(r)[0].shape[0] == 0][:1]      # the two ends of the records' CSR: the batch's last read, a read without overlaps
+        for r in ends:
+            ov, wins = e.fetch_rescue(r)
+            assert ov.shape[0] == len(wins) == e.h_ec_lchain(r)[0].shape[0], r
         print(f"[rescue] {name} ({wl}, {e_rate}): {n} pairs, {int((R[:, 0] != NOALN).sum())} aligned, {total} windows rescued in {n_ol} overlaps; {dict(sorted(seen.items()))}")
         gk = GOLD_KEY.get((name, wl, e_rate))
         if gk:                                                   # the real reference on the sampled reads
@@ -127,6 +134,13 @@ def test_contract():
         with pytest.raises(HaoError, match=r"\(-2\)"):
             e.fetch_rescue(3)
         e.window_rescue_ref()
+        n_ref, _ = e.window_ed_ref(775, 0.04)                                  # a diagonal-placed grid call takes the shared scratch: refused whatever its pair count
+        n_grid = e.window_ed_grid(775, GRID_THRE)
+        print(f"[rescue] contract: {n_ref} pairs of hao_window_ed_ref, {n_grid} of hao_window_ed_grid(775, {GRID_THRE})")
+        with pytest.raises(HaoError, match=r"\(-2\)"):
+            e.window_rescue_ref()
+        e.window_ed_ref(775, 0.04)
+        e.window_rescue_ref()
         e.overlap_batch(1, rs.n)                                               # a new batch
         with pytest.raises(HaoError, match=r"\(-2\)"):
             e.fetch_rescue(3)
@@ -135,6 +149,56 @@ def test_contract():
         e.deliver_ed_config_ref(775, 0.04)                                     # the traced stage in reference placement stays refused
         with pytest.raises(HaoError, match=r"\(-4\)"):
             e.overlap_batch_async(0, rs.n, parts=DELIVER_OL | DELIVER_ED | DELIVER_TRACE)
+    finally:
+        e.close()
+
+
+def test_residency_table():
+    """what each window-alignment call leaves resident and what it takes away (the residency table), walked row by row on one engine"""
+    from hifiasm_amd.api import HaoError
+    e, rs = _engine("hifi")
+
+    def refused(f, *a):
+        with pytest.raises(HaoError, match=r"\(-2\)"):
+            f(*a)
+    try:
+        e.overlap_batch(0, rs.n)                                               # a new batch: nothing is resident
+        for f, a in ((e.window_rescue_ref, ()), (e.window_wlist_ref, ()), (e.fetch_ed_ovlp, (3,)), (e.fetch_rescue, (3,)), (e.fetch_wlist, (3,)), (e.fetch_ed_grid, (1,)), (e.fetch_trace_grid, (1, 1))):
+            refused(f, *a)
+        n, _ = e.window_ed_ref(775, 0.004)                                     # hao_window_ed_ref: its pairs in the shared scratch, its summaries
+        T, R = e.fetch_ed_grid(n)
+        s0 = e.fetch_ed_ovlp(3)
+        refused(e.fetch_rescue, 3); refused(e.window_wlist_ref)
+        tg = e.window_trace_grid(775, 20)                                      # hao_window_trace_grid has buffers of its own: the chain goes on, both stay served
+        total = e.window_rescue_ref()
+        assert total > 0
+        tt = e.fetch_trace_grid(tg[0], tg[2])
+        assert tt[0].shape[0] == tg[0] > 0 and int(tt[2][-1]) == tg[2] > 0
+        ov, wins = e.fetch_rescue(3)
+        out = e.window_wlist_ref()
+        wl3 = e.fetch_wlist(3)
+        assert (e.fetch_ed_grid(n)[1] == R).all()                              # (the later stages leave the scratch to hao_window_ed_ref's pairs)
+        e.window_trace_batch(T[:8], cap=80, mode=0)                            # a host-fed call reuses the scratch: what lies in buffers of its own stays served
+        refused(e.fetch_ed_grid, 1); refused(e.fetch_trace_grid, 1, 1); refused(e.fetch_wlist, 3); refused(e.window_wlist_ref)
+        assert (e.fetch_ed_ovlp(3) == s0).all()
+        ov2, wins2 = e.fetch_rescue(3)
+        assert (ov2 == ov).all() and all((a == b).all() for a, b in zip(wins, wins2))
+        refused(e.window_rescue_ref)                                           # the rescue stage's input is gone; a stage that starts drops its own results
+        refused(e.fetch_rescue, 3)
+        assert (e.fetch_ed_ovlp(3) == s0).all()
+        e.window_ed_ref(775, 0.004)                                            # the chain again, to its end
+        assert e.window_rescue_ref() == total and e.window_wlist_ref() == out
+        e.window_trace_grid(775, 20)                                           # (behind the chain: it disturbs nothing)
+        assert len(e.fetch_wlist(3)) == len(wl3)
+        g = e.window_ed_grid(775, 20)                                          # hao_window_ed_grid takes the scratch: the lists and both stages' input go with it
+        assert g > 0 and e.fetch_ed_grid(g)[0].shape[0] == g
+        refused(e.fetch_wlist, 3); refused(e.window_wlist_ref)
+        assert (e.fetch_ed_ovlp(3) == s0).all() and (e.fetch_rescue(3)[0] == ov).all()
+        assert e.fetch_trace_grid(tg[0], tg[2])[0].shape[0] == tg[0]
+        refused(e.window_rescue_ref)
+        e.overlap_batch(0, 0)                                                  # a batch without reads: every stage runs and has nothing to report
+        assert e.window_ed_ref(775, 0.04) == (0, 0) and e.window_rescue_ref() == 0 and e.window_wlist_ref() == (0, 0, 0, 0, 0)
+        refused(e.fetch_rescue, 0)                                             # (no read to fetch)
     finally:
         e.close()
 

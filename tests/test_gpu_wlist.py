@@ -8,8 +8,8 @@ read sets, none left out:
   * out[1] equals the model's count of windows in the domain whose record has err > 0 (windows with err == 0 are not swept), out[0] / out[3] / out[4] the
     records, entries and untraced windows of the model;
   * records of backward-rescued windows and anchors carry hao_fetch_rescue's y_start, y_end, err and re-placed bit; the rescue results stay fetchable.
-Contract: HAO_EINVAL without hao_window_ed_ref and hao_window_rescue_ref on the batch, after another window-alignment call, after a new batch; a second call
-gives the same result; fetch argument errors; HAO_EUNSUPP from both entry points in a sharded engine.
+Contract: HAO_EINVAL without hao_window_ed_ref and hao_window_rescue_ref on the batch, after another window-alignment call - host-fed, or hao_window_ed_grid
+whatever its pair count (the rescue results stay fetchable) - after a new batch; a second call gives the same result; fetch argument errors; HAO_EUNSUPP from both entry points in a sharded engine.
 Streamed (HAO_DELIVER_OL | HAO_DELIVER_ED | HAO_DELIVER_RESCUE | HAO_DELIVER_WLIST after hao_deliver_ed_config_ref, batches of 64 and 257 reads): what
 hao_unpack_wlist hands back equals the blocking path's lists over the same ranges; a batch without the part, before and after one with it, has the bytes it has
 without the feature, and the part adds exactly the record offsets, 16 bytes per record, the entry offsets and 2 bytes per entry (each padded to 64 bytes in the
@@ -152,6 +152,18 @@ def test_contract():
         with pytest.raises(HaoError, match=r"\(-2\)"):
             e.fetch_wlist(3)
         e.window_wlist_ref()
+        GRID_THRE = 31                                                         # (as many pairs as hao_window_ed_ref forms here: tests/test_gpu_rescue.py)
+        n_ref, _ = e.window_ed_ref(775, 0.04)                                  # a diagonal-placed grid call takes the shared scratch: refused whatever its pair count
+        e.window_rescue_ref(); e.window_wlist_ref()
+        ov, wins = e.fetch_rescue(3)
+        n_grid = e.window_ed_grid(775, GRID_THRE)
+        print(f"[wlist] contract: {n_ref} pairs of hao_window_ed_ref, {n_grid} of hao_window_ed_grid(775, {GRID_THRE})")
+        with pytest.raises(HaoError, match=r"\(-2\)"):
+            e.window_wlist_ref()
+        with pytest.raises(HaoError, match=r"\(-2\)"):
+            e.fetch_wlist(0)
+        ov2, wins2 = e.fetch_rescue(3)                                         # (the rescue results lie in buffers of their own)
+        assert (ov2 == ov).all() and all((a == b).all() for a, b in zip(wins, wins2))
         e.overlap_batch(1, rs.n)                                               # a new batch
         with pytest.raises(HaoError, match=r"\(-2\)"):
             e.fetch_wlist(3)
