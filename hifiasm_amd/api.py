@@ -81,7 +81,7 @@ PLACE_DIAG, PLACE_REF = 0, 1      # hao_ed_delivery_t::placement
 ABI_SYMBOLS = [
     "hao_opt_default", "hao_create", "hao_destroy", "hao_last_error", "hao_set_reads", "hao_ft_gen", "hao_pt_gen",
     "hao_ft_cnt", "hao_pt_get", "hao_ft_table", "hao_pt_table", "hao_hist", "hao_stats", "hao_sketch_batch",
-    "hao_fetch_sketch", "hao_overlap_batch", "hao_fetch_seed_hits", "hao_fetch_overlaps", "hao_batch_totals", "hao_batch_seed_path",
+    "hao_fetch_sketch", "hao_overlap_batch", "hao_fetch_seed_hits", "hao_fetch_overlaps", "hao_batch_totals", "hao_batch_seed_path", "hao_batch_chain_path",
     "hao_stage_times", "hao_pass_default", "hao_overlap_batch_ex", "hao_set_shard", "hao_dist_unique_id", "hao_dist_init",
     "hao_loop_create", "hao_loop_destroy", "hao_dist_init_loopback", "hao_batch_digest", "hao_selftest_rocprim", "hao_selftest_big", "hao_selftest_sortbits", "hao_unpack_cigar", "hao_unpack_overlaps", "hao_overlap_batch_async", "hao_deliver_wait", "hao_unpack_hits", "hao_exact_check", "hao_fetch_exact", "hao_window_ed_batch", "hao_index_save", "hao_index_load", "hao_next_slot", "hao_attach", "hao_window_trace_batch", "hao_delivery_digest", "hao_ft_passes", "hao_ovlp_bin_read", "hao_ovlp_bin_write", "hao_window_ed_grid", "hao_fetch_ed_grid",
     "hao_deliver_ed_config", "hao_deliver_ed", "hao_unpack_ed",
@@ -211,6 +211,7 @@ def lib():
         L.hao_fetch_overlaps.argtypes = [vp, C.c_uint64, C.POINTER(vp), u64p, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), u64p]
         L.hao_batch_totals.argtypes = [vp, u64p]
         L.hao_batch_seed_path.argtypes = [vp, u64p]
+        L.hao_batch_chain_path.argtypes = [vp, u64p]
         L.hao_stage_times.argtypes = [vp, C.POINTER(C.c_char_p), C.POINTER(C.c_float), C.c_int]
         L.hao_batch_digest.argtypes = [vp, u64p, u64p]
         L.hao_overlap_batch_async.argtypes = [vp, C.c_uint64, C.c_uint64, C.POINTER(Pass), C.c_uint32, C.POINTER(C.c_int)]
@@ -763,6 +764,13 @@ class Engine:
         out = (C.c_uint64 * 4)()
         self._ck(self.L.hao_batch_seed_path(self.h, out), "hao_batch_seed_path")
         return dict(first_launch={0: "seed_bin_kernel", 1: "(unused)", 2: "seed_lds_kernel"}[int(out[0])], left_to_tables=int(out[1]), overflow_512=int(out[2]), overflow_1024=int(out[3]))
+
+    def batch_chain_path(self):
+        """which kernels carried the last batch's chain stage: (groups per size class - up to 8 / 64 / 128 / 256 / 512 / 2048 hits and beyond -, and of those the groups
+        the quick check handed to the DP kernel of their class), two lists of seven"""
+        out = (C.c_uint64 * 16)()
+        self._ck(self.L.hao_batch_chain_path(self.h, out), "hao_batch_chain_path")
+        return [int(x) for x in out[0:7]], [int(x) for x in out[7:14]]
 
     def batch_digest(self, n, with_seed_hits=True):
         """per-read digests of the last batch (n reads): (digest of ol / fake cigars / cl, digest of the seed hits or None)"""

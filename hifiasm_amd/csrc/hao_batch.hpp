@@ -9,6 +9,7 @@
 
 struct hao_ctx::Batch {
 	uint64_t n_generic = 0, n_generic_hits = 0, seed_path = 0, seed_left[3] = {0, 0, 0}; DevBuf<unsigned long long> stats, dbgbuf;
+	uint64_t cls_n[HAO_NCLS] = {0, 0, 0, 0, 0, 0, 0}, slow_n[HAO_NCLS] = {0, 0, 0, 0, 0, 0, 0};      // the chain stage's census (hao_batch_chain_path): groups per size class, and those the quick check left to the class's DP kernel
 	uint64_t lo = 0, n = 0, mz0 = 0, n_mz = 0, n_anchor = 0, n_groups = 0, n_chains = 0, n_cl = 0, n_fc_raw = 0, n_ol = 0, n_fc = 0, n_fcw = 0;
 	bool valid = false, host_valid = false;
 	DevBuf<uint64_t> s_start, s_pk, a_off, seg, g_cnt, g_off, g_start, ch_base, cl_base, fc_base, fcs, fc_raw, ol_fc_off, cc_off, cc, fc_final, fcf_off;
@@ -744,6 +745,7 @@ static int hao_overlap_run(hao_ctx *c, uint64_t lo, uint64_t hi, const hao_pass_
 	B.n_exc = n_exc;
 	B.n_generic = 0; for (int x = 0; x < HAO_NCLS; ++x) B.n_generic += slow_st[x];
 	B.n_generic_hits = slow_st[HAO_NCLS];
+	for (int x = 0; x < HAO_NCLS; ++x) { B.cls_n[x] = cls_cnt[x]; B.slow_n[x] = slow_st[x]; }
 	if (c->sw.dp_stats) { fprintf(stderr, "[dp] slow groups by class:"); for (int x = 0; x < HAO_NCLS; ++x) fprintf(stderr, " %llu/%llu", slow_st[x], cls_cnt[x]);
 		fprintf(stderr, "  hits %llu  dp range %llu  spec-committed %llu  spec-failures %llu\n", slow_st[HAO_NCLS], slow_st[HAO_NCLS + 3], slow_st[HAO_NCLS + 1], slow_st[HAO_NCLS + 2]); }
 	B.valid = true;

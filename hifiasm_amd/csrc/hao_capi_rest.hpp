@@ -698,6 +698,15 @@ int hao_batch_seed_path(hao_ctx *c, uint64_t out[4])
 	return HAO_OK;
 }
 
+int hao_batch_chain_path(hao_ctx *c, uint64_t out[16])
+{
+	if (!c || !out || !c->batch || !c->batch->valid) return HAO_EINVAL;
+	hao_ctx::Batch &B = *c->batch;
+	for (int x = 0; x < HAO_NCLS; ++x) { out[x] = B.cls_n[x]; out[HAO_NCLS + x] = B.slow_n[x]; }
+	out[2 * HAO_NCLS] = B.n_generic_hits; out[2 * HAO_NCLS + 1] = 0;
+	return HAO_OK;
+}
+
 int hao_batch_digest(hao_ctx *c, uint64_t *out, uint64_t *out_kh)
 {
 	if (!c || !out || !c->batch || !c->batch->valid) return HAO_EINVAL;

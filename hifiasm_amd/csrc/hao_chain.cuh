@@ -380,8 +380,8 @@ __device__ __forceinline__ hao_hit_t hao_shfl_up_hit(const hao_hit_t &h)      //
 // One wave per (query,target) group.
 // Fast path (data-parallel): every strand block passes quick_ck_lchain - a segmented prefix sum of pair
 // scores with per-pair validity flags - and no second chain qualifies for multi-copy output; then the best
-// block IS the chain: hits are copied through, the fake cigar is a flagged compaction.  >99.9 % of groups on
-// repeat-free genomes.  Everything else runs hao_chain_generic on lane 0 (exact sequential algorithm).
+// block IS the chain: hits are copied through, the fake cigar is a flagged compaction.  >99.9 % of groups on repeat-free genomes.  Every other group goes to the
+// class's slow list (slow[], counted in A.stats[cls]) for the DP kernel of its class: chain_dp128_kernel, chain_dp_kernel<512> or <HAO_DP_CAP> (hao_batch.hpp).
 __global__ __launch_bounds__(64) __attribute__((amdgpu_num_sgpr(96))) void chain_group_kernel(hao_chain_args A, const hao_gent *list, uint64_t n_list, uint32_t *slow, int cls)
 {
 	const uint64_t li = blockIdx.x;      // (one 64-thread workgroup per group)

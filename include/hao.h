@@ -180,6 +180,11 @@ int hao_batch_totals(hao_ctx *c, uint64_t out[8]);
  * out[0] = first launch: 2 the list-major kernel (hao_query5.cuh), 1 unused (round 5's one-wave merge kernel), 0 the table kernels for every read;
  * out[1] = reads that launch left to the table kernels, out[2] / out[3] = reads whose bins overflowed the 512- / the 1024-slot table */
 int hao_batch_seed_path(hao_ctx *c, uint64_t out[4]);
+/* which kernels carried the chain stage (h_ec_lchain's chaining of one (query, target) group of seed hits) of the last batch - the results do not depend on it.
+ * Groups are routed by their number of hits: class 0 = 1 .. 8, 1 = 9 .. 64, 2 = 65 .. 128, 3 = 129 .. 256, 4 = 257 .. 512, 5 = 513 .. 2048, 6 = more.
+ * out[0 .. 6] = groups of each class, out[7 .. 13] = of those, the groups the data-parallel quick check did not settle and handed to the DP kernel of their
+ * class (class 0: to the one-lane-per-group pass), out[14] = seed hits of the handed-over groups, out[15] = 0 */
+int hao_batch_chain_path(hao_ctx *c, uint64_t out[16]);
 
 /* A second (third ...) batch context over the same reads and index: own stream, scratch and result buffers, nothing else.  Batches on different
  * contexts are independent, so one host thread per context keeps two batches in flight on the device: the seed stage of one (memory-bound) runs under

@@ -13,6 +13,11 @@ What is stored (small enough for git):
   * for a sample of reads (default 256, evenly spread): the minimizers, ol->list and fake cigars verbatim + their per-read digests.
 Reads are NOT stored: hifiasm_amd.synth regenerates them (deterministic C generator); CRCs of the lengths and of the first packed
 megabyte detect drift.
+
+A scenario of tests/scenarios.py whose verbatim fixture (make_golden.py) would be too large for git takes the same form (scenarios.DIGEST_SCENARIOS):
+    python tests/golden/make_golden_big.py cedge [n_sample]
+stores the per-read digests of ALL reads unfolded, the k-mer histogram of ha_ft_gen next to the one of ha_pt_gen, the sampled reads as above, and a CRC of the
+base codes.
 """
 import json
 import os
@@ -32,10 +37,50 @@ from hifiasm_amd import synth  # noqa: E402
 from hifiasm_amd.workloads import WORKLOADS, LEN_JIT, workload_reads  # noqa: E402
 from helpers import fold_digests  # noqa: E402
 import oracle_py  # noqa: E402
+import scenarios  # noqa: E402
+
+
+def scenario_main(name, n_sample):
+    """digest-form fixture of a small scenario: every read's digests, a sample of reads verbatim (always with the scenario's `always` reads)"""
+    harness = os.path.join(ROOT, "oracle", "_ref", "ref_harness")
+    assert os.path.exists(harness)
+    dkw, okw = scenarios.SCENARIOS[name]
+    assert not okw, "default options only"
+    rs = scenarios.build_reads(dkw)
+    d = tempfile.mkdtemp(prefix="hao_golddig_", dir=os.environ.get("HAO_TMP", "/tmp"))
+    fa = os.path.join(d, "r.fa")
+    synth.write_fasta(fa, rs)
+    step = max(1, rs.n // n_sample)
+    sample = np.array(sorted(set(range(step // 2, rs.n, step)) | set(scenarios.DIGEST_SCENARIOS[name])), dtype=np.uint64)
+    with open(os.path.join(d, "list.txt"), "w") as fp:
+        fp.write("\n".join(str(int(x)) for x in sample) + "\n")
+    cmd = [harness, "-t", "2", "--time", "--dump", os.path.join(d, "s"), "--reads-list", os.path.join(d, "list.txt"), "--no-tables", "--ft-tables", "--nodump-hits", "--digest", fa]
+    r = subprocess.run(cmd, capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-3000:]
+    tj = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+    pre = os.path.join(d, "s")
+    ld = lambda nm, dt: np.fromfile(f"{pre}.{nm}", dtype=dt)  # noqa: E731
+    meta = oracle_py.load_ref_meta(pre)
+    dig = ld("dig.u64", np.uint64).reshape(-1, 2)
+    assert dig.shape[0] == rs.n
+    out = dict(
+        sample=sample, mz_off=ld("mz_off.u64", np.uint64), mz=ld("mz.u64", np.uint64).reshape(-1, 2),
+        ol_off=ld("ol_off.u64", np.uint64), ol=ld("ol.u32", np.uint32).reshape(-1, 12), fc_off=ld("fc_off.u64", np.uint64), fc=ld("fc.u64", np.uint64),
+        pt_hist=ld("pt_hist.i64", np.int64), ft_hist=ld("ft_hist.i64", np.int64), dig=dig,
+        meta_keys=np.array(list(meta.keys()) + ["pass_overlaps", "pass_chained_hits"]),
+        meta_vals=np.array(list(meta.values()) + [tj["overlaps"], tj["chained_hits"]], dtype=np.int64),
+        codes_crc=np.array([zlib.crc32(rs.codes.tobytes())], dtype=np.uint64), rlen=rs.lengths,
+    )
+    path = os.path.join(HERE, f"{name}.npz")
+    np.savez_compressed(path, **out)
+    print(name, json.dumps(tj), "->", os.path.getsize(path) // 1024, "KiB")
+    shutil.rmtree(d)
 
 
 def main():
     name = sys.argv[1] if len(sys.argv) > 1 else "chr1_250M_hifi30x"
+    if name in scenarios.DIGEST_SCENARIOS:
+        return scenario_main(name, int(sys.argv[2]) if len(sys.argv) > 2 else 32)
     n_sample = int(sys.argv[2]) if len(sys.argv) > 2 else 256
     bf = int(sys.argv[3]) if len(sys.argv) > 3 else 0
     harness = os.path.join(ROOT, "oracle", "_ref", "ref_harness")

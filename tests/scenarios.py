@@ -34,6 +34,8 @@ SCENARIOS = {
     "exact": (dict(genome_size=60_000, coverage=16, read_len=4000, err=0.0002, seed=18, len_jit=1500, n_rate=0.0001), dict(bw_thres=0.001)),
     # ragged / degenerate reads mixed into a normal set (see edge_reads below)
     "edge":  (dict(builder="edge"), {}),
+    # every size class of the chain stage at its capacity edges, on the quick-check path and on the DP path (see chain_edge_reads below)
+    "cedge": (dict(builder="cedge"), {}),
     # off-default (k, w) pairs and option mixes, chosen to leave the tuned paths: small k with a narrow window, the largest k (63) with a window wider than
     # the wave kernel's chunk overlap and no HPC, ONT mode with N bases, a tiny Bloom filter on a repeat-rich set, error-free reads, and k = 57 (the widest
     # k the one-word window kernel takes) at the default w
@@ -44,6 +46,10 @@ SCENARIOS = {
     "fz4":   (dict(genome_size=25_000, coverage=25, read_len=1800, err=0.0, seed=44, len_jit=600), dict(k=45, w=25)),
     "fz5":   (dict(genome_size=35_000, coverage=15, read_len=4500, err=0.003, seed=45, len_jit=1000), dict(k=57, w=51)),
 }
+
+
+# scenarios whose fixture holds per-read digests and a sample of reads instead of every read's lists (tests/golden/make_golden_big.py): {name: reads always in the sample}
+DIGEST_SCENARIOS = {"cedge": (400,)}
 
 
 def edge_reads():
@@ -87,18 +93,136 @@ def len65535_reads():
     return synth.from_codes(reads)
 
 
+# ---- scenario "cedge": crafted (query, target) groups of seed hits at the chain stage's capacity edges ----
+CEDGE_Q = (20_000, 150_000)      # the query read Q = genome[20 000 : 150 000]
+CEDGE_QID = 400                  # its read id: behind the 400 ordinary reads, in front of the crafted targets (target i = read 401 + i)
+CEDGE_CLASS_MAX = (8, 64, 128, 256, 512, 2048)      # hao_size_class (hao_query.cuh): class x holds the groups of up to CEDGE_CLASS_MAX[x] hits, class 6 the larger ones
+# (shape, start in Q, length of the substring of Q, cut, bases left out, hits of the (Q, target) group, of those on the forward strand) - tuned by
+# tests/golden/make_cedge_table.py, never at import time; tests/test_chain_classes_cpu.py fails when the oracle's group sizes leave this table
+CEDGE_TABLE = [
+    ('plain', 127250, 114, 57, 0, 1, 1),
+    ('plain', 127000, 356, 178, 0, 8, 8),
+    ('plain', 127000, 391, 195, 0, 9, 9),
+    ('plain', 93000, 2160, 1129, 0, 63, 63),
+    ('plain', 104750, 2147, 1147, 0, 64, 64),
+    ('plain', 125000, 2219, 1164, 0, 65, 65),
+    ('plain', 123000, 4599, 2237, 0, 127, 127),
+    ('plain', 122750, 4586, 2254, 0, 128, 128),
+    ('plain', 122750, 4636, 2271, 0, 129, 129),
+    ('plain', 120750, 6707, 3361, 0, 192, 192),
+    ('plain', 97237, 9322, 4468, 0, 256, 256),
+    ('plain', 118500, 8638, 4486, 0, 257, 257),
+    ('plain', 32250, 17733, 8897, 0, 512, 512),
+    ('plain', 109500, 17285, 8914, 0, 513, 513),
+    ('plain', 0, 71652, 35453, 0, 2047, 2047),
+    ('plain', 56500, 70675, 35470, 0, 2048, 2048),
+    ('plain', 0, 71706, 35487, 0, 2049, 2049),
+    ('plain', 54250, 72693, 36577, 0, 2112, 2112),
+    ('plain', 6250, 121242, 60590, 0, 3500, 3500),
+    ('swap', 127000, 480, 240, 0, 8, 8),
+    ('del', 125974, 1464, 232, 1000, 8, 8),
+    ('inv', 127000, 481, 240, 0, 8, 5),
+    ('swap', 127000, 485, 242, 0, 9, 9),
+    ('del', 126000, 1491, 245, 1000, 9, 9),
+    ('inv', 127000, 485, 242, 0, 9, 5),
+    ('swap', 29237, 2306, 1153, 0, 64, 64),
+    ('del', 37000, 3403, 1201, 1000, 64, 64),
+    ('inv', 84750, 2480, 1240, 0, 64, 30),
+    ('swap', 125000, 2329, 1164, 0, 65, 65),
+    ('del', 124000, 3500, 1250, 1000, 65, 65),
+    ('inv', 125000, 2329, 1164, 0, 65, 34),
+    ('swap', 34250, 4516, 2258, 0, 128, 128),
+    ('del', 18750, 5726, 2363, 1000, 128, 128),
+    ('inv', 90250, 4757, 2378, 0, 128, 62),
+    ('swap', 24500, 4698, 2349, 0, 129, 129),
+    ('del', 121750, 5551, 2275, 1000, 129, 129),
+    ('inv', 80000, 4706, 2353, 0, 129, 61),
+    ('swap', 10000, 9138, 4569, 0, 256, 256),
+    ('del', 0, 10032, 4516, 1000, 256, 256),
+    ('inv', 71000, 8603, 4301, 0, 256, 132),
+    ('swap', 0, 9123, 4561, 0, 257, 257),
+    ('del', 117500, 9961, 4480, 1000, 257, 257),
+    ('inv', 41250, 8800, 4400, 0, 257, 129),
+    ('swap', 88250, 18230, 9115, 0, 512, 512),
+    ('del', 0, 19106, 9053, 1000, 512, 512),
+    ('inv', 109500, 17304, 8652, 0, 512, 256),
+    ('swap', 19000, 18326, 9163, 0, 513, 513),
+    ('del', 108500, 18596, 8798, 1000, 513, 513),
+    ('inv', 75000, 17922, 8961, 0, 513, 262),
+    ('swap', 0, 71827, 35913, 0, 2048, 2048),
+    ('del', 0, 75320, 35660, 4000, 2048, 2048),
+    ('inv', 56500, 70707, 35353, 0, 2048, 1025),
+    ('swap', 56500, 70693, 35346, 0, 2049, 2049),
+    ('del', 52500, 74635, 35317, 4000, 2049, 2049),
+    ('inv', 0, 71817, 35908, 0, 2049, 1024),
+    ('swap', 6250, 121383, 60691, 0, 3500, 3500),
+    ('del', 0, 125304, 60652, 4000, 3500, 3500),
+    ('inv', 0, 121615, 60807, 0, 3500, 1745),
+    ('inv', 49500, 4819, 2219, 0, 128, 63),
+    ('inv', 81250, 4524, 2208, 0, 128, 64),
+    ('inv', 25250, 4770, 2631, 0, 128, 65),
+    ('inv', 47250, 4559, 2203, 0, 129, 63),
+    ('inv', 102500, 4512, 2347, 0, 129, 64),
+    ('inv', 0, 4683, 2367, 0, 129, 65),
+]
+
+
+def cedge_class(n):
+    """hao_size_class of a group of n hits"""
+    return sum(n > m for m in CEDGE_CLASS_MAX)
+
+
+def cedge_target(q, shape, start, length, cut, gap):
+    """one crafted target: the substring s = q[start : start + length] as it is ("plain"), with the parts on both sides of `cut` exchanged ("swap": the group's
+    hits leave the diagonal order), with `gap` bases behind `cut` left out ("del": a jump of the diagonal beyond the band), or with the part behind `cut`
+    reverse-complemented ("inv": a group of two strand blocks)"""
+    import numpy as np
+    s = q[start:start + length]
+    if shape == "plain":
+        return s.copy()
+    if shape == "swap":
+        return np.concatenate([s[cut:], s[:cut]])
+    if shape == "del":
+        return np.concatenate([s[:cut], s[cut + gap:]])
+    if shape == "inv":
+        return np.concatenate([s[:cut], (3 - s[cut:][::-1]).astype(np.uint8)])
+    raise ValueError(shape)
+
+
+def chain_edge_reads(table=None):
+    """400 reads of 6 kb +- 1 kb at 0.1 % error over a 200 kb genome (an ordinary k-mer histogram), the error-free query read Q = genome[20 000 : 150 000], and the
+    targets of CEDGE_TABLE: substrings of Q whose group of seed hits with Q has exactly 1, 8, 9, 63 .. 2049, 2112 and 3500 hits - both sides of every capacity
+    edge of the chain stage's seven size classes and of its 64-hit tiles -, plain (the quick check accepts them) and rearranged (it rejects them, or a second
+    chain qualifies for multi-copy output: the DP kernel of the class), among them inversions whose strand boundary lies on the last lane of a tile, on the first
+    and on the second.  table: another table than the committed one (the tuning script)."""
+    from hifiasm_amd import synth
+    g = synth.make_genome(200_000, seed=91)
+    base = synth.make_reads(g, 400, 6000, 0.001, seed=92, len_jit=1000)
+    reads = [base.codes[int(base.code_off[i]):int(base.code_off[i + 1])].copy() for i in range(base.n)]
+    assert len(reads) == CEDGE_QID
+    q = g[CEDGE_Q[0]:CEDGE_Q[1]].copy()
+    reads.append(q)
+    for row in (CEDGE_TABLE if table is None else table):
+        reads.append(cedge_target(q, *row[:5]))
+    return synth.from_codes(reads)
+
+
 def build_reads(dkw):
     """the read set of a scenario: synth.dataset(**dkw), or a hand-made set"""
     from hifiasm_amd import synth
     if dkw.get("builder") == "edge":
         return edge_reads()
+    if dkw.get("builder") == "cedge":
+        return chain_edge_reads()
     if dkw.get("builder") == "len65535":
         return len65535_reads()
     return synth.dataset(**dkw)
 
 
 # larger sets used only by the GPU parity tests (oracle vs HIP, no golden file): enough repeat content to push
-# thousands of groups through the chain DP / multi-copy / max_n_chain code, and 15 kb reads through the chunked sketch
+# thousands of groups through the chain DP / multi-copy / max_n_chain code, and 15 kb reads through the chunked sketch.
+# Which size class and which kernel a group of these random sets takes is what the comments below expect, not what a test asserts: scenario "cedge"
+# (chain_edge_reads; tests/test_gpu_chain_classes.py) is the set that holds every class at its edges on both paths, and asserts it through the engine's census
 BIG_SCENARIOS = {
     "rr_big":   (dict(genome_size=400_000, coverage=30, read_len=8000, err=0.001, seed=5, repeat_rich=1, len_jit=2000), {}),
     "hifi_15k": (dict(genome_size=300_000, coverage=25, read_len=15000, err=0.001, seed=21, len_jit=3000), {}),

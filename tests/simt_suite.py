@@ -11,7 +11,7 @@ import pytest
 import simt_build
 from scenarios import BIG_SCENARIOS
 
-BIG = set(BIG_SCENARIOS) | ({"rr", "bf24", "f37", "bw001rr", "fz3"} if not os.environ.get("HAO_SIMT_FULL") else set())      # + the repeat-rich sets: 40 - 130 s each on the emulator
+BIG = set(BIG_SCENARIOS) | ({"rr", "bf24", "f37", "bw001rr", "fz3", "cedge"} if not os.environ.get("HAO_SIMT_FULL") else set())      # + the repeat-rich sets: 40 - 130 s each on the emulator; cedge (4 Mb of reads, 2.5 M seed hits) has a twin of its own, test_simt_chain_classes_cpu.py
 
 
 def _is_big(v):

@@ -1,13 +1,15 @@
 """Pin the C restatement (oracle/hao_oracle.c) against golden dumps of the REAL
 reference (tests/golden/*.npz, produced by tests/golden/make_golden.py from
-oracle/_ref/ref_harness = unmodified hifiasm sources).  CPU only."""
+oracle/_ref/ref_harness = unmodified hifiasm sources).  CPU only.  A scenario whose verbatim dump would be too large for git
+(scenarios.DIGEST_SCENARIOS; tests/golden/make_golden_big.py) is pinned through the reference's digest of EVERY read's seed hits and of every read's result (overlap
+list, fake cigars, chained hits), and through a sample of reads verbatim."""
 import numpy as np
 import pytest
 
-from helpers import scenario_reads, scenario_oracle, load_golden, crc
-from scenarios import SCENARIOS
+from helpers import scenario_reads, scenario_oracle, load_golden, crc, digest_result, digest_hits
+from scenarios import SCENARIOS, DIGEST_SCENARIOS
 
-NAMES = list(SCENARIOS)
+NAMES = [n for n in SCENARIOS if n not in DIGEST_SCENARIOS]
 
 
 @pytest.mark.parametrize("name", NAMES)
@@ -69,3 +71,32 @@ def test_seed_hits_and_chains(name):
         assert cl.shape[0] == int(g["cl_off"][r + 1] - g["cl_off"][r])
         assert crc(cl) == int(g["cl_crc"][r]), f"chained hits of read {r}"
         assert (o.exact(ol) == g["ex"][s:e]).all(), f"exact-overlap flags of read {r}"      # exact_ec_check on the reference's own strings (ecovlp.cpp:2803, 5124-5131)
+
+
+@pytest.mark.parametrize("name", list(DIGEST_SCENARIOS))
+def test_digest_fixture(name):
+    rs, _ = scenario_reads(name)
+    g = load_golden(name)
+    assert crc(rs.codes) == int(g["codes_crc"][0]) and (g["rlen"] == rs.lengths).all()
+    o = scenario_oracle(name)
+    M = g["meta"]
+    assert (o.ft_hist() == g["ft_hist"]).all() and (o.pt_hist() == g["pt_hist"]).all()
+    st = o.stats()
+    for key in ("hom_cov", "het_cov", "max_n_chain", "high_occ", "low_occ", "ft_peak_hom", "ft_peak_het"):
+        assert st[key] == M[key], key
+    assert g["dig"].shape == (o.n_reads, 2) and set(DIGEST_SCENARIOS[name]) <= set(int(x) for x in g["sample"])
+    tot_ol = tot_cl = 0
+    for r in range(o.n_reads):      # every read: the reference's digests
+        assert digest_hits(o.seed_hits(r)) == g["dig"][r, 1], f"seed hits of read {r}"
+        ol, fc, fo, cl = o.lchain(r)
+        assert digest_result(ol, fc, cl) == g["dig"][r, 0], f"overlaps / fake cigars / chained hits of read {r}"
+        tot_ol += ol.shape[0]; tot_cl += cl.shape[0]
+    assert (tot_ol, tot_cl) == (M["pass_overlaps"], M["pass_chained_hits"])
+    mz, ol_all = g["mz"].reshape(-1, 2), g["ol"].reshape(-1, 12)
+    for i, r in enumerate(int(x) for x in g["sample"]):      # the sample: verbatim
+        a = o.sketch(r); b = mz[int(g["mz_off"][i]):int(g["mz_off"][i + 1])]
+        assert a.shape == b.shape and (a == b).all(), f"minimizers of read {r}"
+        ol, fc, fo, cl = o.lchain(r)
+        s, e = int(g["ol_off"][i]), int(g["ol_off"][i + 1])
+        assert ol.shape == ol_all[s:e].shape and (ol == ol_all[s:e]).all(), f"overlap list of read {r}"
+        assert (fc == g["fc"][int(g["fc_off"][s]):int(g["fc_off"][e])]).all(), f"fake cigars of read {r}"
