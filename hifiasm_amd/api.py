@@ -89,7 +89,7 @@ ABI_SYMBOLS = [
     "hao_window_ed_ref", "hao_fetch_ed_ovlp", "hao_deliver_ed_config_ref", "hao_ref_thresholds",
     "hao_window_rescue_ref", "hao_fetch_rescue", "hao_rescue_task", "hao_deliver_rescue", "hao_unpack_rescue",
     "hao_window_wlist_ref", "hao_fetch_wlist", "hao_deliver_wlist", "hao_unpack_wlist",
-    "hao_dist_gather_reads", "hao_reads_digest",
+    "hao_dist_gather_reads", "hao_reads_digest", "hao_index_load_dist", "hao_shard_layout",
 ]
 
 
@@ -221,6 +221,8 @@ def lib():
         L.hao_window_trace_batch.argtypes = [vp, C.c_int, vp, C.c_uint64, vp, vp, C.c_uint32]
         L.hao_index_save.argtypes = [vp, C.c_char_p, C.c_int32, vp]
         L.hao_index_load.argtypes = [vp, C.c_char_p, C.POINTER(C.c_int32)]
+        L.hao_index_load_dist.argtypes = [vp, C.c_char_p, u64p, C.POINTER(C.c_int32)]
+        L.hao_shard_layout.argtypes = [vp, u64p, u64p, u64p, C.POINTER(u32p)]
         L.hao_fetch_exact.argtypes = [vp, C.c_uint64, C.POINTER(vp), u64p]
         L.hao_unpack_hits.argtypes = [C.POINTER(Delivery), C.c_uint64, vp, C.c_uint64]; L.hao_unpack_hits.restype = C.c_uint64
         L.hao_unpack_cigar.argtypes = [C.POINTER(Delivery), C.c_uint64, vp, C.c_uint32]; L.hao_unpack_cigar.restype = C.c_uint32
@@ -611,14 +613,28 @@ class Engine:
         self._ck(self.L.hao_delivery_digest(C.byref(d), out.ctypes.data_as(C.POINTER(C.c_uint64)), int(threads or min(32, os.cpu_count() or 1))), "hao_delivery_digest")
         return out
 
-    def index_save(self, prefix, number_of_round=3):
-        """write <prefix>.pt_flt / .pt_flt.bin / .pt_flt.paf.bin in the reference's resume format (write_pt_index, htab.cpp:1367)"""
-        self._ck(self.L.hao_index_save(self.h, prefix.encode(), number_of_round, None), "hao_index_save")
+    def index_save(self, prefix, number_of_round=3, names=None):
+        """write <prefix>.pt_flt / .pt_flt.bin / .pt_flt.paf.bin in the reference's resume format (write_pt_index, htab.cpp:1367).  On a sharded engine a
+        collective: every rank calls it, rank 0 writes (it needs the gathered store, dist_gather_reads).  names: one str / bytes per GLOBAL read (rank 0's are read)"""
+        arr = None
+        if names is not None:
+            arr = (C.c_char_p * len(names))(*[n if isinstance(n, bytes) else str(n).encode() for n in names])
+        self._ck(self.L.hao_index_save(self.h, prefix.encode(), number_of_round, arr), "hao_index_save")
 
-    def index_load(self, prefix):
-        """hao_index_load: read store + filter table + position index from <prefix>.pt_flt[.bin] -> number_of_round stored in the file"""
+    def index_load(self, prefix, cuts=None):
+        """hao_index_load / hao_index_load_dist: read store + filter table + position index from <prefix>.pt_flt[.bin] -> number_of_round stored in the file.
+        On a sharded engine a collective; cuts: world + 1 first read ids in rank order (None: near-equal read counts).  n_reads, rid_base and lengths are
+        set as set_readset and set_shard set them: the local reads' count and lengths, the global id of the first"""
         r = C.c_int32(0)
-        self._ck(self.L.hao_index_load(self.h, prefix.encode(), C.byref(r)), "hao_index_load")
+        if cuts is None:
+            self._ck(self.L.hao_index_load(self.h, prefix.encode(), C.byref(r)), "hao_index_load")
+        else:
+            fr = np.ascontiguousarray(cuts, dtype=np.uint64)
+            self._ck(self.L.hao_index_load_dist(self.h, prefix.encode(), fr.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(r)), "hao_index_load_dist")
+        n, base, tot, al = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.POINTER(C.c_uint32)()
+        self._ck(self.L.hao_shard_layout(self.h, C.byref(n), C.byref(base), C.byref(tot), C.byref(al)), "hao_shard_layout")
+        self.n_reads, self.rid_base = int(n.value), int(base.value)
+        self.lengths = _arr(al, tot.value, np.uint32)[self.rid_base:self.rid_base + self.n_reads]
         return r.value
 
     def window_trace_batch(self, tasks, cap=80, mode=0):

@@ -293,14 +293,25 @@ int hao_next_slot(hao_ctx *c, int *slot)
 	return HAO_OK;
 }
 
-int hao_index_load(hao_ctx *c, const char *prefix, int32_t *number_of_round)
+int hao_index_load_dist(hao_ctx *c, const char *prefix, const uint64_t *first_rid, int32_t *number_of_round)
 {
 	if (!c || !prefix) return HAO_EINVAL;
 	HAO_NOT_ON_VIEW(c, "hao_index_load");
 	HIP_TRY(hipSetDevice(c->device));
-	try { return hao_index_load_impl(c, prefix, number_of_round); }      // (the loader sizes host vectors from file fields - checked against the file's length, but an exception must not cross the C boundary)
-	catch (const std::bad_alloc &) { c->has_ft = false; c->has_pt = false; c->lk_valid = false; hao_set_err(c, "hao_index_load: out of host memory"); return HAO_ENOMEM; }
-	catch (const std::exception &e) { c->has_ft = false; c->has_pt = false; c->lk_valid = false; hao_set_err(c, std::string("hao_index_load: ") + e.what()); return HAO_EINVAL; }
+	return hao_index_load_impl(c, prefix, first_rid, number_of_round);      // (its local phases turn their exceptions into codes: none crosses the C boundary or leaves a peer waiting)
+}
+
+int hao_index_load(hao_ctx *c, const char *prefix, int32_t *number_of_round) { return hao_index_load_dist(c, prefix, nullptr, number_of_round); }
+
+int hao_shard_layout(hao_ctx *c, uint64_t *n_reads, uint64_t *rid_base, uint64_t *n_total, const uint32_t **all_len)
+{
+	if (!c) return HAO_EINVAL;
+	if (int rc = hao_view_refresh(c)) return rc;
+	if (n_reads) *n_reads = c->n_reads;
+	if (rid_base) *rid_base = c->rid_base;
+	if (n_total) *n_total = c->n_total;
+	if (all_len) *all_len = c->h_len_all.data();
+	return HAO_OK;
 }
 
 int hao_exact_check(hao_ctx *c)

@@ -9,6 +9,8 @@
 #pragma once
 #include <cstdio>
 #include <sys/stat.h>
+#include <new>
+#include <stdexcept>
 #include <string>
 #include <vector>
 
@@ -37,10 +39,19 @@ static bool hao_kh_write(FILE *fp, const std::vector<uint64_t> &keys, const void
 		   fwrite(used.data(), 4, used.size(), fp) == used.size() && fwrite(&ff, 1, 1, fp) == 1 && fwrite(bk.data(), bsz, n_buckets, fp) == n_buckets;
 }
 
-static int hao_index_save_impl(hao_ctx *c, const char *prefix, int32_t number_of_round, const char *const *names)
+// a local phase of the two calls below that sizes host vectors: its exceptions become its status, which travels with the next status exchange
+// (a sharded engine's peers are waiting in it) and never crosses the C boundary
+template<typename F> static int hao_no_throw(hao_ctx *c, const char *what, F f)
 {
-	if (!c->has_ft || !c->has_pt) { hao_set_err(c, "hao_index_save: hao_ft_gen and hao_pt_gen must have run"); return HAO_EINVAL; }
-	if (hao_is_sharded(c)) { hao_set_err(c, "hao_index_save: single-device mode only (a sharded engine holds a slice of the read store)"); return HAO_EUNSUPP; }
+	try { return f(); }
+	catch (const std::bad_alloc &) { hao_set_err(c, std::string(what) + ": out of host memory"); return HAO_ENOMEM; }
+	catch (const std::exception &e) { hao_set_err(c, std::string(what) + ": " + e.what()); return HAO_EINVAL; }
+}
+
+// The writer of the three files: the tables from the engine's host views (hao_pt_download), the reads from the store the view names - the local store of an
+// unsharded engine, the gathered store of a sharded one (hao_ctx.hpp: hao_reads_view), whose entries are global read ids either way.  Serial host code.
+static int hao_index_write(hao_ctx *c, const hao_read_view &V, const char *prefix, int32_t number_of_round, const char *const *names)
+{
 	if (int rc = hao_pt_download(c)) return rc;
 	const std::string base = std::string(prefix) + ".pt_flt";
 	FILE *fp = fopen(base.c_str(), "wb");
@@ -73,28 +84,34 @@ static int hao_index_save_impl(hao_ctx *c, const char *prefix, int32_t number_of
 		ok = ok && fwrite(&number_of_round, 4, 1, fp) == 1 && fwrite(&hom, 4, 1, fp) == 1 && fwrite(&het, 4, 1, fp) == 1 && fwrite(&mnc, 4, 1, fp) == 1; }
 	fclose(fp);
 	if (!ok) { hao_set_err(c, "short write on " + base); return HAO_EINVAL; }
-	// ---- the read store (write_All_reads, Process_Read.cpp:69-125) ----
-	const uint64_t n = c->n_reads;
-	std::vector<uint8_t> packed(c->n_pk_bytes + 1); std::vector<uint64_t> pk_off(n + 1); std::vector<uint32_t> ns;
-	HIP_TRY(hipMemcpy(packed.data(), c->d_packed.p, c->n_pk_bytes, hipMemcpyDeviceToHost));
-	HIP_TRY(hipMemcpy(pk_off.data(), c->d_pk_off.p, (n + 1) * 8, hipMemcpyDeviceToHost));
-	if (c->has_n) { ns.resize(c->h_nsite_off[n] + 1); HIP_TRY(hipMemcpy(ns.data(), c->d_nsite.p, c->h_nsite_off[n] * 4, hipMemcpyDeviceToHost)); }
+	// ---- the read store (write_All_reads, Process_Read.cpp:69-125): the view's offsets say where a read's bytes and N sites lie, its last entries how many there are ----
+	const uint64_t n = V.n;
+	std::vector<uint64_t> pk_off(n + 1), ns_off; std::vector<uint8_t> packed; std::vector<uint32_t> ns;
+	HIP_TRY(hipMemcpy(pk_off.data(), V.pk_off, (n + 1) * 8, hipMemcpyDeviceToHost));
+	packed.resize(pk_off[n] + 1);
+	if (pk_off[n]) HIP_TRY(hipMemcpy(packed.data(), V.packed, pk_off[n], hipMemcpyDeviceToHost));
+	if (V.nsite_off) {
+		ns_off.resize(n + 1);
+		HIP_TRY(hipMemcpy(ns_off.data(), V.nsite_off, (n + 1) * 8, hipMemcpyDeviceToHost));
+		ns.resize(ns_off[n] + 1);
+		if (ns_off[n]) HIP_TRY(hipMemcpy(ns.data(), V.nsite, ns_off[n] * 4, hipMemcpyDeviceToHost));
+	}
 	fp = fopen((base + ".bin").c_str(), "wb");
 	if (!fp) { hao_set_err(c, "cannot write " + base + ".bin"); return HAO_EINVAL; }
 	{
-		const int32_t adapter = 0; const uint64_t index_size = n, name_index_size = n + 1, total_bases = c->n_bases; uint64_t total_name = 0;
+		const int32_t adapter = 0; const uint64_t index_size = n, name_index_size = n + 1; uint64_t total_bases = 0, total_name = 0;
 		std::vector<uint64_t> name_index(n + 1, 0), len64(n); std::string all_names;
-		for (uint64_t i = 0; i < n; ++i) { const std::string nm = names && names[i] ? std::string(names[i]) : "r" + std::to_string(i); name_index[i] = all_names.size(); all_names += nm; len64[i] = c->h_len[i]; }
+		for (uint64_t i = 0; i < n; ++i) { const std::string nm = names && names[i] ? std::string(names[i]) : "r" + std::to_string(i); name_index[i] = all_names.size(); all_names += nm; len64[i] = V.h_len[i]; total_bases += V.h_len[i]; }
 		name_index[n] = total_name = all_names.size();
 		ok = fwrite(&adapter, 4, 1, fp) == 1 && fwrite(&index_size, 8, 1, fp) == 1 && fwrite(&name_index_size, 8, 1, fp) == 1 && fwrite(&n, 8, 1, fp) == 1 &&
 			 fwrite(&total_bases, 8, 1, fp) == 1 && fwrite(&total_name, 8, 1, fp) == 1;
 		for (uint64_t i = 0; i < n && ok; ++i) {      // N sites: count, then positions (u64)
-			uint64_t cnt = c->has_n ? c->h_nsite_off[i + 1] - c->h_nsite_off[i] : 0;
+			uint64_t cnt = V.nsite_off ? ns_off[i + 1] - ns_off[i] : 0;
 			ok = fwrite(&cnt, 8, 1, fp) == 1;
-			for (uint64_t j = 0; j < cnt && ok; ++j) { const uint64_t p = ns[c->h_nsite_off[i] + j]; ok = fwrite(&p, 8, 1, fp) == 1; }
+			for (uint64_t j = 0; j < cnt && ok; ++j) { const uint64_t p = ns[ns_off[i] + j]; ok = fwrite(&p, 8, 1, fp) == 1; }
 		}
 		ok = ok && fwrite(len64.data(), 8, n, fp) == n;
-		for (uint64_t i = 0; i < n && ok; ++i) ok = fwrite(&packed[pk_off[i]], 1, c->h_len[i] / 4 + 1, fp) == c->h_len[i] / 4 + 1;
+		for (uint64_t i = 0; i < n && ok; ++i) ok = fwrite(&packed[pk_off[i]], 1, V.h_len[i] / 4 + 1, fp) == V.h_len[i] / 4 + 1;
 		std::vector<uint8_t> trio(n, 0);      // AMBIGU is re-set by the loader (htab.cpp:1519)
 		const int32_t hom = c->hom_cov, het = c->het_cov;
 		ok = ok && (total_name == 0 || fwrite(all_names.data(), 1, total_name, fp) == total_name) && fwrite(name_index.data(), 8, n + 1, fp) == n + 1 &&
@@ -107,9 +124,27 @@ static int hao_index_save_impl(hao_ctx *c, const char *prefix, int32_t number_of
 	if (!fp) { hao_set_err(c, "cannot write " + base + ".paf.bin"); return HAO_EINVAL; }
 	ok = fwrite(&n, 8, 1, fp) == 1;
 	{ const uint8_t z8 = 0; const uint32_t z32 = 0; for (uint64_t i = 0; i < n && ok; ++i) ok = fwrite(&z8, 1, 1, fp) == 1 && fwrite(&z8, 1, 1, fp) == 1 && fwrite(&z32, 4, 1, fp) == 1; }
-	fclose(fp);
+	ok = (fclose(fp) == 0) && ok;
 	if (!ok) { hao_set_err(c, "short write on " + base + ".paf.bin"); return HAO_EINVAL; }
 	return HAO_OK;
+}
+
+// hao_index_save.  An unsharded engine writes.  A sharded one makes it a collective: every rank holds the replicated tables and - after hao_dist_gather_reads -
+// the whole read store, so rank 0 writes what one engine over all reads would; the ranks agree on whether they are ready before a file is created, and on
+// rank 0's result afterwards (hao_comm.hpp: the ranks fail together), so a peer's return also says that the files are complete.
+static int hao_index_save_impl(hao_ctx *c, const char *prefix, int32_t number_of_round, const char *const *names)
+{
+	hao_read_view V;
+	auto ready = [&]() -> int {
+		if (!c->has_ft || !c->has_pt) { hao_set_err(c, "hao_index_save: hao_ft_gen and hao_pt_gen must have run"); return HAO_EINVAL; }
+		if (!hao_reads_view(c, &V)) { hao_set_err(c, "hao_index_save: a sharded engine holds a slice of the read store - hao_dist_gather_reads must have run"); return HAO_EUNSUPP; }
+		return HAO_OK;
+	};
+	auto write = [&]() -> int { return hao_no_throw(c, "hao_index_save", [&]() -> int { return hao_index_write(c, V, prefix, number_of_round, names); }); };
+	if (!hao_is_sharded(c)) { if (int rc = ready()) return rc; return write(); }
+	hao_comm &cm = *c->comm;
+	if (int rc = hao_comm_agree(c, cm, ready())) return rc;
+	return hao_comm_agree(c, cm, cm.rank == 0 ? write() : HAO_OK);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -156,16 +191,27 @@ __global__ void hao_lk_fill_kernel(const uint64_t *mz_x, uint64_t n_mz, hao_pt_d
 }
 
 
-static int hao_index_load_impl(hao_ctx *c, const char *prefix, int32_t *number_of_round)
+// The loader in three parts, shared by both kinds of engine: the table file into host vectors, the read store's file into the slice of reads the engine is
+// to own (all of them: an unsharded engine), and the installation of both.  The first two only read files, the third only touches the engine.
+struct hao_idx_tables {
+	struct Ent { uint64_t hash; uint32_t sub, cnt; uint64_t off; };
+	std::vector<uint64_t> ftk; std::vector<int32_t> ftv;                      // filter table, keys ascending
+	std::vector<Ent> ents; std::vector<std::vector<uint64_t> > pos;           // position index: the keys and the sub-tables' position arrays
+	int32_t rounds = 0, hom = -1, het = -1, mnc = 100;
+};
+struct hao_idx_reads {
+	uint64_t n_total = 0, lo = 0, hi = 0;                                    // reads in the file, the slice [lo, hi)
+	std::vector<uint32_t> len_all;                                            // lengths of all reads
+	std::vector<uint64_t> pk_off, ns_off; std::vector<uint32_t> ns; std::vector<uint8_t> packed;      // the slice, offsets from its first read
+};
+
+static int hao_idx_parse_tables(hao_ctx *c, const std::string &base, hao_idx_tables &T)
 {
-	if (hao_is_sharded(c)) { hao_set_err(c, "hao_index_load: single-device mode only"); return HAO_EUNSUPP; }
-	c->has_ft = false; c->has_pt = false; c->lk_valid = false; c->h_ix_valid = false;      // a load that fails half-way leaves "no index", not the previous one over new reads
-	const std::string base = std::string(prefix) + ".pt_flt";
+	typedef hao_idx_tables::Ent Ent;
 	FILE *fp = fopen(base.c_str(), "rb");
 	if (!fp) { hao_set_err(c, "cannot read " + base); return HAO_EINVAL; }
-	auto bad = [&](const std::string &what) { if (fp) fclose(fp); hao_set_err(c, "hao_index_load: " + what); return HAO_EINVAL; };
+	auto bad = [&](const std::string &what) { fclose(fp); hao_set_err(c, "hao_index_load: " + what); return HAO_EINVAL; };
 	char mode = 0; bool have_ft = false, have_pt = false;
-	std::vector<uint64_t> ftk; std::vector<int32_t> ftv;
 	if (fread(&mode, 1, 1, fp) != 1) return bad("empty " + base);
 	if (mode == 'f') {
 		std::vector<uint64_t> k; std::vector<uint8_t> v;
@@ -177,73 +223,108 @@ static int hao_index_load_impl(hao_ctx *c, const char *prefix, int32_t *number_o
 			kv[i] = std::make_pair(k[i], x == INT16_MAX ? INT32_MAX : (int32_t)x);
 		}
 		std::sort(kv.begin(), kv.end());
-		ftk.resize(kv.size()); ftv.resize(kv.size());
-		for (size_t i = 0; i < kv.size(); ++i) { ftk[i] = kv[i].first; ftv[i] = kv[i].second; }
+		T.ftk.resize(kv.size()); T.ftv.resize(kv.size());
+		for (size_t i = 0; i < kv.size(); ++i) { T.ftk[i] = kv[i].first; T.ftv[i] = kv[i].second; }
 		have_ft = true;
 		if (fread(&mode, 1, 1, fp) != 1) mode = 0;
 	}
-	struct Ent { uint64_t hash; uint32_t sub, cnt; uint64_t off; };
-	std::vector<Ent> ents; std::vector<std::vector<uint64_t> > pos;
 	if (mode == 'h') {
 		int32_t k = 0, pre = 0; uint64_t tot = 0, tot_pos = 0;
 		if (fread(&k, 4, 1, fp) != 1 || fread(&pre, 4, 1, fp) != 1 || fread(&tot, 8, 1, fp) != 1 || fread(&tot_pos, 8, 1, fp) != 1 || pre < 0 || pre > 20) return bad("index header of " + base);
 		if (k != c->opt.k) return bad("the index was built with k = " + std::to_string(k) + ", the engine runs with k = " + std::to_string(c->opt.k));
 		if (tot > hao_file_left(fp) / 16 || tot_pos > hao_file_left(fp) / 8) return bad("index header of " + base + ": more keys / positions than the file holds");
-		pos.resize((size_t)1 << pre); ents.reserve(tot);
+		T.pos.resize((size_t)1 << pre); T.ents.reserve(tot);
 		std::vector<uint64_t> kk; std::vector<uint8_t> vv;
 		for (uint32_t s = 0; s < (1u << pre); ++s) {
 			uint64_t na = 0;
 			if (!hao_kh_read(fp, 8, kk, vv) || fread(&na, 8, 1, fp) != 1) return bad("sub-table " + std::to_string(s) + " of " + base);
 			if (na > hao_file_left(fp) / 8) return bad("positions of sub-table " + std::to_string(s) + ": more than the file holds");
-			pos[s].resize(na);
-			if (na && fread(pos[s].data(), 8, na, fp) != na) return bad("positions of sub-table " + std::to_string(s));
+			T.pos[s].resize(na);
+			if (na && fread(T.pos[s].data(), 8, na, fp) != na) return bad("positions of sub-table " + std::to_string(s));
 			for (size_t i = 0; i < kk.size(); ++i) {      // key = hash >> pre << 12 | count (htab.cpp:122-124, 303-314), value = offset of its list
 				Ent e; e.hash = ((kk[i] >> 12) << pre) | s; e.sub = s; e.cnt = (uint32_t)(kk[i] & 4095); memcpy(&e.off, &vv[8 * i], 8);
 				if (e.off > na || e.cnt > na - e.off) return bad("a list of sub-table " + std::to_string(s) + " leaves its position array");
-				ents.push_back(e);
+				T.ents.push_back(e);
 			}
 		}
-		if (ents.size() != tot) return bad("key count of " + base);
+		if (T.ents.size() != tot) return bad("key count of " + base);
 		have_pt = true;
 	}
 	if (!have_ft || !have_pt) return bad(base + " holds no filter table / position index");
-	int32_t rounds = 0, hom = -1, het = -1, mnc = 100;
-	if (fread(&rounds, 4, 1, fp) != 1 || fread(&hom, 4, 1, fp) != 1 || fread(&het, 4, 1, fp) != 1 || fread(&mnc, 4, 1, fp) != 1) return bad("tail of " + base);
-	fclose(fp); fp = nullptr;
-	if (number_of_round) *number_of_round = rounds;
-	// ---- the read store (load_All_reads, Process_Read.cpp:127-232) ----
-	fp = fopen((base + ".bin").c_str(), "rb");
-	if (!fp) { hao_set_err(c, "cannot read " + base + ".bin"); return HAO_EINVAL; }
+	if (fread(&T.rounds, 4, 1, fp) != 1 || fread(&T.hom, 4, 1, fp) != 1 || fread(&T.het, 4, 1, fp) != 1 || fread(&T.mnc, 4, 1, fp) != 1) return bad("tail of " + base);
+	fclose(fp);
+	return HAO_OK;
+}
+
+// The read store (load_All_reads, Process_Read.cpp:127-232) for rank `rank` of `world`: the header, every read's N-site count and length - they say where
+// everything lies - and the N sites and packed bases of the reads [first_rid[rank], first_rid[rank + 1]) alone, reached by seeking; first_rid == nullptr:
+// near-equal read counts in rank order.  (names, trio flags and the second copy of the peaks are not the engine's business)
+static int hao_idx_parse_reads(hao_ctx *c, const std::string &path, const uint64_t *first_rid, int rank, int world, hao_idx_reads &R)
+{
+	FILE *fp = fopen(path.c_str(), "rb");
+	if (!fp) { hao_set_err(c, "cannot read " + path); return HAO_EINVAL; }
+	auto bad = [&](const std::string &what) { fclose(fp); hao_set_err(c, "hao_index_load: " + what); return HAO_EINVAL; };
 	int32_t adapter = 0; uint64_t index_size = 0, name_index_size = 0, n = 0, total_bases = 0, total_name = 0;
 	if (fread(&adapter, 4, 1, fp) != 1 || fread(&index_size, 8, 1, fp) != 1 || fread(&name_index_size, 8, 1, fp) != 1 || fread(&n, 8, 1, fp) != 1 || fread(&total_bases, 8, 1, fp) != 1 ||
-		fread(&total_name, 8, 1, fp) != 1 || n >= (1ULL << 28) || n > hao_file_left(fp) / 16) return bad("header of " + base + ".bin");      // (a read costs at least its N-site count and its length: 16 bytes)
-	std::vector<uint64_t> ns_off(n + 1, 0), len64(n), pk_off(n + 1, 0); std::vector<uint32_t> ns, len(n); std::vector<uint8_t> packed;
+		fread(&total_name, 8, 1, fp) != 1 || n >= (1ULL << 28) || n > hao_file_left(fp) / 16) return bad("header of " + path);      // (a read costs at least its N-site count and its length: 16 bytes)
+	if (n == 0) return bad("no reads");
+	if (first_rid) {
+		bool ok = first_rid[0] == 0 && first_rid[world] == n;
+		for (int r = 0; r < world; ++r) ok = ok && first_rid[r] <= first_rid[r + 1];
+		if (!ok) return bad("first_rid must ascend from 0 to the file's " + std::to_string(n) + " reads");
+	}
+	const uint64_t lo = first_rid ? first_rid[rank] : n * (uint64_t)rank / (uint64_t)world, hi = first_rid ? first_rid[rank + 1] : n * (uint64_t)(rank + 1) / (uint64_t)world, nl = hi - lo;
+	R.n_total = n; R.lo = lo; R.hi = hi;
+	R.ns_off.assign(nl + 1, 0); R.pk_off.assign(nl + 1, 0); R.ns.clear(); R.len_all.resize(n);
 	for (uint64_t i = 0; i < n; ++i) {
 		uint64_t cnt = 0; if (fread(&cnt, 8, 1, fp) != 1 || cnt > hao_file_left(fp) / 8) return bad("N sites of read " + std::to_string(i));
-		for (uint64_t j = 0; j < cnt; ++j) { uint64_t p; if (fread(&p, 8, 1, fp) != 1 || p >= (1ULL << 27)) return bad("N sites of read " + std::to_string(i)); ns.push_back((uint32_t)p); }
-		ns_off[i + 1] = ns.size();
+		if (i < lo || i >= hi) { if (cnt && fseeko(fp, (off_t)(cnt * 8), SEEK_CUR) != 0) return bad("N sites of read " + std::to_string(i)); continue; }
+		for (uint64_t j = 0; j < cnt; ++j) { uint64_t p; if (fread(&p, 8, 1, fp) != 1 || p >= (1ULL << 27)) return bad("N sites of read " + std::to_string(i)); R.ns.push_back((uint32_t)p); }
+		R.ns_off[i - lo + 1] = R.ns.size();
 	}
-	if (n && fread(len64.data(), 8, n, fp) != n) return bad("read lengths");
-	for (uint64_t i = 0; i < n; ++i) { if (len64[i] >= (1ULL << 27)) return bad("read longer than 2^27"); len[i] = (uint32_t)len64[i]; pk_off[i + 1] = pk_off[i] + len64[i] / 4 + 1; }
-	for (uint64_t i = 0; i < n; ++i) for (uint64_t j = ns_off[i]; j < ns_off[i + 1]; ++j) if (ns[j] >= len[i]) return bad("an N site of read " + std::to_string(i) + " lies beyond the read");
-	if (pk_off[n] > hao_file_left(fp)) return bad("packed reads: shorter than the lengths say");
-	packed.resize(pk_off[n] + 1);
-	if (pk_off[n] && fread(packed.data(), 1, pk_off[n], fp) != pk_off[n]) return bad("packed reads");
-	fclose(fp); fp = nullptr;      // (names, trio flags and the second copy of the peaks are not the engine's business)
-	if (int rc = hao_set_reads(c, packed.data(), pk_off.data(), len.data(), n, ns_off.data(), ns.empty() ? nullptr : ns.data())) return rc;
+	uint64_t pk_total = 0, pk_lo = 0;
+	{	std::vector<uint64_t> len64(n);
+		if (fread(len64.data(), 8, n, fp) != n) return bad("read lengths");
+		for (uint64_t i = 0; i < n; ++i) {
+			if (len64[i] >= (1ULL << 27)) return bad("read longer than 2^27");
+			R.len_all[i] = (uint32_t)len64[i];
+			if (i == lo) pk_lo = pk_total;
+			if (i >= lo && i < hi) R.pk_off[i - lo + 1] = R.pk_off[i - lo] + len64[i] / 4 + 1;
+			pk_total += len64[i] / 4 + 1;
+		}
+		if (lo == n) pk_lo = pk_total; }
+	for (uint64_t i = 0; i < nl; ++i) for (uint64_t j = R.ns_off[i]; j < R.ns_off[i + 1]; ++j) if (R.ns[j] >= R.len_all[lo + i]) return bad("an N site of read " + std::to_string(lo + i) + " lies beyond the read");
+	if (pk_total > hao_file_left(fp)) return bad("packed reads: shorter than the lengths say");
+	R.packed.resize(R.pk_off[nl] + 1);
+	if (pk_lo && fseeko(fp, (off_t)pk_lo, SEEK_CUR) != 0) return bad("packed reads");
+	if (R.pk_off[nl] && fread(R.packed.data(), 1, R.pk_off[nl], fp) != R.pk_off[nl]) return bad("packed reads");
+	fclose(fp);
+	return HAO_OK;
+}
+
+// The parsed files become the engine's state: the slice as its read store (and, sharded, its shard layout: what hao_set_reads + hao_set_shard with the file's
+// lengths leave), the tables replicated as hao_pt_gen leaves them after its all-gather, and the query side of the local reads - sketched with the loaded
+// filter table, looked up in the loaded index.  Nothing here communicates.
+static int hao_idx_install(hao_ctx *c, hao_idx_tables &T, const hao_idx_reads &R, bool sharded)
+{
+	typedef hao_idx_tables::Ent Ent;
+	const uint64_t n = R.hi - R.lo;
+	if (int rc = hao_set_reads(c, R.packed.data(), R.pk_off.data(), R.len_all.data() + R.lo, n, R.ns_off.data(), R.ns.empty() ? nullptr : R.ns.data())) return rc;
+	if (sharded) { if (int rc = hao_set_shard(c, R.lo, R.n_total, R.len_all.data())) return rc; }
 	// ---- filter table ----
-	c->h_ft_keys = ftk; c->h_ft_vals = ftv; const uint64_t nf = ftk.size();
+	c->h_ft_keys = T.ftk; c->h_ft_vals = T.ftv; const uint64_t nf = T.ftk.size();
 	HIP_TRY(c->d_ft_keys.reserve(nf + 1)); HIP_TRY(c->d_ft_vals.reserve(nf + 1));
-	if (nf) { HIP_TRY(hipMemcpyAsync(c->d_ft_keys.p, ftk.data(), nf * 8, hipMemcpyHostToDevice, c->stream)); HIP_TRY(hipMemcpyAsync(c->d_ft_vals.p, ftv.data(), nf * 4, hipMemcpyHostToDevice, c->stream)); }
+	if (nf) { HIP_TRY(hipMemcpyAsync(c->d_ft_keys.p, T.ftk.data(), nf * 8, hipMemcpyHostToDevice, c->stream)); HIP_TRY(hipMemcpyAsync(c->d_ft_vals.p, T.ftv.data(), nf * 4, hipMemcpyHostToDevice, c->stream)); }
 	if (int rc = hao_build_bucket(c, c->d_ft_keys.p, nf, 16, c->d_ft_bucket)) return rc;
 	if (int rc = hao_ft_build_hash(c, nf)) return rc;
 	HIP_TRY(hipStreamSynchronize(c->stream));
 	c->has_ft = true; c->ft_peak_hom = -1; c->ft_peak_het = -1; c->ft_cutoff = 0; memset(c->ft_hist, 0, sizeof(c->ft_hist));
 	// ---- position index: keys ascending, every key's list in file order (= (rid, pos) order) ----
+	std::vector<Ent> &ents = T.ents;
 	std::sort(ents.begin(), ents.end(), [](const Ent &a, const Ent &b) { return a.hash < b.hash; });
 	const uint64_t nk = ents.size(); uint64_t np = 0; for (const Ent &e : ents) np += e.cnt;
 	std::vector<uint64_t> keys(nk), start(nk), sinfo(np); std::vector<uint32_t> cnt(nk);
-	{ uint64_t o = 0; for (uint64_t i = 0; i < nk; ++i) { const Ent &e = ents[i]; keys[i] = e.hash; start[i] = o; cnt[i] = e.cnt; memcpy(sinfo.data() + o, pos[e.sub].data() + e.off, (size_t)e.cnt * 8); o += e.cnt; } }
+	{ uint64_t o = 0; for (uint64_t i = 0; i < nk; ++i) { const Ent &e = ents[i]; keys[i] = e.hash; start[i] = o; cnt[i] = e.cnt; memcpy(sinfo.data() + o, T.pos[e.sub].data() + e.off, (size_t)e.cnt * 8); o += e.cnt; } }
 	HIP_TRY(c->d_ix_keys.reserve(nk + 1)); HIP_TRY(c->d_ix_start.reserve(nk + 1)); HIP_TRY(c->d_ix_cnt.reserve(nk + 1)); HIP_TRY(c->d_ix_sinfo.reserve(np + 8));
 	if (nk) { HIP_TRY(hipMemcpyAsync(c->d_ix_keys.p, keys.data(), nk * 8, hipMemcpyHostToDevice, c->stream)); HIP_TRY(hipMemcpyAsync(c->d_ix_start.p, start.data(), nk * 8, hipMemcpyHostToDevice, c->stream));
 			  HIP_TRY(hipMemcpyAsync(c->d_ix_cnt.p, cnt.data(), nk * 4, hipMemcpyHostToDevice, c->stream)); }
@@ -253,7 +334,7 @@ static int hao_index_load_impl(hao_ctx *c, const char *prefix, int32_t *number_o
 	if (int rc = hao_build_bucket(c, c->d_ix_keys.p, nk, bits, c->d_ix_bucket)) return rc;
 	c->ix_bucket_bits = bits;
 	HIP_TRY(hipStreamSynchronize(c->stream));
-	c->hom_cov = hom; c->het_cov = het; c->max_n_chain = mnc; memset(c->pt_hist, 0, sizeof(c->pt_hist));
+	c->hom_cov = T.hom; c->het_cov = T.het; c->max_n_chain = T.mnc; memset(c->pt_hist, 0, sizeof(c->pt_hist));
 	// ---- query side: read-ordered minimizers (with the loaded filter table) and their lookup results ----
 	if (n == 0) { hao_set_err(c, "hao_index_load: no reads"); return HAO_EINVAL; }
 	if (int rc = hao_sketch_run(c, 0, n, 1, c->opt.sample_dist, 1)) return rc;
@@ -269,6 +350,26 @@ static int hao_index_load_impl(hao_ctx *c, const char *prefix, int32_t *number_o
 	HIP_TRY(hipStreamSynchronize(c->stream));
 	c->has_pt = true; c->h_ix_valid = false;
 	return HAO_OK;
+}
+
+// hao_index_load_dist.  Every rank of a sharded engine reads the files itself (a shared file system) and installs its slice; the ranks exchange a status after
+// parsing and again after installing (hao_comm.hpp: the ranks fail together), so a file one rank cannot read is everybody's error and nobody waits for a peer
+// that has returned.  An unsharded engine is the world of one without the exchanges.
+static int hao_index_load_impl(hao_ctx *c, const char *prefix, const uint64_t *first_rid, int32_t *number_of_round)
+{
+	const bool sharded = hao_is_sharded(c);
+	const int rank = sharded ? c->comm->rank : 0, world = sharded ? c->comm->world : 1;
+	c->has_ft = false; c->has_pt = false; c->lk_valid = false; c->h_ix_valid = false;      // a load that fails half-way leaves "no index", not the previous one over new reads
+	const std::string base = std::string(prefix) + ".pt_flt";
+	hao_idx_tables T; hao_idx_reads R;      // (sized from file fields - checked against the file's length first)
+	int rc = hao_no_throw(c, "hao_index_load", [&]() -> int { if (int r = hao_idx_parse_tables(c, base, T)) return r; return hao_idx_parse_reads(c, base + ".bin", first_rid, rank, world, R); });
+	if (sharded) rc = hao_comm_agree(c, *c->comm, rc);
+	if (rc) return rc;
+	if (number_of_round) *number_of_round = T.rounds;
+	rc = hao_no_throw(c, "hao_index_load", [&]() -> int { return hao_idx_install(c, T, R, sharded); });
+	if (sharded) rc = hao_comm_agree(c, *c->comm, rc);
+	if (rc) { c->has_ft = false; c->has_pt = false; c->lk_valid = false; }
+	return rc;
 }
 
 

@@ -111,7 +111,7 @@ int hao_dist_init_loopback(hao_ctx *c, void *grp, int rank);
  *   Calling it again while the store is valid is a no-op (no communication); hao_set_reads and hao_set_shard discard the store (the refusals are back until the
  *   next gather); an attached context (hao_attach) borrows it.  The ranks fail together (a rank whose allocation failed takes part in the status exchange and
  *   all return an error).  Shards that are not contiguous slices in rank order: HAO_EINVAL on every rank.  On an unsharded engine: HAO_OK, nothing is allocated -
- *   the local store is the whole store.  hao_index_save / hao_index_load stay single-device.
+ *   the local store is the whole store.  hao_index_save on a sharded engine needs this store (below).
  *   HAO_DBG_TEST=gather_chunk=N: bytes a rank sends per exchange (default 64 MB; a few KB walk the multi-chunk path on a small read set). */
 int hao_dist_gather_reads(hao_ctx *c);
 /* Digest of the reads as the stages above see them - the local store of an unsharded engine, the gathered store of a sharded one (HAO_EUNSUPP without it) -
@@ -516,14 +516,33 @@ uint64_t hao_unpack_trace(const hao_trace_delivery_t *t, const hao_ed_delivery_t
  *   <prefix>.pt_flt  (write_pt_index, htab.cpp:1367-1430),  <prefix>.pt_flt.bin  (write_All_reads, Process_Read.cpp:69-125 - the layout of *.ec.bin),
  *   <prefix>.pt_flt.paf.bin  (empty overlap lists).
  * names[i] = read names or NULL ("r<i>"); number_of_round must equal the loader's -r (default 3: it exits otherwise, htab.cpp:1501-1505).
- * Needs hao_ft_gen + hao_pt_gen; single-device mode. */
+ * Needs hao_ft_gen + hao_pt_gen (or a loaded index).
+ *   On a sharded engine the call is a COLLECTIVE: every rank calls it, rank 0 writes the three files - from its replicated filter table and position index,
+ *   the gathered read store and the replicated lengths - and they are byte for byte what one unsharded engine over all reads writes (global read ids in the
+ *   position lists, N sites, names, peaks, max_n_chain).  `names` is read on rank 0 only and is indexed by GLOBAL read id; the other ranks may pass NULL.
+ *   The ranks exchange a status before a file is created and after rank 0 has closed the last one, and every rank returns the same code (the ranks fail
+ *   together): a peer's HAO_OK says the files are complete.  Without a valid gathered store (hao_dist_gather_reads): HAO_EUNSUPP on every rank, no file. */
 int hao_index_save(hao_ctx *c, const char *prefix, int32_t number_of_round, const char *const *names);
 /* The reader of the same files = load_pt_index (htab.cpp:1432-1550) for the engine: an index written by a stock hifiasm (write_pt_index) or by
  * hao_index_save becomes the engine's read store (replaces hao_set_reads), filter table and position index (replace hao_ft_gen / hao_pt_gen), with the
  * file's hom_cov / het_cov / max_n_chain; *number_of_round = the value stored in the file.  The read-ordered minimizers of the query side are
  * sketched here with the loaded filter table (the reference re-sketches every query read).  The file's k must equal the engine's; w, HPC and the
- * other options are the caller's to match, as with the reference.  Histograms are not in the file: hao_hist returns zeros afterwards. */
+ * other options are the caller's to match, as with the reference.  Histograms are not in the file: hao_hist returns zeros afterwards.
+ * A load that fails leaves the engine without an index.
+ *   hao_index_load_dist loads into a SHARDED engine (after hao_dist_init / hao_dist_init_loopback; a collective, every rank calls it and reads the files
+ *   itself: a shared file system).  first_rid[world + 1], the same on every rank: rank r is to own the reads [first_rid[r], first_rid[r + 1]); it must ascend
+ *   from 0 to the file's read count (HAO_EINVAL otherwise); NULL: near-equal read counts, rank r owns [n r / world, n (r + 1) / world).  A rank reads the table
+ *   file, the read store's header, every read's N-site count and length, and - by seeking - the N sites and packed bases of its own slice only.  Afterwards the
+ *   engine is what hao_set_reads (the slice), hao_set_shard (the slice's first read, the file's lengths), hao_ft_gen and hao_pt_gen on the same cut leave:
+ *   filter table, position index, peaks and max_n_chain replicated, the query side built for the local reads without communication; a gathered store from
+ *   before the load is discarded, and hao_dist_gather_reads and every stage behind it run as after a build.  The ranks exchange a status after parsing and
+ *   after installing: a file that one rank cannot read or that is damaged, or an invalid first_rid, is the same error on every rank, and nobody waits.
+ *   On an unsharded engine the call is hao_index_load (first_rid: NULL or { 0, read count }); hao_index_load on a sharded engine is this call with NULL. */
 int hao_index_load(hao_ctx *c, const char *prefix, int32_t *number_of_round);
+int hao_index_load_dist(hao_ctx *c, const char *prefix, const uint64_t *first_rid /* world + 1 entries, rank order; NULL: equal read counts */, int32_t *number_of_round);
+/* The engine's current read layout (after hao_set_reads / hao_set_shard or a load): local reads, global id of the first, reads of all ranks, and the engine's
+ * own copy of all lengths (valid until the reads change); any pointer may be NULL. */
+int hao_shard_layout(hao_ctx *c, uint64_t *n_reads, uint64_t *rid_base, uint64_t *n_total, const uint32_t **all_len);
 
 /* <prefix>.ovlp.source.bin / .ovlp.reverse.bin (write_ma_hit_ts / load_ma_hit_ts, Overlaps.cpp:23328-23469): the per-read lists of ma_hit_t the reference builds from the
  * overlap regions AFTER alignment and correction (not a product of this path: the engine serves h_ec_lchain, the reference's own code fills and writes these lists - the
