@@ -43,7 +43,7 @@ int hao_create(int device, const hao_opt_t *opt, hao_ctx **out)
 		int lo_ = 0, hi_ = 0; (void)hipDeviceGetStreamPriorityRange(&lo_, &hi_);
 		if (hipStreamCreateWithPriority(&c->stream, hipStreamDefault, lo_) != hipSuccess) { delete c; return HAO_ENODEV; }
 	}
-	if (hipHostMalloc((void**)&c->peek_h, 512 * 8, hipHostMallocMapped) != hipSuccess || hipHostGetDevicePointer((void**)&c->peek_d, c->peek_h, 0) != hipSuccess) { (void)hipStreamDestroy(c->stream); delete c; return HAO_ENOMEM; }
+	if (hipHostMalloc((void**)&c->peek_h, HAO_PEEK_WORDS * 8, hipHostMallocMapped) != hipSuccess || hipHostGetDevicePointer((void**)&c->peek_d, c->peek_h, 0) != hipSuccess) { (void)hipStreamDestroy(c->stream); delete c; return HAO_ENOMEM; }
 	memset(c->ft_hist, 0, sizeof(c->ft_hist)); memset(c->pt_hist, 0, sizeof(c->pt_hist));
 	*out = c;
 	return HAO_OK;

@@ -773,7 +773,7 @@ int hao_selftest_sortbits(hao_ctx *c, uint64_t n, uint64_t out[4])
 		hipLaunchKernelGGL(hao_selftest_s40_cmp_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, s1.p, s2.p, o1.p, o2.p, n, bad.p);
 		unsigned long long hb = 0;
 		if (hipMemcpyAsync(&hb, bad.p, 8, hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) rc = HAO_ENODEV;
-		out[0] = hb; out[1] = c->peek_h[16]; out[2] = c->peek_h[17]; out[3] = c->peek_h[18];
+		out[0] = hb; for (int k = 0; k < 3; ++k) out[1 + k] = c->peeked(PK_SORT40, k);
 	}
 	return rc;
 }

@@ -147,7 +147,7 @@ struct hao_chain_args {
 	hao_chain_par par;
 	int32_t *f, *ii, *p; int64_t *t;             // per-hit scratch
 	hao_hit_t *ohits; uint64_t *fcs; hao_chain_rec *rec; uint32_t *nch, *nout;
-	unsigned long long *stats;                   // [0 .. HAO_NCLS) groups of each size class needing the DP kernel, [HAO_NCLS] their hits
+	unsigned long long *stats;                   // the batch's counter block (hao_stat, hao_query.cuh)
 	int32_t *tm;                                 // per-hit mark scratch for oversize groups
 	int dbg_seq, dbg_stats;          // dbg_seq: 1 one-lane sequential chaining, 3 one-lane DP tail, 4 no speculative tiles (all give identical results)
 	unsigned long long *dbg_qc;   // optional phase timers of chain_group_kernel (HAO_DBG_PRINT=qc)
@@ -381,7 +381,7 @@ __device__ __forceinline__ hao_hit_t hao_shfl_up_hit(const hao_hit_t &h)      //
 // Fast path (data-parallel): every strand block passes quick_ck_lchain - a segmented prefix sum of pair
 // scores with per-pair validity flags - and no second chain qualifies for multi-copy output; then the best
 // block IS the chain: hits are copied through, the fake cigar is a flagged compaction.  >99.9 % of groups on repeat-free genomes.  Every other group goes to the
-// class's slow list (slow[], counted in A.stats[cls]) for the DP kernel of its class: chain_dp128_kernel, chain_dp_kernel<512> or <HAO_DP_CAP> (hao_batch.hpp).
+// class's slow list (slow[], counted in A.stats[HAO_ST_SLOW + cls]) for the DP kernel of its class: chain_dp128_kernel, chain_dp_kernel<512> or <HAO_DP_CAP> (hao_batch.hpp).
 __global__ __launch_bounds__(64) __attribute__((amdgpu_num_sgpr(96))) void chain_group_kernel(hao_chain_args A, const hao_gent *list, uint64_t n_list, uint32_t *slow, int cls)
 {
 	const uint64_t li = blockIdx.x;      // (one 64-thread workgroup per group)
@@ -527,7 +527,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_num_sgpr(96))) void chain
 	if (!fast) {
 		// the DP decides this group's chains: the codes written above describe none of them (a void 0xff would only become a useless verbatim-list entry)
 		if (hcg) for (int32_t i = lane; i < a_n; i += 64) hcg[i] = 0x08;
-		if (lane == 0) { unsigned long long si_ = atomicAdd(A.stats + cls, 1ULL); atomicAdd(A.stats + HAO_NCLS, (unsigned long long)a_n); slow[si_] = (uint32_t)li; A.nch[g] = 0; A.nout[g] = 0; }
+		if (lane == 0) { unsigned long long si_ = atomicAdd(A.stats + HAO_ST_SLOW + cls, 1ULL); atomicAdd(A.stats + HAO_ST_SLOW_HITS, (unsigned long long)a_n); slow[si_] = (uint32_t)li; A.nch[g] = 0; A.nout[g] = 0; }
 		return;
 	}
 	// ---- single chain = the whole best block ----
@@ -622,13 +622,13 @@ __global__ __launch_bounds__(256) void chain_pack8_kernel(hao_chain_args A, cons
 		const int64_t min_sc = (int64_t)((double)msc * A.par.mcopy_rate);        // plus == 0 here: every f >= span > 0
 		if ((int64_t)(best ? maxf0 : maxf1) >= min_sc) fast = false;             // a second chain may qualify: exact sequential path
 	}
-	{	// The groups the check does not settle go to the class's slow list (one atomic per wave; A.stats[0] counts them like chain_group_kernel's classes) and
+	{	// The groups the check does not settle go to the class's slow list (one atomic per wave; A.stats[HAO_ST_SLOW] counts them like chain_group_kernel's classes) and
 		// are chained by chain_tiny_kernel, 64 to a wave: run here - one lane of a group's eight, in a quarter of the waves of a repeat-rich set (3.7 % of its
 		// tiny groups) - the sequential routine cost as much as everything else in this kernel.  Their codes keep the "nothing to say" prefill until then.
 		const bool sl = !skip && !fast && idx == 0; const unsigned long long sq = __ballot(sl);
 		if (sq) {
 			unsigned long long base = 0;
-			if (lane == 0) base = atomicAdd(A.stats, (unsigned long long)__popcll(sq));
+			if (lane == 0) base = atomicAdd(A.stats + HAO_ST_SLOW, (unsigned long long)__popcll(sq));
 			base = (unsigned long long)hao_readlane_i64((int64_t)base, 0);
 			if (sl) { slow[base + __popcll(sq & ((1ULL << lane) - 1))] = (uint32_t)(li & 0xffffffffu); A.nch[g] = 0; A.nout[g] = 0; }
 		}
@@ -960,7 +960,7 @@ __device__ __forceinline__ void hao_dp_body(const hao_chain_args &A, const hao_g
 		}
 		n_spec_ok_out = n_spec_ok; n_spec_fail_out = n_spec_fail;
 	}
-	if (A.dbg_stats && lane == 0) { atomicAdd(A.stats + HAO_NCLS + 1, (unsigned long long)n_spec_ok_out); atomicAdd(A.stats + HAO_NCLS + 2, (unsigned long long)n_spec_fail_out); atomicAdd(A.stats + HAO_NCLS + 3, (unsigned long long)(ei - si)); }
+	if (A.dbg_stats && lane == 0) { atomicAdd(A.stats + HAO_ST_SPEC_OK, (unsigned long long)n_spec_ok_out); atomicAdd(A.stats + HAO_ST_SPEC_FAIL, (unsigned long long)n_spec_fail_out); atomicAdd(A.stats + HAO_ST_SPEC_RANGE, (unsigned long long)(ei - si)); }
 	if (A.dbg_seq == 3) { if (lane == 0) hao_chain_tail(A, g, a, a_n, P, f, p, t, ii, msc, msc_i, plus); return; }
 	hao_chain_tail_wave(A, g, gs, a, a_n, P, f, p, t, ii, INLDS ? (int64_t)CAP : (int64_t)0, l_cn, l_rec, msc, msc_i, plus);
 }

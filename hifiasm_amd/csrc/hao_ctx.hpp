@@ -125,6 +125,40 @@ struct hao_switches {
 // previous batch's results that the delivery path has in flight there: the "asynchronous" delivery would serialise with the compute it should hide under.
 static __global__ void hao_peek_kernel(const unsigned long long *src, int n, unsigned long long *dst)
 { if ((int)threadIdx.x < n) dst[threadIdx.x] = src[threadIdx.x]; }
+// The read-back slots: which words of the 512 (hao_ctx::peek_h / peek_d) each value lands in.  A slot belongs to one reader - hao_peek writes it, hao_ctx::peeked
+// reads it after the reader's own synchronise - so a value may stay in its slot across calls without another caller writing over it.
+enum hao_peek_id : int {
+	PK_ANCHORS, PK_CLS_BASE,                                                  // hao_batch.hpp: the batch's seed hits; the class layout (HAO_NCLS + 1 words)
+	PK_N_CHAINS, PK_N_CL, PK_N_FC_RAW, PK_N_OL, PK_N_FC,                      //   the batch's totals: chains, chained hits, raw and final fake-cigar entries, overlaps
+	PK_N_EXC, PK_N_CODES, PK_N_FCW, PK_SEED_OVF, PK_ERR, PK_SLOW,             //   verbatim hits, code bytes, raw cigar words, the three seed overflow cursors, c->d_err, the slow statistics (HAO_ST_SLOW .. HAO_ST_CLS_BASE)
+	PK_GRID_PAIRS, PK_REF_SLOTS, PK_REF_UNRES,                                //   the window grid: pairs, covered windows, unresolved windows
+	PK_SORT40,                                                                // hao_tables.hpp: hao_index_sort's runs listed, scratch used, scratch overflow
+	PK_TG_TRACED, PK_TG_CTR, PK_TG_NCIG,                                      // hao_f3.hip, traced grid: selected pairs; (entry bound, untraced pairs); cigar entries
+	PK_RS_SIZES, PK_RS_WAITING, PK_RS_TOTAL, PK_RS_NWINS,                     //   rescue: (states, record slots); lanes still waiting after a round; rescued windows; records
+	PK_WL_N, PK_WL_PLAN, PK_WL_NCIG, PK_WL_CTR,                               //   window lists: records; (swept records, entry bound, -); cigar entries; the stage's six counters
+	PK_COUNT
+};
+struct hao_peek_rng { int at, n; };
+static constexpr hao_peek_rng HAO_PEEK[PK_COUNT] = {
+	/* PK_ANCHORS */ {0, 1}, /* PK_CLS_BASE */ {1, 8},
+	/* PK_N_CHAINS */ {9, 1}, /* PK_N_CL */ {10, 1}, /* PK_N_FC_RAW */ {11, 1}, /* PK_N_OL */ {12, 1}, /* PK_N_FC */ {13, 1},
+	/* PK_N_EXC */ {14, 1}, /* PK_N_CODES */ {15, 1}, /* PK_N_FCW */ {19, 1}, /* PK_SEED_OVF */ {20, 3}, /* PK_ERR */ {23, 1}, /* PK_SLOW */ {64, 11},
+	/* PK_GRID_PAIRS */ {32, 1}, /* PK_REF_SLOTS */ {37, 1}, /* PK_REF_UNRES */ {38, 1},
+	/* PK_SORT40 */ {16, 3},
+	/* PK_TG_TRACED */ {33, 1}, /* PK_TG_CTR */ {34, 2}, /* PK_TG_NCIG */ {36, 1},
+	/* PK_RS_SIZES */ {40, 2}, /* PK_RS_WAITING */ {42, 1}, /* PK_RS_TOTAL */ {43, 1}, /* PK_RS_NWINS */ {44, 1},
+	/* PK_WL_N */ {48, 1}, /* PK_WL_PLAN */ {49, 3}, /* PK_WL_NCIG */ {52, 1}, /* PK_WL_CTR */ {53, 6},
+};
+constexpr int HAO_PEEK_WORDS = 512;
+constexpr bool hao_peek_table_ok()
+{
+	for (int i = 0; i < PK_COUNT; ++i) {
+		if (HAO_PEEK[i].at < 0 || HAO_PEEK[i].n < 1 || HAO_PEEK[i].at + HAO_PEEK[i].n > HAO_PEEK_WORDS) return false;
+		for (int j = 0; j < i; ++j) if (HAO_PEEK[i].at < HAO_PEEK[j].at + HAO_PEEK[j].n && HAO_PEEK[j].at < HAO_PEEK[i].at + HAO_PEEK[i].n) return false;
+	}
+	return true;
+}
+static_assert(hao_peek_table_ok(), "read-back slots: a range beyond the mapped words, or two ranges that overlap");
 
 // What the window-alignment calls have left resident on the current batch.  Every write is a transition, every read a predicate: nothing outside assigns a member.
 //   owner, n   whose pairs lie in the shared scratch al_task / al_res: nobody's (a new batch or a host-fed call), hao_window_ed_grid's n, or hao_window_ed_ref's n
@@ -166,7 +200,8 @@ struct hao_ctx {
 	int device = 0; hao_opt_t opt; std::string err; hipStream_t stream = nullptr; hao_switches sw;
 	// hao_attach: a second batch context over this engine's reads and index (own stream, scratch, results); index_gen counts the owner's rebuilds
 	hao_ctx *owner = nullptr; uint64_t index_gen = 0, attached_gen = 0;
-	unsigned long long *peek_h = nullptr, *peek_d = nullptr;      // 512 words of mapped pinned memory
+	unsigned long long *peek_h = nullptr, *peek_d = nullptr;      // HAO_PEEK_WORDS words of mapped pinned memory, laid out by HAO_PEEK
+	unsigned long long peeked(hao_peek_id slot, int k = 0) const { return peek_h[HAO_PEEK[slot].at + k]; }      // word k of a slot, once the stream that ran hao_peek is synchronised
 	// ---- read store (HBM) ----
 	uint64_t n_reads = 0, n_bases = 0, n_pk_bytes = 0; bool has_n = false; uint32_t max_len = 0;
 	DevBuf<uint8_t> d_packed; DevBuf<uint64_t> d_pk_off; DevBuf<uint32_t> d_len; DevBuf<uint64_t> d_nsite_off; DevBuf<uint32_t> d_nsite;
@@ -252,6 +287,14 @@ struct hao_ctx {
 static void hao_set_err(hao_ctx *c, const std::string &m) { if (c) c->err = m; }
 
 #define HAO_CHECK_LAUNCH() HIP_TRY(hipGetLastError())
+
+// `words` device words at src into a read-back slot, on the engine's stream (one wave; no copy engine: see hao_peek_kernel)
+static int hao_peek(hao_ctx *c, const void *src, int words, hao_peek_id slot)
+{
+	if (words > HAO_PEEK[slot].n) { hao_set_err(c, "hao_peek: more words than the slot holds"); return HAO_EINVAL; }
+	hipLaunchKernelGGL(hao_peek_kernel, dim3(1), dim3(64), 0, c->stream, (const unsigned long long*)src, words, c->peek_d + HAO_PEEK[slot].at); HAO_CHECK_LAUNCH();
+	return HAO_OK;
+}
 
 // sharded mode (the engine holds a slice of the read store)?  A view (hao_attach) has no communicator of its own: its owner's decides.
 static bool hao_comm_is_active(const struct hao_comm *cm);

@@ -119,11 +119,11 @@ int hao_al_trace_grid(hao_ctx *c, const hao_ovlp_t *ol, const hao_ed_pair *pairs
 	const auto idx = rocprim::make_counting_iterator<uint32_t>(0);
 	HIP_TRY(rocprim::select(nullptr, tb, idx, G.want.p, G.sel.p, (uint64_t*)c->d_cursor.p, n, c->stream)); HIP_TRY(hao_tmp(c, tb));
 	HIP_TRY(rocprim::select(c->d_tmp.p, tb, idx, G.want.p, G.sel.p, (uint64_t*)c->d_cursor.p, n, c->stream));
-	hipLaunchKernelGGL(hao_peek_kernel, dim3(1), dim3(64), 0, c->stream, (const unsigned long long*)c->d_cursor.p, 1, c->peek_d + 33); HAO_CHECK_LAUNCH();
-	hipLaunchKernelGGL(hao_peek_kernel, dim3(1), dim3(64), 0, c->stream, G.ctr.p, 2, c->peek_d + 34); HAO_CHECK_LAUNCH();
+	if (int rc = hao_peek(c, c->d_cursor.p, 1, PK_TG_TRACED)) return rc;
+	if (int rc = hao_peek(c, G.ctr.p, 2, PK_TG_CTR)) return rc;
 	HIP_TRY(hipStreamSynchronize(c->stream));
-	const uint64_t T = c->peek_h[33], bound = c->peek_h[34];
-	*n_untraced = c->peek_h[35];
+	const uint64_t T = c->peeked(PK_TG_TRACED), bound = c->peeked(PK_TG_CTR);
+	*n_untraced = c->peeked(PK_TG_CTR, 1);
 	c->timer.mark("trace_sel");
 	HIP_TRY(cig.reserve(bound + 1)); HIP_TRY(G.off.reserve(T + 2)); HIP_TRY(hipMemsetAsync(G.off.p, 0, 8, c->stream));      // (off[0] = 0: no traced pair, every offset is 0)
 	if (T) {
@@ -144,9 +144,9 @@ int hao_al_trace_grid(hao_ctx *c, const hao_ovlp_t *ol, const hao_ed_pair *pairs
 			if (int rc = hao_excl_scan_u64(c, G.cnt.p, G.loc.p, m + 1)) return rc;
 			hipLaunchKernelGGL(hao_tg_compact_kernel, g2, b_, 0, c->stream, G.rows.p, cap, G.loc.p, m, G.off.p + lo, cig.p, (uint64_t)cig.cap); HAO_CHECK_LAUNCH();
 		}
-		hipLaunchKernelGGL(hao_peek_kernel, dim3(1), dim3(64), 0, c->stream, (const unsigned long long*)(G.off.p + T), 1, c->peek_d + 36); HAO_CHECK_LAUNCH();
+		if (int rc = hao_peek(c, G.off.p + T, 1, PK_TG_NCIG)) return rc;
 		HIP_TRY(hipStreamSynchronize(c->stream));
-		*n_cigar = c->peek_h[36];
+		*n_cigar = c->peeked(PK_TG_NCIG);
 		if (*n_cigar > bound) { hao_set_err(c, "traced grid stage: more cigar entries than their bound"); return HAO_EUNSUPP; }      // (hao_tg_bound rules it out)
 	}
 	c->timer.mark("trace_align");
@@ -185,9 +185,9 @@ int hao_al_rescue(hao_ctx *c, const hao_ref_io &io)
 	else if (n_pairs) { hipLaunchKernelGGL(hao_rs_scatter_pe16_kernel, dim3((unsigned)((n_pairs + 255) / 256)), b_, 0, c->stream, ol, io.pairs, io.err8, io.pe16, n_pairs, wl, RA.win_off, G.wpe.p); HAO_CHECK_LAUNCH(); }
 	hao_rs_args A; A.ol = ol; A.n_ol = n_ol; A.wl = wl; A.win_off = RA.win_off; A.shift = RA.shift; A.tab = RA.tab; A.werr = c->rf.werr.p; A.wpe = G.wpe.p; A.len = hao_al_reads_of(c).len;
 	hipLaunchKernelGGL((hao_rs_gap_kernel<false>), go, b_, 0, c->stream, A, G.ctr.p, (uint64_t*)nullptr, (hao_rs_state*)nullptr, (hao_rs_win*)nullptr); HAO_CHECK_LAUNCH();
-	hipLaunchKernelGGL(hao_peek_kernel, dim3(1), dim3(64), 0, c->stream, (const unsigned long long*)G.ctr.p, 2, c->peek_d + 40); HAO_CHECK_LAUNCH();
+	if (int rc = hao_peek(c, G.ctr.p, 2, PK_RS_SIZES)) return rc;
 	HIP_TRY(hipStreamSynchronize(c->stream));
-	const uint64_t na = c->peek_h[40], ns = c->peek_h[41];
+	const uint64_t na = c->peeked(PK_RS_SIZES), ns = c->peeked(PK_RS_SIZES, 1);
 	HIP_TRY(G.st.reserve(na + 1)); HIP_TRY(G.rec.reserve(ns + 1));
 	hipLaunchKernelGGL((hao_rs_gap_kernel<true>), go, b_, 0, c->stream, A, G.ctr.p, G.rbase.p, G.st.p, G.rec.p); HAO_CHECK_LAUNCH();
 	uint64_t rounds = 0;
@@ -202,10 +202,10 @@ int hao_al_rescue(hao_ctx *c, const hao_ref_io &io)
 			for (;;) {
 				HIP_TRY(hipMemsetAsync(G.ctr.p + 4, 0, 8, c->stream));
 				hipLaunchKernelGGL(hao_rs_round_kernel, dim3((unsigned)((m + 255) / 256)), b_, 0, c->stream, R, A, G.st.p + lo, m, G.rec.p, G.path.p, slice, G.ctr.p + 4); HAO_CHECK_LAUNCH();
-				hipLaunchKernelGGL(hao_peek_kernel, dim3(1), dim3(64), 0, c->stream, (const unsigned long long*)(G.ctr.p + 4), 1, c->peek_d + 42); HAO_CHECK_LAUNCH();
+				if (int rc = hao_peek(c, G.ctr.p + 4, 1, PK_RS_WAITING)) return rc;
 				HIP_TRY(hipStreamSynchronize(c->stream));
 				++rounds;
-				if (c->peek_h[42] == 0) break;
+				if (c->peeked(PK_RS_WAITING) == 0) break;
 				if (rounds > 4 * n_slots + 16) { G.path.release(); hao_set_err(c, "rescue stage: more rounds than alignment steps exist"); return HAO_EUNSUPP; }      // (every round completes a step of every waiting lane)
 			}
 		}
@@ -214,14 +214,14 @@ int hao_al_rescue(hao_ctx *c, const hao_ref_io &io)
 	HIP_TRY(c->al_k1.reserve(n_ol + 2));      // (al_k1: the upload path's key buffer, free here)
 	hipLaunchKernelGGL(hao_rs_count_kernel, dim3((unsigned)((n_ol + 256) / 256)), b_, 0, c->stream, n_ol, RA.win_off, G.rbase.p, G.rec.p, c->al_k1.p); HAO_CHECK_LAUNCH();
 	if (int rc = hao_excl_scan_u64(c, c->al_k1.p, io.rs_off->p, n_ol + 1)) return rc;
-	hipLaunchKernelGGL(hao_peek_kernel, dim3(1), dim3(64), 0, c->stream, (const unsigned long long*)(io.rs_off->p + n_ol), 1, c->peek_d + 44); HAO_CHECK_LAUNCH();
+	if (int rc = hao_peek(c, io.rs_off->p + n_ol, 1, PK_RS_NWINS)) return rc;
 	HIP_TRY(hipStreamSynchronize(c->stream));
-	const uint64_t n_wins = c->peek_h[44];
+	const uint64_t n_wins = c->peeked(PK_RS_NWINS);
 	HIP_TRY(io.rs_wins->reserve(n_wins + 1));
 	if (n_wins) { hipLaunchKernelGGL(hao_rs_compact_kernel, go, b_, 0, c->stream, n_ol, RA.win_off, G.rbase.p, G.rec.p, io.rs_off->p, io.rs_wins->p); HAO_CHECK_LAUNCH(); }
-	hipLaunchKernelGGL(hao_peek_kernel, dim3(1), dim3(64), 0, c->stream, (const unsigned long long*)(G.ctr.p + 5), 1, c->peek_d + 43); HAO_CHECK_LAUNCH();
+	if (int rc = hao_peek(c, G.ctr.p + 5, 1, PK_RS_TOTAL)) return rc;
 	HIP_TRY(hipStreamSynchronize(c->stream));
-	c->rs_total = c->peek_h[43]; c->rs_rounds = rounds; c->rs_active = na; c->rs_slots = ns; c->rs_nw = n_wins;
+	c->rs_total = c->peeked(PK_RS_TOTAL); c->rs_rounds = rounds; c->rs_active = na; c->rs_slots = ns; c->rs_nw = n_wins;
 	if (G.path.cap > (1ULL << 27)) G.path.release();      // (more than 1 GB of column scratch is not kept between calls)
 	return HAO_OK;
 }
@@ -251,10 +251,10 @@ int hao_al_wlist(hao_ctx *c, const hao_ref_io &io)
 	hipLaunchKernelGGL(hao_wl_count_kernel, dim3((unsigned)((n_ol + 256) / 256)), b_, 0, c->stream, W, G.cnt.p); HAO_CHECK_LAUNCH();
 	if (int rc = hao_excl_scan_u64(c, G.cnt.p, o_woff.p, n_ol + 1)) return rc;
 	hipLaunchKernelGGL(hao_wl_plan_kernel, go, b_, 0, c->stream, W, o_woff.p, G.plan.p, o_wins.p, G.ncig.p, G.key.p, G.idx.p, wbits, G.ctr.p); HAO_CHECK_LAUNCH();
-	hipLaunchKernelGGL(hao_peek_kernel, dim3(1), dim3(64), 0, c->stream, (const unsigned long long*)(o_woff.p + n_ol), 1, c->peek_d + 48); HAO_CHECK_LAUNCH();
-	hipLaunchKernelGGL(hao_peek_kernel, dim3(1), dim3(64), 0, c->stream, (const unsigned long long*)G.ctr.p, 3, c->peek_d + 49); HAO_CHECK_LAUNCH();
+	if (int rc = hao_peek(c, o_woff.p + n_ol, 1, PK_WL_N)) return rc;
+	if (int rc = hao_peek(c, G.ctr.p, 3, PK_WL_PLAN)) return rc;
 	HIP_TRY(hipStreamSynchronize(c->stream));
-	const uint64_t N = c->peek_h[48], M = c->peek_h[49], bound = c->peek_h[50];
+	const uint64_t N = c->peeked(PK_WL_N), M = c->peeked(PK_WL_PLAN), bound = c->peeked(PK_WL_PLAN, 1);
 	if (N > n_slots || M > N) { hao_set_err(c, "window lists: more records than covered windows"); return HAO_EUNSUPP; }
 	const uint32_t cap = 2 * 31 + 3 + (2 * wl + 62) / 0x3fff;      // (hao_tg_bound for thre <= 31 and a window of wl bases)
 	if (M) {
@@ -276,17 +276,17 @@ int hao_al_wlist(hao_ctx *c, const hao_ref_io &io)
 	if (int rc = hao_excl_scan_u64(c, G.ncig.p, o_cigoff.p, N + 1)) return rc;
 	HIP_TRY(o_cig.reserve(bound + 1));
 	if (N) { hipLaunchKernelGGL(hao_wl_fill_kernel, dim3((unsigned)((N + 255) / 256)), b_, 0, c->stream, W, G.plan.p, o_wins.p, N, o_cigoff.p, G.rowof.p, G.rows.p, cap, o_cig.p, bound); HAO_CHECK_LAUNCH(); }
-	hipLaunchKernelGGL(hao_peek_kernel, dim3(1), dim3(64), 0, c->stream, (const unsigned long long*)(o_cigoff.p + N), 1, c->peek_d + 52); HAO_CHECK_LAUNCH();
-	hipLaunchKernelGGL(hao_peek_kernel, dim3(1), dim3(64), 0, c->stream, (const unsigned long long*)G.ctr.p, 6, c->peek_d + 53); HAO_CHECK_LAUNCH();
+	if (int rc = hao_peek(c, o_cigoff.p + N, 1, PK_WL_NCIG)) return rc;
+	if (int rc = hao_peek(c, G.ctr.p, 6, PK_WL_CTR)) return rc;
 	HIP_TRY(hipStreamSynchronize(c->stream));
 	if (G.path.cap > (1ULL << 27)) G.path.release();      // (more than 1 GB of column scratch is not kept between calls)
 	if (G.rows.cap > (1ULL << 29)) G.rows.release();      // (nor more than 1 GB of rows)
-	if (c->peek_h[52] > bound) { hao_set_err(c, "window lists: more cigar entries than their bound"); return HAO_EUNSUPP; }      // (hao_tg_bound rules it out)
-	if (c->peek_h[57] || c->peek_h[58]) {      // (a broken invariant is an error, not an untraced window)
-		hao_set_err(c, "window lists: " + std::to_string(c->peek_h[58]) + " records whose task could not be rebuilt from the rescue records, " + std::to_string(c->peek_h[57]) + " whose traced sweep lost the distance-only alignment or overran its row");
+	if (c->peeked(PK_WL_NCIG) > bound) { hao_set_err(c, "window lists: more cigar entries than their bound"); return HAO_EUNSUPP; }      // (hao_tg_bound rules it out)
+	if (c->peeked(PK_WL_CTR, 4) || c->peeked(PK_WL_CTR, 5)) {      // (a broken invariant is an error, not an untraced window)
+		hao_set_err(c, "window lists: " + std::to_string(c->peeked(PK_WL_CTR, 5)) + " records whose task could not be rebuilt from the rescue records, " + std::to_string(c->peeked(PK_WL_CTR, 4)) + " whose traced sweep lost the distance-only alignment or overran its row");
 		return HAO_EUNSUPP;
 	}
-	out[0] = N; out[1] = M; out[2] = c->peek_h[56]; out[3] = c->peek_h[52]; out[4] = c->peek_h[55];
+	out[0] = N; out[1] = M; out[2] = c->peeked(PK_WL_CTR, 3); out[3] = c->peeked(PK_WL_NCIG); out[4] = c->peeked(PK_WL_CTR, 2);
 	return HAO_OK;
 }
 

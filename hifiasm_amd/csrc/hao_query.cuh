@@ -419,6 +419,21 @@ __global__ __launch_bounds__(256, CAPLOG == 9 ? 6 : CAPLOG == 10 ? 3 : 1) void s
 // (no dependent index loads in the consumers), the biggest classes first: a slow group of a big class is found early
 // and its sequential DP overlaps the quick checks of the smaller classes.
 #define HAO_NCLS 7
+// The batch's counter block (hao_ctx::Batch::stats): HAO_ST_COUNT words on the device, zeroed once per batch.  The kernels (hao_chain_args::stats, the cursors
+// they are handed) and the host (hao_batch.hpp) reach its words by these names only.
+enum hao_stat : int {
+	HAO_ST_SLOW = 0,                                      // [HAO_NCLS] groups of each size class the quick check leaves to the class's DP kernel (chain_group_kernel, chain_pack8_kernel)
+	HAO_ST_SLOW_HITS = HAO_ST_SLOW + HAO_NCLS,            // their hits
+	HAO_ST_SPEC_OK, HAO_ST_SPEC_FAIL, HAO_ST_SPEC_RANGE,  // HAO_DBG_PRINT=dp: speculative tiles committed / failed, hits in the DP's range (hao_dp_body)
+	HAO_ST_CLS_BASE,                                      // [HAO_NCLS + 1] first work-list entry of each size class, then the number of groups (groups_layout_kernel)
+	HAO_ST_PAD = HAO_ST_CLS_BASE + HAO_NCLS + 1,          // [2] nobody's: they keep the words behind them where the kernels' arguments have always pointed
+	HAO_ST_FCW = HAO_ST_PAD + 2,                          // words of the fake cigars that travel raw (chain_final_kernel)
+	HAO_ST_CODES,                                         // code bytes of the wire format (hao_pack_codes_kernel)
+	HAO_ST_EXC,                                           // verbatim hits of the wire format (hao_pack_args::exc_cnt)
+	HAO_ST_OVF1, HAO_ST_OVF2, HAO_ST_OVF0,                // cursors of the seed overflow lists: reads left by the 512-slot tier, by the 1024-slot tier, by the list-major kernel
+	HAO_ST_L5_CURSOR,                                     // the list-major kernel's read cursor
+	HAO_ST_COUNT
+};
 #define HAO_TINY_MAX 8          // groups up to this many hits: class 0, one LANE per group (chain_tiny_kernel)
 struct hao_gent { uint32_t g, r; uint64_t start; uint32_t n, yid, xl, yl; };      // 32 bytes
 __host__ __device__ __forceinline__ int hao_size_class(uint32_t n) { return n <= HAO_TINY_MAX ? 0 : n <= 64 ? 1 : n <= 128 ? 2 : n <= 256 ? 3 : n <= 512 ? 4 : n <= 2048 ? 5 : 6; }

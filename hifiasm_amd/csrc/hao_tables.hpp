@@ -619,8 +619,8 @@ static int hao_ft_run(hao_ctx *c)
 }
 
 // (hash, read-order index) pairs in stable hash order: x[] -> sx[], iota -> oi2[] (oi[] is scratch).  sort40: 5 radix passes over hash bits 24 .. 63, then the
-// fix-up of the 40-bit runs that hold more than one key (hao_index.cuh); its counters (runs listed, scratch used, scratch overflow) land in c->peek_h[16 .. 18]
-// once the stream has been synchronised - the caller sorts again with sort40 = false if peek_h[16] > hao_sort40_cap(m) or peek_h[18] != 0.
+// fix-up of the 40-bit runs that hold more than one key (hao_index.cuh); its counters (runs listed, scratch used, scratch overflow) land in the read-back slot PK_SORT40
+// once the stream has been synchronised - the caller sorts again with sort40 = false if the runs exceed hao_sort40_cap(m) or the overflow flag is set.
 static inline uint64_t hao_sort40_cap(uint64_t m) { return std::max<uint64_t>(1 << 16, m >> 10); }      // dirty runs listed (expected: m^2 / 2^41 runs of ~2 keys)
 static int hao_index_sort(hao_ctx *c, const uint64_t *x, uint64_t *sx, uint32_t *oi, uint32_t *oi2, uint64_t m, bool sort40)
 {
@@ -635,7 +635,7 @@ static int hao_index_sort(hao_ctx *c, const uint64_t *x, uint64_t *sx, uint32_t 
 		HIP_TRY(hipMemsetAsync(c->w_s40_cnt.p, 0, 32, c->stream));
 		hipLaunchKernelGGL(hao_sort40_mark_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, c->stream, sx, m, c->w_s40_list.p, c->w_s40_cnt.p, cap); HAO_CHECK_LAUNCH();
 		hipLaunchKernelGGL(hao_sort40_fix_kernel, dim3((unsigned)cap), dim3(64), 0, c->stream, sx, oi2, m, c->w_s40_list.p, c->w_s40_cnt.p, cap, c->w_s40_x.p, c->w_s40_o.p, tcap); HAO_CHECK_LAUNCH();
-		hipLaunchKernelGGL(hao_peek_kernel, dim3(1), dim3(64), 0, c->stream, (const unsigned long long*)c->w_s40_cnt.p, 3, c->peek_d + 16); HAO_CHECK_LAUNCH();
+		if (int rc = hao_peek(c, c->w_s40_cnt.p, 3, PK_SORT40)) return rc;
 	}
 	return HAO_OK;
 }
@@ -706,8 +706,8 @@ static int hao_pt_run(hao_ctx *c)
 			c->timer.mark("pt_sort");
 			if (int rc = rle_hist(c->d_ix_sx.p, m)) return rc;      // (synchronises the stream)
 			if (m && sort40) {
-				c->s40_runs = c->peek_h[16];
-				if (c->peek_h[16] > hao_sort40_cap(m) || c->peek_h[18]) { sort40 = false; continue; }      // more two-key runs than the fix-up was sized for: all 64 bits after all
+				c->s40_runs = c->peeked(PK_SORT40);
+				if (c->s40_runs > hao_sort40_cap(m) || c->peeked(PK_SORT40, 2)) { sort40 = false; continue; }      // more two-key runs than the fix-up was sized for: all 64 bits after all
 			}
 			break;
 		}
