@@ -83,7 +83,7 @@ ABI_SYMBOLS = [
     "hao_ft_cnt", "hao_pt_get", "hao_ft_table", "hao_pt_table", "hao_hist", "hao_stats", "hao_sketch_batch",
     "hao_fetch_sketch", "hao_overlap_batch", "hao_fetch_seed_hits", "hao_fetch_overlaps", "hao_batch_totals", "hao_batch_seed_path", "hao_batch_chain_path",
     "hao_stage_times", "hao_pass_default", "hao_overlap_batch_ex", "hao_set_shard", "hao_dist_unique_id", "hao_dist_init",
-    "hao_loop_create", "hao_loop_destroy", "hao_dist_init_loopback", "hao_batch_digest", "hao_selftest_rocprim", "hao_selftest_big", "hao_selftest_sortbits", "hao_unpack_cigar", "hao_unpack_overlaps", "hao_overlap_batch_async", "hao_deliver_wait", "hao_unpack_hits", "hao_exact_check", "hao_fetch_exact", "hao_window_ed_batch", "hao_index_save", "hao_index_load", "hao_next_slot", "hao_attach", "hao_window_trace_batch", "hao_delivery_digest", "hao_ft_passes", "hao_ovlp_bin_read", "hao_ovlp_bin_write", "hao_window_ed_grid", "hao_fetch_ed_grid",
+    "hao_loop_create", "hao_loop_destroy", "hao_dist_init_loopback", "hao_batch_digest", "hao_selftest_rocprim", "hao_selftest_big", "hao_selftest_sortbits", "hao_unpack_cigar", "hao_unpack_overlaps", "hao_overlap_batch_async", "hao_deliver_wait", "hao_unpack_hits", "hao_exact_check", "hao_fetch_exact", "hao_window_ed_batch", "hao_index_save", "hao_index_load", "hao_next_slot", "hao_attach", "hao_window_trace_batch", "hao_window_ed_long", "hao_window_trace_long", "hao_delivery_digest", "hao_ft_passes", "hao_ovlp_bin_read", "hao_ovlp_bin_write", "hao_window_ed_grid", "hao_fetch_ed_grid",
     "hao_deliver_ed_config", "hao_deliver_ed", "hao_unpack_ed",
     "hao_window_trace_grid", "hao_fetch_trace_grid", "hao_deliver_trace", "hao_unpack_trace",
     "hao_window_ed_ref", "hao_fetch_ed_ovlp", "hao_deliver_ed_config_ref", "hao_ref_thresholds",
@@ -219,6 +219,8 @@ def lib():
         L.hao_exact_check.argtypes = [vp]
         L.hao_window_ed_batch.argtypes = [vp, vp, C.c_uint64, vp]
         L.hao_window_trace_batch.argtypes = [vp, C.c_int, vp, C.c_uint64, vp, vp, C.c_uint32]
+        L.hao_window_ed_long.argtypes = [vp, vp, C.c_uint64, vp]
+        L.hao_window_trace_long.argtypes = [vp, C.c_int, vp, C.c_uint64, vp, vp, C.c_uint32]
         L.hao_index_save.argtypes = [vp, C.c_char_p, C.c_int32, vp]
         L.hao_index_load.argtypes = [vp, C.c_char_p, C.POINTER(C.c_int32)]
         L.hao_index_load_dist.argtypes = [vp, C.c_char_p, u64p, C.POINTER(C.c_int32)]
@@ -653,6 +655,21 @@ class Engine:
         out = np.zeros((t.shape[0], 2), dtype=np.int32)
         self._ck(self.L.hao_window_ed_batch(self.h, t.ctypes.data_as(C.c_void_p), t.shape[0], out.ctypes.data_as(C.c_void_p)), "hao_window_ed_batch")
         return out
+
+    def window_ed_long(self, tasks):
+        """window_ed_batch for thresholds up to 2047 and strings up to 16383 bases (bands of up to 64 words: the reference's *_infi_* functions); any mix of widths"""
+        t = np.ascontiguousarray(tasks, dtype=np.uint32).reshape(-1, 10)
+        out = np.zeros((t.shape[0], 2), dtype=np.int32)
+        self._ck(self.L.hao_window_ed_long(self.h, t.ctypes.data_as(C.c_void_p), t.shape[0], out.ctypes.data_as(C.c_void_p)), "hao_window_ed_long")
+        return out
+
+    def window_trace_long(self, tasks, cap=80, mode=0):
+        """window_trace_batch for thresholds up to 2047 and strings up to 16383 bases; same modes, records and cigar encoding"""
+        t = np.ascontiguousarray(tasks, dtype=np.uint32).reshape(-1, 10)
+        out = np.zeros((t.shape[0], 6), dtype=np.int32); cig = np.zeros((t.shape[0], cap), dtype=np.uint16)
+        self._ck(self.L.hao_window_trace_long(self.h, mode, t.ctypes.data_as(C.c_void_p), t.shape[0], out.ctypes.data_as(C.c_void_p), cig.ctypes.data_as(C.c_void_p), cap),
+                 "hao_window_trace_long")
+        return out, cig
 
     def window_ed_grid(self, window=375, thre=15):
         """window / candidate pairs of the last batch on the reference's window grid, generated and aligned on the device; returns their number"""

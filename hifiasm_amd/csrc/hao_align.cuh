@@ -78,6 +78,9 @@ template<int N> HAO_AL_FN uint64_t hao_al_word64(const hao_wide<N> &v, int h) { 
 // (cal_exz_global / cal_exz_infi pick by band width, Correct.cpp:15482-15494, 14508-14564)
 HAO_AL_FN uint32_t hao_al_nword(uint32_t thre) { return (2 * thre + 1 + 63) >> 6; }
 template<typename WT> HAO_AL_FN bool hao_al_mine(uint32_t thre) { return hao_al_nword(thre) == (uint32_t)(sizeof(WT) / 8); }
+// words of a band vector of type WT in the kept columns: the type's own size - a compile-time constant for the register-resident types; the cooperative kernel's
+// finish (hao_align_coop.cuh) works on a band whose word count is known at run time only and specialises this
+template<typename WT> struct hao_al_words { static HAO_AL_MFN int of(int32_t thre) { (void)thre; return (int)(sizeof(WT) / 8); } };
 // w_<sf>_set_bit_lsub (:1029-1033): the low l bits set.  The 128-bit macro shifts a 64-bit word by 64 when l == 64: undefined in C, 0 on x86-64 (shift count
 // modulo 64) - the reference as built starts abs_diag = 64 from VN = 0, and so does this.
 template<typename WT> HAO_AL_FN WT hao_al_lsub(int32_t l) { return (sizeof(WT) == 16 && l == 64) ? (WT)0 : (WT)((((WT)1) << l) - 1); }
@@ -164,28 +167,35 @@ template<typename WT> HAO_AL_FN WT hao_al_eq_of(const hao_al_state<WT> &S, uint3
 template<typename WT> HAO_AL_FN void hao_al_eq_or(hao_al_state<WT> &S, uint32_t c, WT m)
 { S.eq[0] |= c == 0 ? m : (WT)0; S.eq[1] |= c == 1 ? m : (WT)0; S.eq[2] |= c == 2 ? m : (WT)0; S.eq[3] |= c == 3 ? m : (WT)0; }
 
-// set-up of a task (the checks and initial vectors of the reference's functions): false = the answer is already known (no alignment)
-template<typename WT, int MODE> HAO_AL_FN bool hao_al_init(hao_al_state<WT> &S, const hao_ed_reads &R, const hao_ed_task_t &T)
+// set-up of a task, first half: the reference's checks and every scalar of the state - no band vector is touched, so the cooperative kernel (hao_align_coop.cuh), whose
+// lanes hold one word of the band each, shares it.  first: the band bit of the pattern's first character, bd: the characters that enter before the first column.
+// false = the answer is already known (no alignment)
+template<typename WT, int MODE> HAO_AL_FN bool hao_al_init_head(hao_al_state<WT> &S, const hao_ed_task_t &T, int32_t &first, int32_t &bd)
 {
-	const bool back = MODE == HAO_AL_EXT_BWD;
 	S.pn = (int32_t)T.p_len; S.tn = (int32_t)T.t_len; S.thre = (int32_t)T.thre; S.adiag = (MODE == HAO_AL_SEMI || MODE == HAO_AL_ED) ? (int32_t)T.abs_diag : 0;
 	S.cut = S.thre + (S.thre << 1); S.best = HAO_AL_NONE; S.a_p = -1; S.a_t = -1; S.tmp_e = HAO_AL_NONE; S.dead = 0; S.alive = 0;
 	const int32_t thre = S.thre;
+	first = 0; bd = 0;
 	if (MODE == HAO_AL_ED) { if (S.pn > S.tn + S.cut || S.tn > S.pn + S.cut || S.tn <= 0) return false; }
 	else if (MODE == HAO_AL_SEMI) { if (S.pn <= 0 || S.tn <= 0 || S.pn > S.tn + S.cut || S.tn > S.pn + S.cut) return false; }
 	else if (MODE == HAO_AL_GLOBAL) { if (S.pn <= 0 || S.tn <= 0 || S.pn > S.tn + thre || S.tn > S.pn + thre) return false; }
 	else { if (S.pn <= 0 || S.tn <= 0) return false; if (S.pn > S.tn + thre) S.pn = S.tn + thre; else if (S.tn > S.pn + thre) S.tn = S.pn + thre; }
+	if (MODE == HAO_AL_SEMI || MODE == HAO_AL_ED) { first = S.adiag; bd = ((thre << 1) + 1) - S.adiag; S.i_bd = (thre << 1) - S.adiag; S.err = S.adiag; }      // the band starts abs_diag diagonals in: the pattern was clipped at the start of its read
+	else { first = thre; bd = thre + 1; S.i_bd = thre; S.err = thre; }                                                                                          // both strings start together: the band is centred on the main diagonal
+	if (bd > S.pn) bd = S.pn;
+	return true;
+}
+// set-up of a task (the checks and initial vectors of the reference's functions): false = the answer is already known (no alignment)
+template<typename WT, int MODE> HAO_AL_FN bool hao_al_init(hao_al_state<WT> &S, const hao_ed_reads &R, const hao_ed_task_t &T)
+{
+	const bool back = MODE == HAO_AL_EXT_BWD;
+	int32_t first, bd;
+	if (!hao_al_init_head<WT, MODE>(S, T, first, bd)) return false;
+	const int32_t thre = S.thre;
 	hao_al_pstream_init(S.ps, hao_al_walk_of(R, T.p_rid, T.p_pos, T.p_len, T.p_rev, back));
 	S.eq[0] = 0; S.eq[1] = 0; S.eq[2] = 0; S.eq[3] = 0;
-	int32_t first, bd;
-	if (MODE == HAO_AL_SEMI || MODE == HAO_AL_ED) {      // the band starts abs_diag diagonals in: the pattern was clipped at the start of its read
-		first = S.adiag; bd = ((thre << 1) + 1) - S.adiag; S.i_bd = (thre << 1) - S.adiag; S.err = S.adiag;
-		S.VP = 0; S.VN = hao_al_lsub<WT>(S.adiag);
-	} else {                                             // both strings start together: the band is centred on the main diagonal
-		first = thre; bd = thre + 1; S.i_bd = thre; S.err = thre;
-		S.VN = (((WT)1) << thre) - 1; S.VP = ((((WT)1) << ((thre << 1) + 1)) - 1) ^ S.VN;
-	}
-	if (bd > S.pn) bd = S.pn;
+	if (MODE == HAO_AL_SEMI || MODE == HAO_AL_ED) { S.VP = 0; S.VN = hao_al_lsub<WT>(S.adiag); }
+	else { S.VN = (((WT)1) << thre) - 1; S.VP = ((((WT)1) << ((thre << 1) + 1)) - 1) ^ S.VN; }
 	WT mm = ((WT)1) << first;
 	for (int32_t i = 0; i < bd; ++i) { hao_al_eq_or(S, hao_al_pstream_next(S.ps), mm); mm <<= 1; }      // (an N in the pattern sets no mask: the reference's Peq[4] is cleared after its loop)
 	S.top = ((WT)1) << (thre << 1);
@@ -251,7 +261,7 @@ HAO_AL_FN void hao_al_push(uint16_t *cg, uint32_t cap, int32_t &n, int32_t op, i
 template<typename WT, int KW = 5> HAO_AL_FN int32_t hao_al_walk_back(const uint64_t *col, uint64_t stride, int32_t thre, int32_t i, int32_t sft, int32_t poff, int32_t cur,
 		uint16_t *cg, uint32_t cap, int32_t &ncg, int32_t &pdir, int32_t &pdn)
 {
-	constexpr int NW = sizeof(WT) / 8;
+	const int NW = hao_al_words<WT>::of(thre);
 	const int32_t low = thre << 1; int32_t d = 0;
 	while (i > 0 && cur > 0) {
 		const uint64_t *w_ = col + KW * NW * (uint64_t)(KW == 5 ? i - 1 : i) * stride;

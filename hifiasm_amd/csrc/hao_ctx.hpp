@@ -70,12 +70,12 @@ struct StageTimer {
 //   HAO_FT_PASSES                                           ha_ft_gen's hash-range passes (0: what the free device memory asks for)
 //   HAO_ARENA_NUMA                                          placement of the pinned delivery arenas
 //   HAO_DBG_PRINT=seed,qc,dp,sel,dl,bloom,sync              timers / counters on stderr (sync: wait after every stage and say its name - localises a device fault)
-//   HAO_DBG_FORCE=seq_chain,dp_seqtail,dp_nospec,dp_serial,seq_prune,noql      send every read / group down one of the engine's FALLBACK paths (tests: each has to give the default path's bytes)
-//   HAO_DBG_TEST=ix_pad=N,sort40_min=N,sk_gcap=N,exc_cap=N,fc_raw_every=N,exc_every=N,qmz_raw=1,arena_probe=1,ft_chunk_slots=N,gather_chunk=N      capacities and thresholds shrunk so that small inputs reach the overflow / big-index code
+//   HAO_DBG_FORCE=seq_chain,dp_seqtail,dp_nospec,dp_serial,seq_prune,noql,al_coop      send every read / group down one of the engine's FALLBACK paths (tests: each has to give the default path's bytes)
+//   HAO_DBG_TEST=ix_pad=N,sort40_min=N,sk_gcap=N,exc_cap=N,fc_raw_every=N,exc_every=N,qmz_raw=1,arena_probe=1,ft_chunk_slots=N,gather_chunk=N,al_slice=N      capacities and thresholds shrunk so that small inputs reach the overflow / big-index code
 struct hao_switches {
 	bool seedphase = false, qcphase = false, dp_stats = false, selphase = false, dltime = false, bloom = false;                 // HAO_DBG_PRINT
-	bool seq_chain = false, dp_seqtail = false, dp_nospec = false, dp_serial = false, seq_prune = false, seed_noql = false;     // HAO_DBG_FORCE
-	long long sk_gcap = -1, exc_cap = -1, ft_chunk_slots = 0; unsigned long long gather_chunk = 64ULL << 20, ix_pad = 0, sort40_min = 1ULL << 23; int fc_raw_every = 0, exc_every = 0; bool qmz_raw = false, arena_probe = false;      // HAO_DBG_TEST
+	bool seq_chain = false, dp_seqtail = false, dp_nospec = false, dp_serial = false, seq_prune = false, seed_noql = false, al_coop = false;     // HAO_DBG_FORCE
+	long long sk_gcap = -1, exc_cap = -1, ft_chunk_slots = 0; unsigned long long gather_chunk = 64ULL << 20, al_slice = 4ULL << 30, ix_pad = 0, sort40_min = 1ULL << 23; int fc_raw_every = 0, exc_every = 0; bool qmz_raw = false, arena_probe = false;      // HAO_DBG_TEST
 	int arena_numa = 3, seed_merge_maxn = 24000, seed_lds_ratio = 120, ft_passes = 0, seed_lds = 1;
 	static bool in_list(const char *v, const char *name) {      // name is an element of the comma-separated list v
 		const size_t n = strlen(name);
@@ -98,6 +98,7 @@ struct hao_switches {
 			dp_serial = in_list(v, "dp_serial");      // DP and pack kernels on the engine's stream (no side streams)
 			seq_prune = in_list(v, "seq_prune");      // the selection's pruning by one lane
 			seed_noql = in_list(v, "noql");           // the seed kernels' generic per-minimizer tables (the path of batches with a read of more than HAO_QTAB_CAP minimizers)
+			al_coop = in_list(v, "al_coop");          // hao_window_ed_long / hao_window_trace_long: every pair through the cooperative kernel (hao_align_coop.cuh), bands of one to four words included
 		}
 		if (const char *v = getenv("HAO_DBG_TEST")) {
 			unsigned long long x;
@@ -110,6 +111,7 @@ struct hao_switches {
 			if (in_kv(v, "qmz_raw", x)) qmz_raw = x != 0;                   // the delivered minimizer tables in their 8-byte form whatever the read lengths (the form of batches with a read of 65 536 bases or more)
 			if (in_kv(v, "arena_probe", x)) arena_probe = x != 0;           // the delivery arenas' placement probe (hao_arena_ensure) whatever their size and rate
 			if (in_kv(v, "ft_chunk_slots", x)) ft_chunk_slots = (long long)x;      // k-mer slots hashed per chunk of reads in ha_ft_gen's pass mode
+			if (in_kv(v, "al_slice", x)) al_slice = std::max<unsigned long long>(x, 8);      // bytes of column scratch per slice of hao_window_trace_long's second sweep (default 4 GB: a few hundred KB walk several slices on a handful of pairs)
 			if (in_kv(v, "gather_chunk", x)) gather_chunk = std::max<unsigned long long>(x, 64);      // bytes a rank contributes per exchange of hao_dist_gather_reads (default 64 MB: a few KB walk the multi-chunk path on a small read set)
 		}
 		if (const char *e = getenv("HAO_SEED_LDS")) seed_lds = atoi(e) ? 1 : 0;      // 0 = the table kernels (hao_query.cuh, hao_query3.cuh) for every read instead of the list-major kernel (hao_query5.cuh): the tests run them on every scenario - they carry repeat-rich batches and the reads the list-major kernel leaves

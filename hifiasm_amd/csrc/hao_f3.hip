@@ -1,14 +1,16 @@
 // libhao.so, second translation unit: f3, the window-alignment batches (hao_align.cuh) - 36 instantiations of hao_al_kernel (five modes, with and without
-// traceback, bands of one to four words), the four of the delivery path's kernel (hao_ed_deliver.cuh) and the four of the traced grid stage's
+// traceback, bands of one to four words), the nine of the cooperative kernel for wider bands (hao_align_coop.cuh), the four of the delivery path's kernel (hao_ed_deliver.cuh) and the four of the traced grid stage's
 // (hao_trace_grid.cuh) that the rest of the library reaches through hao_al_ed_resident / hao_al_ed_deliver / hao_al_trace_grid only, the rescue stage
 // (hao_rescue.cuh, hao_al_rescue) and the window lists (hao_wlist.cuh, hao_al_wlist); compiled beside
 // hao_capi.hip (hifiasm_amd/build.py).
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <vector>
 #include "hao_ctx.hpp"
 #include "hao_comm.hpp"
 #include "hao_align.cuh"
+#include "hao_align_coop.cuh"
 #include "hao_ed_deliver.cuh"
 #include "hao_trace_grid.cuh"
 #include "hao_rescue.cuh"
@@ -357,6 +359,154 @@ int hao_window_trace_batch(hao_ctx *c, int mode, const hao_ed_task_t *tasks, uin
 	else if (mode == HAO_ALIGN_EXT_BWD) rc = hao_al_trace_run<HAO_AL_EXT_BWD>(c, R, dt.p, order.p, n_tasks, words, tn_max, dr.p, want.p, dc.p, cigar_cap);
 	else if (mode == HAO_ALIGN_SEMI) rc = hao_al_trace_run<HAO_AL_SEMI>(c, R, dt.p, order.p, n_tasks, words, tn_max, dr.p, want.p, dc.p, cigar_cap);
 	else rc = hao_al_trace_run<HAO_AL_GLOBAL>(c, R, dt.p, order.p, n_tasks, words, tn_max, dr.p, want.p, dc.p, cigar_cap);
+	if (rc) return rc;
+	HIP_TRY(hipMemcpyAsync(out, dr.p, n_tasks * sizeof(hao_trace_result_t), hipMemcpyDeviceToHost, c->stream));
+	if (cigar_cap) HIP_TRY(hipMemcpyAsync(cigars, dc.p, n_tasks * (uint64_t)cigar_cap * 2, hipMemcpyDeviceToHost, c->stream));
+	HIP_TRY(hipStreamSynchronize(c->stream));
+	if (c->al_path.cap > (1ULL << 27)) c->al_path.release();      // (more than 1 GB of column scratch is not kept between calls)
+	if (c->al_cig.cap > (1ULL << 29)) c->al_cig.release();        // (nor more than 1 GB of cigar rows)
+	return HAO_OK;
+}
+
+}
+
+// ---- the long calls (hao_align_coop.cuh): bands of up to 64 words ----
+// Classes of a call's pairs: 0 = bands of at most four words, served by hao_al_kernel; 1 .. 4 = the cooperative kernel's segments of 8, 16, 32 and 64 lanes
+// (HAO_DBG_FORCE=al_coop: no class 0).  The order is made on the host - class, then text, stable - so that a wave's segments are full and neighbours share a text.
+struct hao_alc_plan { uint64_t lo[6]; uint32_t words; uint64_t tn_max0; };      // class k = order[lo[k] .. lo[k + 1]); words / tn_max0: class 0's band words and longest text
+static int hao_alc_upload(hao_ctx *c, const hao_ed_task_t *tasks, uint64_t n, hao_alc_plan &P, std::vector<uint32_t> &ord)
+{
+	std::vector<uint64_t> key(n); std::vector<uint8_t> cls(n);
+	P.words = 0; P.tn_max0 = 1;
+	for (uint64_t i = 0; i < n; ++i) {
+		const uint32_t nw = hao_al_nword(tasks[i].thre);
+		if (nw <= 4 && !c->sw.al_coop) { cls[i] = 0; key[i] = hao_al_sort_key(tasks[i]); P.words |= 1u << (nw - 1); P.tn_max0 = std::max<uint64_t>(P.tn_max0, tasks[i].t_len); }
+		else { cls[i] = (uint8_t)(hao_alc_lg(nw) - 2); key[i] = hao_al_sort_key(tasks[i]) & ((1ULL << 62) - 1); }
+	}
+	ord.resize(n); for (uint64_t i = 0; i < n; ++i) ord[i] = (uint32_t)i;
+	std::stable_sort(ord.begin(), ord.end(), [&](uint32_t a, uint32_t b) { return cls[a] != cls[b] ? cls[a] < cls[b] : key[a] < key[b]; });
+	for (int k = 0; k <= 5; ++k) P.lo[k] = (uint64_t)(std::lower_bound(ord.begin(), ord.end(), k, [&](uint32_t a, int v) { return (int)cls[a] < v; }) - ord.begin());
+	HIP_TRY(c->al_task.reserve(n)); HIP_TRY(c->al_order.reserve(n));
+	HIP_TRY(hipMemcpyAsync(c->al_task.p, tasks, n * sizeof(hao_ed_task_t), hipMemcpyHostToDevice, c->stream));
+	HIP_TRY(hipMemcpyAsync(c->al_order.p, ord.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+	return HAO_OK;
+}
+// one launch of the cooperative kernel: m pairs of class k (order / poff: their entries)
+template<int MODE, bool TRACE> static int hao_alc_launch(hao_ctx *c, const hao_ed_reads &R, int k, const uint32_t *order, uint64_t m, uint64_t *path, const uint64_t *poff,
+		hao_ed_result_t *out_ed, hao_trace_result_t *out_tr, uint8_t *want, uint16_t *dc, uint32_t cap)
+{
+	const int lg = k + 2; const uint64_t per_block = 4 * (uint64_t)(64 >> lg);
+	hipLaunchKernelGGL((hao_alc_kernel<MODE, TRACE>), dim3((unsigned)((m + per_block - 1) / per_block)), dim3(256), 0, c->stream, R, (const hao_ed_task_t*)c->al_task.p, order, m, lg, path, poff, out_ed, out_tr, want, dc, cap);
+	HAO_CHECK_LAUNCH();
+	return HAO_OK;
+}
+// the traced modes over the plan's classes: class 0 through hao_al_trace_run, the others in two sweeps of the cooperative kernel - the first keeps nothing and marks
+// the pairs that end within their threshold, the second keeps three words per band word and column for those, in slices whose columns fit c->sw.al_slice bytes
+template<int MODE> static int hao_alc_trace_run(hao_ctx *c, const hao_ed_reads &R, const hao_ed_task_t *tasks, const hao_alc_plan &P, const std::vector<uint32_t> &ord, uint64_t n,
+		hao_trace_result_t *dr, uint8_t *want, uint16_t *dc, uint32_t cap)
+{
+	const uint32_t *order = c->al_order.p;
+	if (P.lo[1]) { if (int rc = hao_al_trace_run<MODE>(c, R, c->al_task.p, order, P.lo[1], P.words, P.tn_max0, dr, want, dc, cap)) return rc; }
+	if (P.lo[5] == P.lo[1]) return HAO_OK;
+	for (int k = 1; k <= 4; ++k) if (P.lo[k + 1] > P.lo[k]) {
+		if (int rc = hao_alc_launch<MODE, false>(c, R, k, order + P.lo[k], P.lo[k + 1] - P.lo[k], nullptr, nullptr, nullptr, dr, want, nullptr, 0u)) return rc; }
+	std::vector<uint8_t> hw(n);
+	HIP_TRY(hipMemcpyAsync(hw.data(), want, n, hipMemcpyDeviceToHost, c->stream));
+	HIP_TRY(hipStreamSynchronize(c->stream));
+	// the selected pairs, still by class and text; a slice = consecutive pairs of one class whose columns fit the budget (at least one pair), offsets from the slice's start
+	struct Slice { int k; uint64_t lo, m; };
+	std::vector<uint32_t> sel; std::vector<uint64_t> off; std::vector<Slice> slices;
+	const uint64_t budget = c->sw.al_slice / 8; uint64_t most = 0;
+	for (int k = 1; k <= 4; ++k) {
+		uint64_t used = 0; Slice sl{k, sel.size(), 0};
+		for (uint64_t q = P.lo[k]; q < P.lo[k + 1]; ++q) if (hw[ord[q]]) {
+			const uint64_t w = hao_alc_path_words(tasks[ord[q]].thre, tasks[ord[q]].t_len);
+			if (sl.m && used + w > budget) { slices.push_back(sl); sl = Slice{k, sel.size(), 0}; used = 0; }
+			sel.push_back(ord[q]); off.push_back(used); used += w; ++sl.m; most = std::max(most, used);
+		}
+		if (sl.m) slices.push_back(sl);
+	}
+	if (sel.empty()) return HAO_OK;
+	HIP_TRY(c->al_sel.reserve(sel.size())); HIP_TRY(c->al_k1.reserve(off.size())); HIP_TRY(c->al_path.reserve(most + 1));
+	HIP_TRY(hipMemcpyAsync(c->al_sel.p, sel.data(), sel.size() * 4, hipMemcpyHostToDevice, c->stream));
+	HIP_TRY(hipMemcpyAsync(c->al_k1.p, off.data(), off.size() * 8, hipMemcpyHostToDevice, c->stream));
+	for (const Slice &sl : slices) { if (int rc = hao_alc_launch<MODE, true>(c, R, sl.k, c->al_sel.p + sl.lo, sl.m, c->al_path.p, c->al_k1.p + sl.lo, nullptr, dr, nullptr, dc, cap)) return rc; }
+	HIP_TRY(hipStreamSynchronize(c->stream));      // (sel / off leave scope)
+	return HAO_OK;
+}
+// the range checks both long calls share (the reference indexes its strings unchecked; a device kernel must not)
+static bool hao_alc_in_range(const hao_read_view &V, const hao_ed_task_t &t)
+{
+	return t.p_rid < V.n && t.t_rid < V.n && (uint64_t)t.p_pos + t.p_len <= V.h_len[t.p_rid] && (uint64_t)t.t_pos + t.t_len <= V.h_len[t.t_rid] &&
+		t.thre <= HAO_ED_LONG_MAX_THRE && t.p_len <= HAO_ED_LONG_MAX_LEN && t.t_len <= HAO_ED_LONG_MAX_LEN;
+}
+
+extern "C" {
+
+int hao_window_ed_long(hao_ctx *c, const hao_ed_task_t *tasks, uint64_t n_tasks, hao_ed_result_t *out)
+{
+	if (!c || (!tasks && n_tasks) || (!out && n_tasks)) return HAO_EINVAL;
+	if (int rc = hao_view_refresh(c)) return rc;
+	HAO_STAGE_VIEW(c, V, "hao_window_ed_long needs the bases of both reads");
+	c->win.on_host_fed();
+	if (n_tasks == 0) return HAO_OK;
+	if (n_tasks >= (1ULL << 32)) { hao_set_err(c, "hao_window_ed_long: more than 2^32 tasks in one call"); return HAO_EUNSUPP; }
+	for (uint64_t i = 0; i < n_tasks; ++i) {
+		const hao_ed_task_t &t = tasks[i];
+		if (!hao_alc_in_range(V, t) || t.abs_diag > 2 * t.thre) { hao_set_err(c, "hao_window_ed_long: task " + std::to_string(i) + " out of range"); return HAO_EINVAL; }
+		const uint32_t nw = hao_al_nword(t.thre);
+		if (nw > 1 && (int64_t)t.p_len - (int64_t)t.t_len + (int64_t)t.abs_diag > 64 * (int64_t)nw) {      // (hao_window_ed_batch's rule: the final scan stays inside the band's words)
+			hao_set_err(c, "hao_window_ed_long: task " + std::to_string(i) + ": p_len - t_len + abs_diag beyond the band's words"); return HAO_EINVAL; }
+	}
+	HIP_TRY(hipSetDevice(c->device));
+	hao_alc_plan P; std::vector<uint32_t> ord;
+	if (int rc = hao_alc_upload(c, tasks, n_tasks, P, ord)) return rc;
+	HIP_TRY(c->al_res.reserve(n_tasks));
+	hao_ed_task_t *dt = c->al_task.p; uint32_t *order = c->al_order.p; hao_ed_result_t *dr = c->al_res.p;
+	const hao_ed_reads R = hao_al_reads_of(c);
+	if (P.lo[1]) {
+		const dim3 g_((unsigned)((P.lo[1] + 255) / 256)), b_(256); const uint64_t n0 = P.lo[1];
+		if (P.words & 1u) { hipLaunchKernelGGL((hao_al_kernel<uint64_t, HAO_AL_ED, false>), g_, b_, 0, c->stream, R, dt, order, n0, (uint64_t*)nullptr, (uint64_t)0, dr, (hao_trace_result_t*)nullptr, (uint8_t*)nullptr, (uint16_t*)nullptr, 0u); HAO_CHECK_LAUNCH(); }
+		if (P.words & 2u) { hipLaunchKernelGGL((hao_al_kernel<hao_u128, HAO_AL_ED, false>), g_, b_, 0, c->stream, R, dt, order, n0, (uint64_t*)nullptr, (uint64_t)0, dr, (hao_trace_result_t*)nullptr, (uint8_t*)nullptr, (uint16_t*)nullptr, 0u); HAO_CHECK_LAUNCH(); }
+		if (P.words & 4u) { hipLaunchKernelGGL((hao_al_kernel<hao_wide<3>, HAO_AL_ED, false>), g_, b_, 0, c->stream, R, dt, order, n0, (uint64_t*)nullptr, (uint64_t)0, dr, (hao_trace_result_t*)nullptr, (uint8_t*)nullptr, (uint16_t*)nullptr, 0u); HAO_CHECK_LAUNCH(); }
+		if (P.words & 8u) { hipLaunchKernelGGL((hao_al_kernel<hao_wide<4>, HAO_AL_ED, false>), g_, b_, 0, c->stream, R, dt, order, n0, (uint64_t*)nullptr, (uint64_t)0, dr, (hao_trace_result_t*)nullptr, (uint8_t*)nullptr, (uint16_t*)nullptr, 0u); HAO_CHECK_LAUNCH(); }
+	}
+	for (int k = 1; k <= 4; ++k) if (P.lo[k + 1] > P.lo[k]) {
+		if (int rc = hao_alc_launch<HAO_AL_ED, false>(c, R, k, order + P.lo[k], P.lo[k + 1] - P.lo[k], nullptr, nullptr, dr, nullptr, nullptr, nullptr, 0u)) return rc; }
+	HIP_TRY(hipMemcpyAsync(out, dr, n_tasks * sizeof(hao_ed_result_t), hipMemcpyDeviceToHost, c->stream));
+	HIP_TRY(hipStreamSynchronize(c->stream));
+	return HAO_OK;
+}
+
+int hao_window_trace_long(hao_ctx *c, int mode, const hao_ed_task_t *tasks, uint64_t n_tasks, hao_trace_result_t *out, uint16_t *cigars, uint32_t cigar_cap)
+{
+	if (!c || (mode < HAO_ALIGN_GLOBAL || mode > HAO_ALIGN_SEMI) || (!tasks && n_tasks) || (!out && n_tasks) || (!cigars && n_tasks && cigar_cap)) return HAO_EINVAL;
+	if (int rc = hao_view_refresh(c)) return rc;
+	HAO_STAGE_VIEW(c, V, "hao_window_trace_long needs the bases of both reads");
+	c->win.on_host_fed();
+	if (n_tasks == 0) return HAO_OK;
+	if (n_tasks >= (1ULL << 32)) { hao_set_err(c, "hao_window_trace_long: more than 2^32 tasks in one call"); return HAO_EUNSUPP; }
+	for (uint64_t i = 0; i < n_tasks; ++i) {
+		const hao_ed_task_t &t = tasks[i];
+		if (!hao_alc_in_range(V, t)) { hao_set_err(c, "hao_window_trace_long: task " + std::to_string(i) + " out of range"); return HAO_EINVAL; }
+		if (mode == HAO_ALIGN_SEMI) {
+			const int64_t ai = (int64_t)t.p_len - (int64_t)t.t_len + (int64_t)t.abs_diag;
+			if (ai < 0 || ai > 2 * (int64_t)t.thre || t.t_len <= t.abs_diag || t.abs_diag > 2 * t.thre) { hao_set_err(c, "hao_window_trace_long: task " + std::to_string(i) + ": the band does not cover the pattern"); return HAO_EINVAL; }
+		}
+	}
+	HIP_TRY(hipSetDevice(c->device));
+	hao_alc_plan P; std::vector<uint32_t> ord;
+	if (int rc = hao_alc_upload(c, tasks, n_tasks, P, ord)) return rc;
+	DevBuf<hao_trace_result_t> &dr = c->al_tres; DevBuf<uint16_t> &dc = c->al_cig; DevBuf<uint8_t> &want = c->al_want;
+	HIP_TRY(dr.reserve(n_tasks)); HIP_TRY(want.reserve(n_tasks)); HIP_TRY(dc.reserve(n_tasks * (uint64_t)cigar_cap + 1));
+	HIP_TRY(hipMemsetAsync(want.p, 0, n_tasks, c->stream));
+	if (cigar_cap) HIP_TRY(hipMemsetAsync(dc.p, 0, n_tasks * (uint64_t)cigar_cap * 2, c->stream));      // (tasks without an alignment: rows of zeros)
+	const hao_ed_reads R = hao_al_reads_of(c);
+	int rc;
+	if (mode == HAO_ALIGN_EXT_FWD) rc = hao_alc_trace_run<HAO_AL_EXT_FWD>(c, R, tasks, P, ord, n_tasks, dr.p, want.p, dc.p, cigar_cap);
+	else if (mode == HAO_ALIGN_EXT_BWD) rc = hao_alc_trace_run<HAO_AL_EXT_BWD>(c, R, tasks, P, ord, n_tasks, dr.p, want.p, dc.p, cigar_cap);
+	else if (mode == HAO_ALIGN_SEMI) rc = hao_alc_trace_run<HAO_AL_SEMI>(c, R, tasks, P, ord, n_tasks, dr.p, want.p, dc.p, cigar_cap);
+	else rc = hao_alc_trace_run<HAO_AL_GLOBAL>(c, R, tasks, P, ord, n_tasks, dr.p, want.p, dc.p, cigar_cap);
 	if (rc) return rc;
 	HIP_TRY(hipMemcpyAsync(out, dr.p, n_tasks * sizeof(hao_trace_result_t), hipMemcpyDeviceToHost, c->stream));
 	if (cigar_cap) HIP_TRY(hipMemcpyAsync(cigars, dc.p, n_tasks * (uint64_t)cigar_cap * 2, hipMemcpyDeviceToHost, c->stream));

@@ -265,7 +265,8 @@ int hao_fetch_exact(hao_ctx *c, uint64_t rid, const uint8_t **flags, uint64_t *n
  * Band width: 2 thre + 1 diagonals in one 64-bit word (thre <= 31), in two (thre 32 .. 63: the reference's ed_band_cal_*_128_* functions, generated
  * from the same text by HA_ED_INIT(128), :1287-2129, and chosen by band width, cal_exz_global Correct.cpp:15482-15494), or in nword = 3 / 4 words
  * (thre 64 .. 95 / 96 .. 127: the reference's ed_band_cal_*_infi_* functions, :2134-3100, which cal_exz_infi calls with nword = ceil((2 thre + 1) / 64),
- * Correct.cpp:14508-14565); thre > HAO_ED_MAX_THRE: HAO_EINVAL.  With a band of two or more words p_len - t_len + abs_diag <= 64 nword is required
+ * Correct.cpp:14508-14565); thre > HAO_ED_MAX_THRE: HAO_EINVAL here - wider bands, up to nword = 64 (thre <= HAO_ED_LONG_MAX_THRE), are hao_window_ed_long's and
+ * hao_window_trace_long's, where a segment of 8 .. 64 lanes owns a pair and each lane holds one word of the band.  With a band of two or more words p_len - t_len + abs_diag <= 64 nword is required
  * (beyond it the reference's final scan indexes past its band words).  out[i].err = edit distance or INT32_MAX (no alignment within thre, the reference's clear_align state), out[i].pe = end of the
  * alignment on the pattern or -1; ps = -1, ts = 0, te = t_len - 1 are constants of the call.  One lane per pair; single-device mode (the bases of
  * both reads must be local).  This is the data-parallel core of the window alignment; window placement and retries stay with the caller. */
@@ -473,6 +474,19 @@ typedef struct { int32_t err, ps, pe, ts, te, n_cigar; } hao_trace_result_t;
                                  * The band must cover the pattern: 0 <= p_len - t_len + abs_diag <= 2 thre and t_len > abs_diag (else HAO_EINVAL: the reference's
                                  * traceback would index its column words out of range).  (Numbering: the modes of Correct.cpp:14536-14545.) */
 int hao_window_trace_batch(hao_ctx *c, int mode, const hao_ed_task_t *tasks, uint64_t n_tasks, hao_trace_result_t *out, uint16_t *cigars, uint32_t cigar_cap);
+
+/* Window alignment beyond 127 errors: the alignments of the stretches between anchored windows - cal_exz_infi (Correct.cpp:14508-14565) as hc_aln_exz (:14576-14636)
+ * and hc_aln_exz_adv (:16082) call it, with patterns of up to MAX_SIN_L = 10000 bases and thresholds scaled up to MAX_SIN_E = 2047 (Levenshtein_distance.h:751-758),
+ * i.e. the ed_band_cal_*_infi_* functions (:2134-3100) with nword = ceil((2 thre + 1) / 64) up to 64.  hao_window_ed_long is hao_window_ed_batch and
+ * hao_window_trace_long is hao_window_trace_batch - same task and result records, modes and cigar encoding, same domain rules (p_len - t_len + abs_diag <= 64 nword
+ * for the distance-only call, the band covering the pattern for HAO_ALIGN_SEMI), bit for bit the same results - for thre <= HAO_ED_LONG_MAX_THRE and
+ * p_len, t_len <= HAO_ED_LONG_MAX_LEN (else HAO_EINVAL).  A call may mix all widths: pairs whose band fits four words run on hao_window_ed_batch's kernels, the others
+ * on the cooperative kernel (hao_align_coop.cuh).  The traced call runs two sweeps; the second keeps 24 nword bytes per text column of the pairs that aligned (about
+ * 21 MB for 64 words and 14 000 columns), in slices of at most ~4 GB.  Attached contexts and sharded engines (after hao_dist_gather_reads) as for the batch calls. */
+#define HAO_ED_LONG_MAX_THRE 2047     /* the reference's MAX_SIN_E: 4095 diagonals in 64 words */
+#define HAO_ED_LONG_MAX_LEN 16383     /* covers MAX_SIN_L + 2 MAX_SIN_E */
+int hao_window_ed_long(hao_ctx *c, const hao_ed_task_t *tasks, uint64_t n_tasks, hao_ed_result_t *out);
+int hao_window_trace_long(hao_ctx *c, int mode, const hao_ed_task_t *tasks, uint64_t n_tasks, hao_trace_result_t *out, uint16_t *cigars, uint32_t cigar_cap);
 
 /* f3 with traceback on the device grid: the semi-global traced alignment (HAO_ALIGN_SEMI: ed_band_cal_semi_64_w_absent_diag_trace + gen_trace, the call
  * Correct.cpp:3897-3911 makes right after the distance-only one) of the grid pairs hao_window_ed_grid(window, thre) forms, in the same text order.  A pair is
