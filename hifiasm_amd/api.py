@@ -90,11 +90,17 @@ ABI_SYMBOLS = [
     "hao_window_rescue_ref", "hao_fetch_rescue", "hao_rescue_task", "hao_deliver_rescue", "hao_unpack_rescue",
     "hao_window_wlist_ref", "hao_fetch_wlist", "hao_deliver_wlist", "hao_unpack_wlist",
     "hao_dist_gather_reads", "hao_reads_digest", "hao_index_load_dist", "hao_shard_layout",
+    "hao_window_ladder", "hao_fetch_ladder", "hao_ladder_thresholds",
 ]
 
 
 RESCUE_OVLP = np.dtype([("verdict", np.uint16), ("flags", np.uint16), ("exit_win", np.uint32), ("align_length", np.uint32), ("n_rescued", np.uint32)])
 RESCUE_FWD, RESCUE_BWD, RESCUE_ANCHOR, RESCUE_UNTRACED, RESCUE_NO_EXIT = 0, 1, 2, 1, 0xFFFFFFFF
+# hao_ladder_req_t / hao_ladder_res_t (hao_window_ladder) and the result's flags
+LADDER_REQ = np.dtype([("ol", np.uint32), ("mode", np.uint32), ("qs", np.int32), ("qe", np.int32), ("ts", np.int32), ("te", np.int32), ("estimate_err", np.int32), ("reserved", np.uint32)])
+LADDER_RES = np.dtype([("rung", np.uint32), ("thre", np.int32), ("qs", np.int32), ("qe", np.int32), ("ts", np.int32), ("te", np.int32), ("aux_beg", np.int32), ("flags", np.uint32),
+                       ("err", np.int32), ("a_ps", np.int32), ("a_pe", np.int32), ("a_ts", np.int32), ("a_te", np.int32), ("n_cigar", np.int32)])
+LADDER_REFUSED, LADDER_UNTRACED = 1, 2
 WLIST_PRIMARY, WLIST_UNTRACED = 3, 1 << 19      # hao_wlist_win_t::info: source of a first-placement window the rescue did not trace; the untraced flag
 
 
@@ -221,6 +227,9 @@ def lib():
         L.hao_window_trace_batch.argtypes = [vp, C.c_int, vp, C.c_uint64, vp, vp, C.c_uint32]
         L.hao_window_ed_long.argtypes = [vp, vp, C.c_uint64, vp]
         L.hao_window_trace_long.argtypes = [vp, C.c_int, vp, C.c_uint64, vp, vp, C.c_uint32]
+        L.hao_window_ladder.argtypes = [vp, vp, C.c_uint64, C.c_double, C.c_int64, C.c_int64, vp, vp, vp, C.c_uint64, u64p]
+        L.hao_fetch_ladder.argtypes = [vp, vp, C.c_uint64, u64p, u64p]
+        L.hao_ladder_thresholds.argtypes = [C.c_int64, C.c_int64, C.c_double, C.c_int64, C.c_int64, C.POINTER(C.c_int32)]
         L.hao_index_save.argtypes = [vp, C.c_char_p, C.c_int32, vp]
         L.hao_index_load.argtypes = [vp, C.c_char_p, C.POINTER(C.c_int32)]
         L.hao_index_load_dist.argtypes = [vp, C.c_char_p, u64p, C.POINTER(C.c_int32)]
@@ -671,6 +680,33 @@ class Engine:
                  "hao_window_trace_long")
         return out, cig
 
+    def window_ladder(self, req, e_rate, maxl, maxe, cap=None):
+        """hao_window_ladder over the current batch: req = LADDER_REQ records (or int rows ol, mode, qs, qe, ts, te, estimate_err) -> (LADDER_RES records, cig_off
+        int64 [n + 1], cigars uint16).  cap = None: the stage runs once and the entries, which stay resident, are fetched at their size (hao_fetch_ladder); a
+        number: the entries come back only when they fit it (cigars is None otherwise; cig_off[-1] is the capacity needed)"""
+        q = np.asarray(req)
+        if q.dtype != LADDER_REQ:
+            rows = np.asarray(req, dtype=np.int64).reshape(-1, 7)
+            q = np.zeros(rows.shape[0], dtype=LADDER_REQ)
+            for k, f in enumerate(("ol", "mode", "qs", "qe", "ts", "te", "estimate_err")):
+                q[f] = rows[:, k]
+        q = np.ascontiguousarray(q); n = q.shape[0]
+        res = np.zeros(n, dtype=LADDER_RES); off = np.zeros(n + 1, dtype=np.uint64); need = C.c_uint64()
+        cig = np.zeros(max(1, cap or 0), dtype=np.uint16)
+        self._ck(self.L.hao_window_ladder(self.h, q.ctypes.data_as(C.c_void_p), n, C.c_double(e_rate), C.c_int64(maxl), C.c_int64(maxe), res.ctypes.data_as(C.c_void_p),
+                                          off.ctypes.data_as(C.c_void_p), cig.ctypes.data_as(C.c_void_p), cap or 0, C.byref(need)), "hao_window_ladder")
+        if cap is None:
+            cig = np.zeros(max(1, need.value), dtype=np.uint16)
+            self._ck(self.L.hao_fetch_ladder(self.h, cig.ctypes.data_as(C.c_void_p), cig.shape[0], None, None), "hao_fetch_ladder")
+            return res, off.astype(np.int64), cig[:need.value]
+        return res, off.astype(np.int64), (cig[:need.value] if need.value <= cap else None)
+
+    def ladder_rounds(self):
+        """the requests that were open in each of the last hao_window_ladder call's four rounds"""
+        r = (C.c_uint64 * 4)()
+        self._ck(self.L.hao_fetch_ladder(self.h, None, 0, None, r), "hao_fetch_ladder")
+        return [int(x) for x in r]
+
     def window_ed_grid(self, window=375, thre=15):
         """window / candidate pairs of the last batch on the reference's window grid, generated and aligned on the device; returns their number"""
         n = C.c_uint64()
@@ -818,6 +854,13 @@ class Engine:
         ms = (C.c_float * 64)()
         n = self.L.hao_stage_times(self.h, names, ms, 64)
         return [(names[i].decode(), float(ms[i])) for i in range(n)]
+
+
+def ladder_thresholds(ql, estimate_err, e_rate, maxl, maxe):
+    """hao_ladder_thresholds: the four rungs' thresholds of a request as the device computes them (-1: skipped) and the number of attempts"""
+    t = (C.c_int32 * 4)()
+    n = lib().hao_ladder_thresholds(ql, estimate_err, C.c_double(e_rate), maxl, maxe, t)
+    return [int(x) for x in t], n
 
 
 def ref_thresholds(window, e_rate):

@@ -555,6 +555,45 @@ int hao_fetch_wlist(hao_ctx *c, uint64_t rid, uint64_t *n_ol, const uint64_t **w
 	return HAO_OK;
 }
 
+// the threshold ladder (hao_ladder.cuh, hao_f3.hip): requests up, the stage over the batch's final ol->list and fake cigars, results / offsets / entries down
+static int hao_ladder_run(hao_ctx *c, const hao_ladder_req_t *req, uint64_t n, double e_rate, int64_t maxl, int64_t maxe, hao_ladder_res_t *out, uint64_t *cig_off, uint16_t *cigars, uint64_t cigar_cap, uint64_t *n_cigar)
+{
+	hao_ctx::Batch &B = *c->batch; hao_ctx::Batch::OutSet &O = B.O(); hao_ctx::Ladder &G = c->ld;
+	*n_cigar = 0; c->ld_valid = false; c->ld_ncig = 0; for (int j = 0; j < 4; ++j) c->ld_rounds[j] = 0;
+	{ HAO_STAGE_VIEW(c, V, "hao_window_ladder needs the bases of both reads"); (void)V; }
+	if (!(e_rate >= 0 && e_rate <= 1) || maxl < 0 || maxe < 0 || maxe > HAO_ED_LONG_MAX_THRE) { hao_set_err(c, "hao_window_ladder: e_rate outside [0, 1], maxl negative, or maxe negative or beyond HAO_ED_LONG_MAX_THRE"); return HAO_EINVAL; }
+	if (n >= (1ULL << 32)) { hao_set_err(c, "hao_window_ladder: more than 2^32 requests in one call"); return HAO_EUNSUPP; }
+	c->win.on_host_fed();      // (the task / result scratch is shared with the other window-alignment calls)
+	if (n == 0) { cig_off[0] = 0; c->ld_valid = true; return HAO_OK; }
+	HIP_TRY(G.req.reserve(n));
+	HIP_TRY(hipMemcpyAsync(G.req.p, req, n * sizeof(hao_ladder_req_t), hipMemcpyHostToDevice, c->stream));
+	if (int rc = hao_al_ladder(c, O.ol_out.p, B.n_ol, O.fc_out.p, O.fc_out_off.p, n, e_rate, maxl, maxe, n_cigar, c->ld_rounds)) return rc;
+	HIP_TRY(hipMemcpyAsync(out, G.res.p, n * sizeof(hao_ladder_res_t), hipMemcpyDeviceToHost, c->stream));
+	HIP_TRY(hipMemcpyAsync(cig_off, G.off.p, (n + 1) * 8, hipMemcpyDeviceToHost, c->stream));
+	if (*n_cigar && *n_cigar <= cigar_cap) HIP_TRY(hipMemcpyAsync(cigars, G.cig.p, *n_cigar * 2, hipMemcpyDeviceToHost, c->stream));
+	HIP_TRY(hipStreamSynchronize(c->stream));
+	if (c->al_path.cap > (1ULL << 27)) c->al_path.release();      // (more than 1 GB of column scratch is not kept between calls)
+	for (int j = 0; j < 4; ++j) if (G.rows[j].cap > (1ULL << 29)) G.rows[j].release();      // (nor more than 1 GB of cigar rows)
+	c->ld_ncig = *n_cigar; c->ld_valid = true;
+	return HAO_OK;
+}
+
+int hao_fetch_ladder(hao_ctx *c, uint16_t *cigars, uint64_t cigar_cap, uint64_t *n_cigar, uint64_t rounds[4])
+{
+	if (!c) return HAO_EINVAL;
+	if (!c->ld_valid) { hao_set_err(c, "hao_fetch_ladder: no results of hao_window_ladder are resident"); return HAO_EINVAL; }
+	if (n_cigar) *n_cigar = c->ld_ncig;
+	if (rounds) for (int j = 0; j < 4; ++j) rounds[j] = c->ld_rounds[j];
+	if (cigars && c->ld_ncig && c->ld_ncig <= cigar_cap) { HIP_TRY(hipSetDevice(c->device)); HIP_TRY(hipMemcpy(cigars, c->ld.cig.p, c->ld_ncig * 2, hipMemcpyDeviceToHost)); }
+	return HAO_OK;
+}
+
+int hao_window_ladder(hao_ctx *c, const hao_ladder_req_t *req, uint64_t n_req, double e_rate, int64_t maxl, int64_t maxe, hao_ladder_res_t *out, uint64_t *cig_off, uint16_t *cigars, uint64_t cigar_cap, uint64_t *n_cigar)
+{
+	if (!c || !cig_off || !n_cigar || (n_req && (!req || !out)) || (cigar_cap && !cigars)) return HAO_EINVAL;
+	return hao_window_stage(c, "ladder", [&] { return hao_ladder_run(c, req, n_req, e_rate, maxl, maxe, out, cig_off, cigars, cigar_cap, n_cigar); });
+}
+
 int hao_deliver_wlist(hao_ctx *c, int slot, hao_wlist_delivery_t *out) { return hao_deliver_part(c, slot, out, &hao_ctx::Batch::Slot::wl, HAO_DELIVER_WLIST, "hao_deliver_wlist", "HAO_DELIVER_WLIST"); }
 
 uint64_t hao_unpack_wlist(const hao_delivery_t *d, const hao_ed_delivery_t *e, const hao_rescue_delivery_t *r, const hao_wlist_delivery_t *w, const uint32_t *len, uint64_t rid,

@@ -138,6 +138,7 @@ enum hao_peek_id : int {
 	PK_TG_TRACED, PK_TG_CTR, PK_TG_NCIG,                                      // hao_f3.hip, traced grid: selected pairs; (entry bound, untraced pairs); cigar entries
 	PK_RS_SIZES, PK_RS_WAITING, PK_RS_TOTAL, PK_RS_NWINS,                     //   rescue: (states, record slots); lanes still waiting after a round; rescued windows; records
 	PK_WL_N, PK_WL_PLAN, PK_WL_NCIG, PK_WL_CTR,                               //   window lists: records; (swept records, entry bound, -); cigar entries; the stage's six counters
+	PK_LD_SETUP, PK_LD_ROUND, PK_LD_SEL, PK_LD_END,                           //   threshold ladder: (refused requests, open requests); a round's counters (hao_ladder.cuh: HAO_LD_RND ..); selected pairs per (mode, cooperative class); (cigar entries, rows that overran)
 	PK_COUNT
 };
 struct hao_peek_rng { int at, n; };
@@ -150,6 +151,7 @@ static constexpr hao_peek_rng HAO_PEEK[PK_COUNT] = {
 	/* PK_TG_TRACED */ {33, 1}, /* PK_TG_CTR */ {34, 2}, /* PK_TG_NCIG */ {36, 1},
 	/* PK_RS_SIZES */ {40, 2}, /* PK_RS_WAITING */ {42, 1}, /* PK_RS_TOTAL */ {43, 1}, /* PK_RS_NWINS */ {44, 1},
 	/* PK_WL_N */ {48, 1}, /* PK_WL_PLAN */ {49, 3}, /* PK_WL_NCIG */ {52, 1}, /* PK_WL_CTR */ {53, 6},
+	/* PK_LD_SETUP */ {80, 2}, /* PK_LD_ROUND */ {82, 48}, /* PK_LD_SEL */ {130, 16}, /* PK_LD_END */ {146, 2},
 };
 constexpr int HAO_PEEK_WORDS = 512;
 constexpr bool hao_peek_table_ok()
@@ -272,6 +274,14 @@ struct hao_ctx {
 		std::vector<uint64_t> h_woff, h_cig_off, r_woff, r_cig_off; std::vector<hao_rs_win> h_wins; std::vector<uint16_t> h_cig;
 	} wl;
 	uint64_t wl_out[5] = { 0, 0, 0, 0, 0 };
+	// the threshold ladder (hao_ladder.cuh; hao_window_ladder): requests, results, the attempts' thresholds, entry counts / row references / CSR offsets per request,
+	// the open lists of this round and the next, per slot of a round the coordinates, the selected pairs of the cooperative classes and their column offsets, the
+	// cigar rows of each round (kept until the CSR array is filled), the CSR array, 64 counters
+	struct Ladder {
+		DevBuf<hao_ladder_req_t> req; DevBuf<hao_ladder_res_t> res; DevBuf<int32_t> att; DevBuf<uint64_t> ncig, rowref, off, poff, selcnt; DevBuf<uint32_t> open[2], sel; DevBuf<hao_ld_coord> coord;
+		DevBuf<uint16_t> rows[4], cig; DevBuf<unsigned long long> ctr;
+	} ld;
+	bool ld_valid = false; uint64_t ld_ncig = 0, ld_rounds[4] = { 0, 0, 0, 0 };      // hao_fetch_ladder: the last call's entries are resident in ld.cig; their number; the open requests of each round
 	// f3 with traceback on the grid (hao_trace_grid.cuh): the stage's scratch, compute stream only (hao_window_trace_grid and HAO_DELIVER_TRACE share it) -
 	// flags and selected pairs, entry counts and their scans, the compact array's offsets, the column scratch, the rows of one slice, two counters
 	struct TraceGrid {

@@ -1,7 +1,7 @@
 // libhao.so, second translation unit: f3, the window-alignment batches (hao_align.cuh) - 36 instantiations of hao_al_kernel (five modes, with and without
 // traceback, bands of one to four words), the nine of the cooperative kernel for wider bands (hao_align_coop.cuh), the four of the delivery path's kernel (hao_ed_deliver.cuh) and the four of the traced grid stage's
 // (hao_trace_grid.cuh) that the rest of the library reaches through hao_al_ed_resident / hao_al_ed_deliver / hao_al_trace_grid only, the rescue stage
-// (hao_rescue.cuh, hao_al_rescue) and the window lists (hao_wlist.cuh, hao_al_wlist); compiled beside
+// (hao_rescue.cuh, hao_al_rescue), the window lists (hao_wlist.cuh, hao_al_wlist) and the threshold ladder (hao_ladder.cuh, hao_al_ladder); compiled beside
 // hao_capi.hip (hifiasm_amd/build.py).
 #include <algorithm>
 #include <cmath>
@@ -15,6 +15,7 @@
 #include "hao_trace_grid.cuh"
 #include "hao_rescue.cuh"
 #include "hao_wlist.cuh"
+#include "hao_ladder.cuh"
 
 // ---- f3 (hao_align.cuh): host side of the window-alignment batches ----
 // tasks -> device, and their order by text window (hao_align.cuh: a wave takes 64 neighbours of that order, which mostly share one text)
@@ -516,4 +517,124 @@ int hao_window_trace_long(hao_ctx *c, int mode, const hao_ed_task_t *tasks, uint
 	return HAO_OK;
 }
 
+}
+
+// ---- the threshold ladder (hao_ladder.cuh; hao_window_ladder, hao_capi_rest.hpp) ----
+// one round's sweeps of one mode over the sorted slots: lo[k] .. lo[k + 1] = class k's stretch of `order` (class 0: hao_al_trace_run, which selects and traces on
+// its own; classes 1 - 4: the first sweep of the cooperative kernel and the selection of the pairs that aligned, into sel / selcnt)
+template<int MODE> static int hao_ld_first(hao_ctx *c, const hao_ed_reads &R, int mode, const uint64_t lo[6], uint32_t words, uint64_t tn_max0, hao_trace_result_t *dr, uint8_t *want, uint16_t *dc, uint32_t cap)
+{
+	hao_ctx::Ladder &G = c->ld; const uint32_t *order = c->al_order.p;
+	if (lo[1] > lo[0]) { if (int rc = hao_al_trace_run<MODE>(c, R, c->al_task.p, order + lo[0], lo[1] - lo[0], words, tn_max0, dr, want, dc, cap)) return rc; }
+	for (int k = 1; k <= 4; ++k) if (lo[k + 1] > lo[k]) {
+		const uint64_t m = lo[k + 1] - lo[k];
+		if (int rc = hao_alc_launch<MODE, false>(c, R, k, order + lo[k], m, nullptr, nullptr, nullptr, dr, want, nullptr, 0u)) return rc;
+		size_t tb = 0;
+		HIP_TRY(rocprim::select(nullptr, tb, order + lo[k], G.sel.p + lo[k], G.selcnt.p + mode * 4 + (k - 1), m, hao_al_flagged{want}, c->stream)); HIP_TRY(hao_tmp(c, tb));
+		HIP_TRY(rocprim::select(c->d_tmp.p, tb, order + lo[k], G.sel.p + lo[k], G.selcnt.p + mode * 4 + (k - 1), m, hao_al_flagged{want}, c->stream));
+	}
+	return HAO_OK;
+}
+// the second sweep of class k's n_sel selected pairs (sel: their slots), every pair with a column block of pw words, in slices that fit the column budget
+template<int MODE> static int hao_ld_second(hao_ctx *c, const hao_ed_reads &R, int k, const uint32_t *sel, uint64_t n_sel, uint64_t pw, hao_trace_result_t *dr, uint16_t *dc, uint32_t cap)
+{
+	hao_ctx::Ladder &G = c->ld;
+	const uint64_t per = std::max<uint64_t>(1, std::min<uint64_t>(n_sel, (c->sw.al_slice / 8) / pw));
+	HIP_TRY(G.poff.reserve(n_sel + 1)); HIP_TRY(c->al_path.reserve(per * pw + 1));
+	hipLaunchKernelGGL(hao_ld_poff_kernel, dim3((unsigned)((n_sel + 255) / 256)), dim3(256), 0, c->stream, G.poff.p, n_sel, per, pw); HAO_CHECK_LAUNCH();
+	for (uint64_t at = 0; at < n_sel; at += per) {
+		if (int rc = hao_alc_launch<MODE, true>(c, R, k, sel + at, std::min<uint64_t>(per, n_sel - at), c->al_path.p, G.poff.p + at, nullptr, dr, nullptr, dc, cap)) return rc; }
+	return HAO_OK;
+}
+
+// n requests (already in c->ld.req) over the overlaps ol[n_ol] and their fake cigars: results in c->ld.res, CSR offsets in c->ld.off (n + 1), entries in c->ld.cig;
+// *n_cigar = the entries.  Host round trips: one for the checks, per round one for its counters, one per mode with narrow bands (hao_al_trace_run's selection) and
+// one for the cooperative classes' selections, one for the total at the end.
+int hao_al_ladder(hao_ctx *c, const hao_ovlp_t *ol, uint64_t n_ol, const uint64_t *fc, const uint64_t *fc_off, uint64_t n, double e_rate, int64_t maxl, int64_t maxe, uint64_t *n_cigar, uint64_t rounds_out[4])
+{
+	hao_ctx::Ladder &G = c->ld; *n_cigar = 0;
+	hao_read_view V; (void)hao_reads_view(c, &V);
+	const hao_ed_reads R = hao_al_reads_of(c);
+	HIP_TRY(G.res.reserve(n)); HIP_TRY(G.att.reserve(4 * n)); HIP_TRY(G.ncig.reserve(n + 1)); HIP_TRY(G.rowref.reserve(n)); HIP_TRY(G.off.reserve(n + 2)); HIP_TRY(G.open[0].reserve(n)); HIP_TRY(G.open[1].reserve(n));
+	HIP_TRY(G.sel.reserve(n)); HIP_TRY(G.selcnt.reserve(16)); HIP_TRY(G.coord.reserve(n)); HIP_TRY(G.ctr.reserve(64)); HIP_TRY(G.cig.reserve(1));
+	HIP_TRY(c->al_task.reserve(n)); HIP_TRY(c->al_k1.reserve(n)); HIP_TRY(c->al_k2.reserve(n)); HIP_TRY(c->al_i1.reserve(n)); HIP_TRY(c->al_order.reserve(n)); HIP_TRY(c->al_tres.reserve(n)); HIP_TRY(c->al_want.reserve(n));
+	HIP_TRY(hipMemsetAsync(G.ctr.p, 0, 64 * 8, c->stream));
+	hao_ld_args A; A.req = G.req.p; A.n_req = n; A.ol = ol; A.n_ol = n_ol; A.fc = fc; A.fc_off = fc_off; A.len = V.len; A.n_reads = V.n; A.e_rate = e_rate; A.maxl = maxl; A.maxe = maxe; A.coop_all = c->sw.al_coop ? 1 : 0;
+	const dim3 b_(256), gn((unsigned)((n + 255) / 256));
+	hipLaunchKernelGGL(hao_ld_thre_kernel, gn, b_, 0, c->stream, A, G.att.p, G.res.p, G.ncig.p, G.open[0].p, G.ctr.p); HAO_CHECK_LAUNCH();
+	if (int rc = hao_peek(c, G.ctr.p, 2, PK_LD_SETUP)) return rc;
+	HIP_TRY(hipStreamSynchronize(c->stream));
+	if (c->peeked(PK_LD_SETUP)) { hao_set_err(c, "hao_window_ladder: " + std::to_string(c->peeked(PK_LD_SETUP)) + " requests out of range (overlap index, mode, estimate_err, coordinates, or a length beyond HAO_ED_LONG_MAX_LEN)"); return HAO_EINVAL; }
+	uint64_t m = c->peeked(PK_LD_SETUP, 1);
+	hao_ld_rows W; for (int j = 0; j < 4; ++j) { W.rows[j] = nullptr; W.cap[j] = 0; rounds_out[j] = 0; }
+	for (int j = 0; j < 4 && m; ++j) {
+		rounds_out[j] = m;
+		const uint32_t *open = G.open[j & 1].p; uint32_t *next = G.open[(j + 1) & 1].p;
+		const dim3 gm((unsigned)((m + 255) / 256));
+		HIP_TRY(hipMemsetAsync(G.ctr.p + HAO_LD_RND, 0, HAO_LD_RND_N * 8, c->stream)); HIP_TRY(hipMemsetAsync(G.selcnt.p, 0, 16 * 8, c->stream)); HIP_TRY(hipMemsetAsync(c->al_want.p, 0, m, c->stream));
+		hipLaunchKernelGGL(hao_ld_task_kernel, gm, b_, 0, c->stream, A, j, G.att.p, open, m, c->al_task.p, G.coord.p, c->al_k1.p, c->al_i1.p, G.ctr.p); HAO_CHECK_LAUNCH();
+		size_t tb = 0;
+		HIP_TRY(rocprim::radix_sort_pairs(nullptr, tb, c->al_k1.p, c->al_k2.p, c->al_i1.p, c->al_order.p, m, 0, 64, c->stream)); HIP_TRY(hao_tmp(c, tb));
+		HIP_TRY(rocprim::radix_sort_pairs(c->d_tmp.p, tb, c->al_k1.p, c->al_k2.p, c->al_i1.p, c->al_order.p, m, 0, 64, c->stream));
+		if (int rc = hao_peek(c, G.ctr.p + HAO_LD_RND, HAO_LD_RND_N, PK_LD_ROUND)) return rc;
+		HIP_TRY(hipStreamSynchronize(c->stream));
+		auto rnd = [&](int k) { return (uint64_t)c->peeked(PK_LD_ROUND, k - HAO_LD_RND); };
+		// a row of the round holds the longest cigar an alignment within the round's widest threshold can have (hao.h: 2 thre + 3 for strings this short)
+		const uint32_t cap = 2 * (uint32_t)rnd(HAO_LD_THRE) + 3;
+		uint64_t lo[4][6], at = 0, n_task = 0;
+		for (int md = 0; md < 4; ++md) { for (int k = 0; k < 5; ++k) { lo[md][k] = at; at += rnd(HAO_LD_CNT + md * 5 + k); } lo[md][5] = at; }
+		n_task = at;
+		if (n_task > m) { hao_set_err(c, "hao_window_ladder: more tasks than open requests"); return HAO_EUNSUPP; }
+		DevBuf<uint16_t> &rows = G.rows[j];
+		HIP_TRY(rows.reserve(m * (uint64_t)cap + 1)); W.rows[j] = rows.p; W.cap[j] = cap;
+		hao_trace_result_t *dr = c->al_tres.p; uint8_t *want = c->al_want.p;
+		for (int md = 0; md < 4; ++md) if (lo[md][5] > lo[md][0]) {
+			const uint32_t words = (uint32_t)rnd(HAO_LD_WORDS + md); const uint64_t tn0 = std::max<uint64_t>(1, rnd(HAO_LD_TN + md)); int rc;
+			if (md == HAO_ALIGN_EXT_FWD) rc = hao_ld_first<HAO_AL_EXT_FWD>(c, R, md, lo[md], words, tn0, dr, want, rows.p, cap);
+			else if (md == HAO_ALIGN_EXT_BWD) rc = hao_ld_first<HAO_AL_EXT_BWD>(c, R, md, lo[md], words, tn0, dr, want, rows.p, cap);
+			else if (md == HAO_ALIGN_SEMI) rc = hao_ld_first<HAO_AL_SEMI>(c, R, md, lo[md], words, tn0, dr, want, rows.p, cap);
+			else rc = hao_ld_first<HAO_AL_GLOBAL>(c, R, md, lo[md], words, tn0, dr, want, rows.p, cap);
+			if (rc) return rc;
+		}
+		bool coop = false; for (int md = 0; md < 4; ++md) coop = coop || lo[md][5] > lo[md][1];
+		if (coop) {
+			if (int rc = hao_peek(c, G.selcnt.p, 16, PK_LD_SEL)) return rc;
+			HIP_TRY(hipStreamSynchronize(c->stream));
+			for (int md = 0; md < 4; ++md) for (int k = 1; k <= 4; ++k) {
+				const uint64_t n_sel = c->peeked(PK_LD_SEL, md * 4 + (k - 1)), pw = rnd(HAO_LD_PW + md * 4 + (k - 1));
+				if (!n_sel) continue;
+				if (n_sel > lo[md][k + 1] - lo[md][k] || !pw) { hao_set_err(c, "hao_window_ladder: more selected pairs than tasks"); return HAO_EUNSUPP; }
+				const uint32_t *sel = G.sel.p + lo[md][k]; int rc;
+				if (md == HAO_ALIGN_EXT_FWD) rc = hao_ld_second<HAO_AL_EXT_FWD>(c, R, k, sel, n_sel, pw, dr, rows.p, cap);
+				else if (md == HAO_ALIGN_EXT_BWD) rc = hao_ld_second<HAO_AL_EXT_BWD>(c, R, k, sel, n_sel, pw, dr, rows.p, cap);
+				else if (md == HAO_ALIGN_SEMI) rc = hao_ld_second<HAO_AL_SEMI>(c, R, k, sel, n_sel, pw, dr, rows.p, cap);
+				else rc = hao_ld_second<HAO_AL_GLOBAL>(c, R, k, sel, n_sel, pw, dr, rows.p, cap);
+				if (rc) return rc;
+			}
+		}
+		hipLaunchKernelGGL(hao_ld_commit_kernel, gm, b_, 0, c->stream, j, G.att.p, open, m, c->al_task.p, G.coord.p, dr, cap, G.res.p, G.ncig.p, G.rowref.p, next, G.ctr.p); HAO_CHECK_LAUNCH();
+		// the next round's list becomes the open one; its count crosses with the checks of the next round - here, to size that round's launches
+		HIP_TRY(hipMemcpyAsync(G.ctr.p + HAO_LD_OPEN, G.ctr.p + HAO_LD_NEXT, 8, hipMemcpyDeviceToDevice, c->stream)); HIP_TRY(hipMemsetAsync(G.ctr.p + HAO_LD_NEXT, 0, 8, c->stream));
+		if (int rc = hao_peek(c, G.ctr.p, 2, PK_LD_SETUP)) return rc;
+		HIP_TRY(hipStreamSynchronize(c->stream));
+		m = c->peeked(PK_LD_SETUP, 1);
+		if (m > n) { hao_set_err(c, "hao_window_ladder: more open requests than requests"); return HAO_EUNSUPP; }
+	}
+	HIP_TRY(hipMemsetAsync(G.ncig.p + n, 0, 8, c->stream));
+	if (int rc = hao_excl_scan_u64(c, G.ncig.p, G.off.p, n + 1)) return rc;
+	HIP_TRY(hipMemcpyAsync(G.ctr.p + HAO_LD_NEXT, G.off.p + n, 8, hipMemcpyDeviceToDevice, c->stream));
+	if (int rc = hao_peek(c, G.ctr.p + HAO_LD_NEXT, 2, PK_LD_END)) return rc;
+	HIP_TRY(hipStreamSynchronize(c->stream));
+	const uint64_t total = c->peeked(PK_LD_END);
+	if (c->peeked(PK_LD_END, 1)) { hao_set_err(c, "hao_window_ladder: " + std::to_string(c->peeked(PK_LD_END, 1)) + " cigars longer than their row"); return HAO_EUNSUPP; }      // (2 thre + 3 entries bound an alignment within thre)
+	HIP_TRY(G.cig.reserve(total + 1));
+	if (total) { hipLaunchKernelGGL(hao_ld_fill_kernel, dim3((unsigned)((n * 64 + 255) / 256)), b_, 0, c->stream, W, G.ncig.p, G.rowref.p, G.off.p, n, G.cig.p, total); HAO_CHECK_LAUNCH(); }
+	*n_cigar = total;
+	return HAO_OK;
+}
+
+extern "C" int hao_ladder_thresholds(int64_t ql, int64_t estimate_err, double e_rate, int64_t maxl, int64_t maxe, int32_t thre[4])
+{
+	if (!thre) return HAO_EINVAL;
+	return hao_ld_rungs(ql, estimate_err, e_rate, maxl, maxe, thre);
 }

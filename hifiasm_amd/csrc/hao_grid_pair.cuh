@@ -130,6 +130,8 @@ struct hao_rs_state { uint32_t ol; int32_t phase, k, j, last, cs; uint32_t aflag
 #define HAO_RS_UNTRACED_BIT (1u << 19)
 // a record's plan in the window-list stage (hao_wlist.cuh; here because the context holds a buffer of them): overlap, slot | source << 28 | needs-a-sweep bit, target offset of a rescue task
 struct hao_wl_plan { uint32_t ol, ks; int64_t toff; };
+// the threshold ladder (hao_ladder.cuh; here because the context holds a buffer of them): the coordinates an attempt hands the aligner, per slot of a round's open list
+struct hao_ld_coord { int32_t qs, qe, ts, te, aux; uint32_t flags; };
 
 // what the reference-placed generators read beside the overlaps: the covered windows of overlap i are slots win_off[i] .. win_off[i + 1] of shift[] (slot
 // k = grid window x_pos_s / window + k), tab = the threshold table; all null in diagonal placement

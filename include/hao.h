@@ -488,6 +488,44 @@ int hao_window_trace_batch(hao_ctx *c, int mode, const hao_ed_task_t *tasks, uin
 int hao_window_ed_long(hao_ctx *c, const hao_ed_task_t *tasks, uint64_t n_tasks, hao_ed_result_t *out);
 int hao_window_trace_long(hao_ctx *c, int mode, const hao_ed_task_t *tasks, uint64_t n_tasks, hao_trace_result_t *out, uint16_t *cigars, uint32_t cigar_cap);
 
+/* The threshold ladder of hc_aln_exz (Correct.cpp:14576-14636) on the device: the caller of the long alignments.  A request names a stretch [qs, qe) of the
+ * query read of overlap `ol` (index into the resident ol->list of the current batch, all reads of the batch counted through) and, for modes 0 - 2, a stretch
+ * [ts, te) of its target; ts == te == -1 forces mode 3, as :14582 does.  Per request the stage makes up to four attempts (rungs) at growing thresholds -
+ * scale_ed_thre(estimate_err), ql * e_rate, twice the second, ql * 0.51, each through scale_ed_thre(., maxe) and capped at ql = qe - qs, a rung skipped unless its
+ * threshold exceeds the one before - and every attempt is one cal_exz_infi (:14508-14574): the coordinate step of the mode (3: update_semi_coord over the
+ * overlap's resident fake cigar and init_waln; 1 / 2: adjust_ext_offset with the rung's threshold; 0: none), the test qe > qs && te > ts, and the traced
+ * alignment of hao_window_trace_long in the band that threshold asks for.  The first rung whose alignment ends within its threshold is the result.  A request with
+ * ql > maxl or estimate_err * 1.2 > maxe gets rung 0 without an attempt.  q_tot is the length of the overlap's query read, t_tot of its target.
+ *   Result: rung (0: none), its threshold, the coordinates and aux_beg the aligner was given (rung 0: the request's own, ts = te = -1 in mode 3,
+ *   thre = aux_beg = 0), the bit_extz_t fields of hao_trace_result_t (rung 0: err INT32_MAX, the others -1, no cigar), and flags over ALL attempts made:
+ *     HAO_LADDER_REFUSED   an attempt's coordinate step left nothing to align (init_waln refused, or an empty interval): that attempt failed, as in the reference;
+ *     HAO_LADDER_UNTRACED  a mode-3 attempt whose start resolves to no fake-cigar entry (the reference exits there) or whose band does not cover the pattern
+ *                          (HAO_ALIGN_SEMI's domain: the reference's traceback would index its columns out of range): nothing is guessed, the attempt failed.
+ *   Cigars in CSR form, push_trace's encoding: request i's entries at cigars[cig_off[i] .. cig_off[i + 1]).  out, cig_off (n + 1 entries) and *n_cigar (the
+ *   entries of all requests) are always written; the entries only when *n_cigar <= cigar_cap - call again with that capacity otherwise.
+ * On the device: one kernel computes every request's rungs; then at most four rounds of a coordinate-and-task kernel over the open requests, the traced sweeps by
+ * band width (hao_al_kernel up to four words, hao_alc_kernel beyond) and a commit kernel that writes the results of the requests that aligned and compacts the
+ * rest into the next round's list.  Only counters cross to the host between rounds.
+ * Blocking; over the current batch (HAO_EINVAL without one).  Like every host-fed window-alignment call it takes the shared task scratch: fetch what
+ * hao_window_ed_ref / hao_window_wlist_ref left before calling it.  Attached contexts and sharded engines (after hao_dist_gather_reads; HAO_EUNSUPP before) as for
+ * the batch calls.  HAO_EINVAL: maxe > HAO_ED_LONG_MAX_THRE or negative, maxl negative, e_rate outside [0, 1], and any request with `ol` outside the batch, a mode outside 0 - 3,
+ * estimate_err outside [0, 2^30), coordinates outside 0 <= qs <= qe <= q_tot or (modes 0 - 2; mode 3 does not read ts / te) 0 <= ts <= te <= t_tot, or - for a request that passes the maxl / maxe gate - ql or a
+ * text length an attempt derives beyond HAO_ED_LONG_MAX_LEN.
+ * Not built: adjust_specific_ext_offset (:14424; the caller passes the interval and the mode it wants), hc_aln_exz_adv and its fifth rung, a streamed part. */
+typedef struct { uint32_t ol, mode; int32_t qs, qe, ts, te, estimate_err; uint32_t reserved; } hao_ladder_req_t;      /* 32 bytes */
+typedef struct { uint32_t rung; int32_t thre, qs, qe, ts, te, aux_beg; uint32_t flags; int32_t err, a_ps, a_pe, a_ts, a_te, n_cigar; } hao_ladder_res_t;      /* 56 bytes */
+#define HAO_LADDER_REFUSED 1u
+#define HAO_LADDER_UNTRACED 2u
+int hao_window_ladder(hao_ctx *c, const hao_ladder_req_t *req, uint64_t n_req, double e_rate, int64_t maxl, int64_t maxe,
+                      hao_ladder_res_t *out, uint64_t *cig_off, uint16_t *cigars, uint64_t cigar_cap, uint64_t *n_cigar);
+/* The cigar entries of the last hao_window_ladder call on this context, which stay resident until its next call (HAO_EINVAL before the first and after one that
+ * failed): *n_cigar = their number, the entries into cigars when they fit cigar_cap - so a caller that does not know the capacity runs the stage once, not
+ * twice - and rounds[j] = the requests that were open in round j (n_cigar, cigars and rounds may be NULL). */
+int hao_fetch_ladder(hao_ctx *c, uint16_t *cigars, uint64_t cigar_cap, uint64_t *n_cigar, uint64_t rounds[4]);
+/* TEST SUPPORT, not part of the stable interface (it may change or go with the kernel it mirrors): host code, no context - the rungs of one request as the
+ * kernel computes them, thre[4] (-1 where the rung is skipped or the gate is shut); returns the number of attempts */
+int hao_ladder_thresholds(int64_t ql, int64_t estimate_err, double e_rate, int64_t maxl, int64_t maxe, int32_t thre[4]);
+
 /* f3 with traceback on the device grid: the semi-global traced alignment (HAO_ALIGN_SEMI: ed_band_cal_semi_64_w_absent_diag_trace + gen_trace, the call
  * Correct.cpp:3897-3911 makes right after the distance-only one) of the grid pairs hao_window_ed_grid(window, thre) forms, in the same text order.  A pair is
  * TRACED iff its distance-only result aligned (err <= thre) and its band covers the pattern (0 <= p_len - t_len + abs_diag <= 2 thre, t_len > abs_diag: the
