@@ -348,7 +348,7 @@ int hao_window_trace_grid(hao_ctx *c, uint32_t window, uint32_t thre, uint64_t o
 {
 	if (!c || !out) return HAO_EINVAL;
 	const int rc = hao_window_stage(c, nullptr, [&] { return hao_trace_grid_run(c, window, thre, out); });      // (hao_stage_times: ed_grid, ed_align, trace_sel, trace_align)
-	if (!rc && c->tg.path.cap > (1ULL << 27)) c->tg.path.release();      // (more than 1 GB of column scratch is not kept between blocking calls)
+	if (!rc) hao_release_above(c->tg.path, HAO_SCRATCH_KEEP);      // (between blocking calls)
 	return rc;
 }
 
@@ -572,8 +572,8 @@ static int hao_ladder_run(hao_ctx *c, const hao_ladder_req_t *req, uint64_t n, d
 	HIP_TRY(hipMemcpyAsync(cig_off, G.off.p, (n + 1) * 8, hipMemcpyDeviceToHost, c->stream));
 	if (*n_cigar && *n_cigar <= cigar_cap) HIP_TRY(hipMemcpyAsync(cigars, G.cig.p, *n_cigar * 2, hipMemcpyDeviceToHost, c->stream));
 	HIP_TRY(hipStreamSynchronize(c->stream));
-	if (c->al_path.cap > (1ULL << 27)) c->al_path.release();      // (more than 1 GB of column scratch is not kept between calls)
-	for (int j = 0; j < 4; ++j) if (G.rows[j].cap > (1ULL << 29)) G.rows[j].release();      // (nor more than 1 GB of cigar rows)
+	hao_release_above(c->al_path, HAO_SCRATCH_KEEP);
+	for (int j = 0; j < 4; ++j) hao_release_above(G.rows[j], HAO_SCRATCH_KEEP);
 	c->ld_ncig = *n_cigar; c->ld_valid = true;
 	return HAO_OK;
 }

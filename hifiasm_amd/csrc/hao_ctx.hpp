@@ -6,6 +6,7 @@
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
+#include <type_traits>
 #include "hao_common.cuh"
 #include "hao_grid_pair.cuh"      // (hao_ed_pair)
 
@@ -111,7 +112,7 @@ struct hao_switches {
 			if (in_kv(v, "qmz_raw", x)) qmz_raw = x != 0;                   // the delivered minimizer tables in their 8-byte form whatever the read lengths (the form of batches with a read of 65 536 bases or more)
 			if (in_kv(v, "arena_probe", x)) arena_probe = x != 0;           // the delivery arenas' placement probe (hao_arena_ensure) whatever their size and rate
 			if (in_kv(v, "ft_chunk_slots", x)) ft_chunk_slots = (long long)x;      // k-mer slots hashed per chunk of reads in ha_ft_gen's pass mode
-			if (in_kv(v, "al_slice", x)) al_slice = std::max<unsigned long long>(x, 8);      // bytes of column scratch per slice of hao_window_trace_long's second sweep (default 4 GB: a few hundred KB walk several slices on a handful of pairs)
+			if (in_kv(v, "al_slice", x)) al_slice = std::max<unsigned long long>(x, 8);      // bytes of column scratch per slice of every traced sweep (default 4 GB): hao_col_slice's stages - hao_window_trace_batch's second sweep, the traced grid, the rescue rounds, the window lists - cut whole blocks of 256 pairs, so 8 gives them slices of 256; hao_window_trace_long's and the ladder's second sweeps pack per-pair blocks (a few hundred KB walk several slices on a handful of pairs)
 			if (in_kv(v, "gather_chunk", x)) gather_chunk = std::max<unsigned long long>(x, 64);      // bytes a rank contributes per exchange of hao_dist_gather_reads (default 64 MB: a few KB walk the multi-chunk path on a small read set)
 		}
 		if (const char *e = getenv("HAO_SEED_LDS")) seed_lds = atoi(e) ? 1 : 0;      // 0 = the table kernels (hao_query.cuh, hao_query3.cuh) for every read instead of the list-major kernel (hao_query5.cuh): the tests run them on every scenario - they carry repeat-rich batches and the reads the list-major kernel leaves
@@ -338,15 +339,46 @@ static inline bool hao_reads_view(const hao_ctx *c, hao_read_view *V)
 // scratch for rocprim calls
 static inline hipError_t hao_tmp(hao_ctx *c, size_t bytes) { return c->d_tmp.reserve(bytes + 256); }
 
+// a rocprim call: run(nullptr, bytes) asks for the scratch size, run(scratch, bytes) does the work
+template<typename F>
+static int hao_rocprim(hao_ctx *c, F run)
+{
+	size_t tb = 0;
+	HIP_TRY(run((void*)nullptr, tb));
+	HIP_TRY(hao_tmp(c, tb));
+	HIP_TRY(run((void*)c->d_tmp.p, tb));
+	return HAO_OK;
+}
 template<typename In, typename Out>
 static int hao_excl_scan_u64(hao_ctx *c, In in, Out out, size_t n)
 {
-	size_t tb = 0;
-	HIP_TRY(rocprim::exclusive_scan(nullptr, tb, in, out, (uint64_t)0, n, rocprim::plus<uint64_t>(), c->stream));
-	HIP_TRY(hao_tmp(c, tb));
-	HIP_TRY(rocprim::exclusive_scan(c->d_tmp.p, tb, in, out, (uint64_t)0, n, rocprim::plus<uint64_t>(), c->stream));
-	return HAO_OK;
+	return hao_rocprim(c, [&](void *tmp, size_t &tb) { return rocprim::exclusive_scan(tmp, tb, in, out, (uint64_t)0, n, rocprim::plus<uint64_t>(), c->stream); });
 }
+// (k_in, v_in) -> (k_out, v_out), stable, by the low `bits` bits of the key
+template<typename K, typename V>
+static int hao_sort_pairs(hao_ctx *c, K *k_in, K *k_out, V *v_in, V *v_out, size_t n, unsigned bits)
+{
+	return hao_rocprim(c, [&](void *tmp, size_t &tb) { return rocprim::radix_sort_pairs(tmp, tb, k_in, k_out, v_in, v_out, n, 0, bits, c->stream); });
+}
+// out = the entries of `in` that a flag array (a pointer: flag[i] of entry i) or a predicate on the entry's value keeps, in order; *count = how many
+template<typename In, typename F, typename Out>
+static int hao_select(hao_ctx *c, In in, F flags_or_pred, Out out, uint64_t *count, size_t n)
+{
+	return hao_rocprim(c, [&](void *tmp, size_t &tb) {
+		if constexpr (std::is_pointer<F>::value) return rocprim::select(tmp, tb, in, flags_or_pred, out, count, n, c->stream);
+		else return rocprim::select(tmp, tb, in, out, count, n, flags_or_pred, c->stream);
+	});
+}
+
+// column scratch of the window-alignment stages: pairs per slice of a sweep over n pairs that keeps bytes_per_pair each - whole blocks of 256, within the budget
+// (c->sw.al_slice, 4 GB unless a test shrinks it), one block at the least
+static inline uint64_t hao_col_slice(const hao_ctx *c, uint64_t n, uint64_t bytes_per_pair)
+{
+	return std::max<uint64_t>(256, std::min<uint64_t>((n + 255) & ~255ULL, (c->sw.al_slice / bytes_per_pair) & ~255ULL));
+}
+// scratch of more than `bytes` is not kept between calls
+#define HAO_SCRATCH_KEEP (1ULL << 30)
+template<typename T> static inline void hao_release_above(DevBuf<T> &b, uint64_t bytes) { if ((uint64_t)b.cap * sizeof(T) > bytes) b.release(); }
 
 // An attached batch context (hao_attach) reads the owner's read store and index through borrowed pointers; they are taken again whenever the owner has
 // rebuilt something since (the owner must not be rebuilding while a view runs a batch: same rule as for the owner's own batches).

@@ -17,6 +17,35 @@
 #include "hao_wlist.cuh"
 #include "hao_ladder.cuh"
 
+// ---- the choices every stage makes, each written once ----
+// f(hao_type<WT>{}) with the band vector of nword 64-bit words (one to four: the callers hold wider bands off)
+template<typename T> struct hao_type { using type = T; };
+template<typename F> static void hao_by_nword(uint32_t nword, F &&f)
+{
+	if (nword == 1) f(hao_type<uint64_t>{}); else if (nword == 2) f(hao_type<hao_u128>{}); else if (nword == 3) f(hao_type<hao_wide<3> >{}); else f(hao_type<hao_wide<4> >{});
+}
+// f(M), decltype(M)::value = hao_align.cuh's MODE of a traced mode of include/hao.h (HAO_ALIGN_*, which the entry points have checked)
+template<typename F> static int hao_by_mode(int mode, F &&f)
+{
+	if (mode == HAO_ALIGN_EXT_FWD) return f(std::integral_constant<int, HAO_AL_EXT_FWD>{});
+	if (mode == HAO_ALIGN_EXT_BWD) return f(std::integral_constant<int, HAO_AL_EXT_BWD>{});
+	if (mode == HAO_ALIGN_SEMI) return f(std::integral_constant<int, HAO_AL_SEMI>{});
+	return f(std::integral_constant<int, HAO_AL_GLOBAL>{});
+}
+// one sweep of hao_al_kernel over order[0 .. n): a launch per band word count set in `words` (bit nword - 1; a launch skips the tasks of the other widths, hao_al_mine)
+template<int MODE, bool TRACE> static int hao_al_sweep(hao_ctx *c, const hao_ed_reads &R, const hao_ed_task_t *tasks, const uint32_t *order, uint64_t n, uint32_t words,
+		uint64_t *path, uint64_t stride, hao_ed_result_t *out_ed, hao_trace_result_t *out_tr, uint8_t *want, uint16_t *dc, uint32_t cap)
+{
+	const dim3 g_((unsigned)((n + 255) / 256)), b_(256);
+	for (uint32_t nw = 1; nw <= 4; ++nw) if (words >> (nw - 1) & 1u) {
+		hao_by_nword(nw, [&](auto w) { hipLaunchKernelGGL((hao_al_kernel<typename decltype(w)::type, MODE, TRACE>), g_, b_, 0, c->stream, R, tasks, order, n, path, stride, out_ed, out_tr, want, dc, cap); });
+		HAO_CHECK_LAUNCH();
+	}
+	return HAO_OK;
+}
+// al_order = the slots of al_k1 / al_i1 (key and index per task) by key: text order
+static int hao_al_sort_by_text(hao_ctx *c, uint64_t n) { return hao_sort_pairs(c, c->al_k1.p, c->al_k2.p, c->al_i1.p, c->al_order.p, n, 64); }
+
 // ---- f3 (hao_align.cuh): host side of the window-alignment batches ----
 // tasks -> device, and their order by text window (hao_align.cuh: a wave takes 64 neighbours of that order, which mostly share one text)
 static int hao_al_upload_sorted(hao_ctx *c, const hao_ed_task_t *tasks, uint64_t n)
@@ -24,10 +53,7 @@ static int hao_al_upload_sorted(hao_ctx *c, const hao_ed_task_t *tasks, uint64_t
 	HIP_TRY(c->al_task.reserve(n)); HIP_TRY(c->al_k1.reserve(n)); HIP_TRY(c->al_k2.reserve(n)); HIP_TRY(c->al_i1.reserve(n)); HIP_TRY(c->al_order.reserve(n));
 	HIP_TRY(hipMemcpyAsync(c->al_task.p, tasks, n * sizeof(hao_ed_task_t), hipMemcpyHostToDevice, c->stream));
 	hipLaunchKernelGGL(hao_al_key_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, c->al_task.p, n, c->al_k1.p, c->al_i1.p); HAO_CHECK_LAUNCH();
-	size_t tb = 0;
-	HIP_TRY(rocprim::radix_sort_pairs(nullptr, tb, c->al_k1.p, c->al_k2.p, c->al_i1.p, c->al_order.p, n, 0, 64, c->stream)); HIP_TRY(hao_tmp(c, tb));
-	HIP_TRY(rocprim::radix_sort_pairs(c->d_tmp.p, tb, c->al_k1.p, c->al_k2.p, c->al_i1.p, c->al_order.p, n, 0, 64, c->stream));
-	return HAO_OK;
+	return hao_al_sort_by_text(c, n);
 }
 // the reads of a launch: the context's view (hao_ctx.hpp: hao_reads_view; the entry points refuse before they get here when there is none)
 static hao_ed_reads hao_al_reads_of(hao_ctx *c)
@@ -41,33 +67,20 @@ template<int MODE> static int hao_al_trace_run(hao_ctx *c, const hao_ed_reads &R
 		hao_trace_result_t *dr, uint8_t *want, uint16_t *dc, uint32_t cap)
 {
 	// first sweep: no column storage, every task; decides which tasks end within their threshold (want[])
-	const dim3 g_((unsigned)((n + 255) / 256)), b_(256);
-	// (one launch per band word count that occurs: a launch skips the tasks of the other widths, hao_al_mine)
-	if (words & 1u) { hipLaunchKernelGGL((hao_al_kernel<uint64_t, MODE, false>), g_, b_, 0, c->stream, R, dt, order, n, (uint64_t*)nullptr, (uint64_t)0, (hao_ed_result_t*)nullptr, dr, want, (uint16_t*)nullptr, 0u); HAO_CHECK_LAUNCH(); }
-	if (words & 2u) { hipLaunchKernelGGL((hao_al_kernel<hao_u128, MODE, false>), g_, b_, 0, c->stream, R, dt, order, n, (uint64_t*)nullptr, (uint64_t)0, (hao_ed_result_t*)nullptr, dr, want, (uint16_t*)nullptr, 0u); HAO_CHECK_LAUNCH(); }
-	if (words & 4u) { hipLaunchKernelGGL((hao_al_kernel<hao_wide<3>, MODE, false>), g_, b_, 0, c->stream, R, dt, order, n, (uint64_t*)nullptr, (uint64_t)0, (hao_ed_result_t*)nullptr, dr, want, (uint16_t*)nullptr, 0u); HAO_CHECK_LAUNCH(); }
-	if (words & 8u) { hipLaunchKernelGGL((hao_al_kernel<hao_wide<4>, MODE, false>), g_, b_, 0, c->stream, R, dt, order, n, (uint64_t*)nullptr, (uint64_t)0, (hao_ed_result_t*)nullptr, dr, want, (uint16_t*)nullptr, 0u); HAO_CHECK_LAUNCH(); }
+	if (int rc = hao_al_sweep<MODE, false>(c, R, dt, order, n, words, nullptr, 0, nullptr, dr, want, nullptr, 0u)) return rc;
 	// the tasks of the second sweep, still in text order
 	DevBuf<uint32_t> &sel = c->al_sel; DevBuf<uint64_t> &path = c->al_path; uint64_t n_sel = 0;
 	HIP_TRY(sel.reserve(n + 1)); HIP_TRY(c->d_cursor.reserve(2));
-	size_t tb = 0;
-	HIP_TRY(rocprim::select(nullptr, tb, order, sel.p, (uint64_t*)c->d_cursor.p, n, hao_al_flagged{want}, c->stream)); HIP_TRY(hao_tmp(c, tb));
-	HIP_TRY(rocprim::select(c->d_tmp.p, tb, order, sel.p, (uint64_t*)c->d_cursor.p, n, hao_al_flagged{want}, c->stream));
+	if (int rc = hao_select(c, order, hao_al_flagged{want}, sel.p, (uint64_t*)c->d_cursor.p, n)) return rc;
 	HIP_TRY(hipMemcpyAsync(&n_sel, c->d_cursor.p, 8, hipMemcpyDeviceToHost, c->stream));
 	HIP_TRY(hipStreamSynchronize(c->stream));
 	if (n_sel) {
-		// second sweep: 40 bytes per band word, text column and selected pair, in slices whose columns fit ~4 GB; then the traceback
+		// second sweep: 40 bytes per band word, text column and selected pair, in slices whose columns fit the budget; then the traceback
 		const uint64_t cw = 5 * (uint64_t)((words & 8u) ? 4 : (words & 4u) ? 3 : (words & 2u) ? 2 : 1);
-		const uint64_t slice = std::max<uint64_t>(256, std::min<uint64_t>((n_sel + 255) & ~255ULL, ((4ULL << 30) / (8 * cw * tn_max)) & ~255ULL));
+		const uint64_t slice = hao_col_slice(c, n_sel, 8 * cw * tn_max);
 		HIP_TRY(path.reserve(cw * tn_max * slice + 1));
 		for (uint64_t lo = 0; lo < n_sel; lo += slice) {
-			const uint64_t m = std::min<uint64_t>(slice, n_sel - lo);
-			const dim3 g2((unsigned)((m + 255) / 256));
-			if (words & 1u) { hipLaunchKernelGGL((hao_al_kernel<uint64_t, MODE, true>), g2, b_, 0, c->stream, R, dt, sel.p + lo, m, path.p, slice, (hao_ed_result_t*)nullptr, dr, (uint8_t*)nullptr, dc, cap); HAO_CHECK_LAUNCH(); }
-			if (words & 2u) { hipLaunchKernelGGL((hao_al_kernel<hao_u128, MODE, true>), g2, b_, 0, c->stream, R, dt, sel.p + lo, m, path.p, slice, (hao_ed_result_t*)nullptr, dr, (uint8_t*)nullptr, dc, cap); HAO_CHECK_LAUNCH(); }
-			if (words & 4u) { hipLaunchKernelGGL((hao_al_kernel<hao_wide<3>, MODE, true>), g2, b_, 0, c->stream, R, dt, sel.p + lo, m, path.p, slice, (hao_ed_result_t*)nullptr, dr, (uint8_t*)nullptr, dc, cap); HAO_CHECK_LAUNCH(); }
-			if (words & 8u) { hipLaunchKernelGGL((hao_al_kernel<hao_wide<4>, MODE, true>), g2, b_, 0, c->stream, R, dt, sel.p + lo, m, path.p, slice, (hao_ed_result_t*)nullptr, dr, (uint8_t*)nullptr, dc, cap); HAO_CHECK_LAUNCH(); }
-		}
+			if (int rc = hao_al_sweep<MODE, true>(c, R, dt, sel.p + lo, std::min<uint64_t>(slice, n_sel - lo), words, path.p, slice, nullptr, dr, nullptr, dc, cap)) return rc; }
 	}
 	return HAO_OK;
 }
@@ -78,14 +91,7 @@ int hao_al_ed_resident(hao_ctx *c, uint64_t n, uint32_t nword)
 	HIP_TRY(c->al_order.reserve(n + 1)); HIP_TRY(c->al_res.reserve(n + 1));
 	hipLaunchKernelGGL(hao_al_iota_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, c->al_order.p, n); HAO_CHECK_LAUNCH();
 	const hao_ed_reads R = hao_al_reads_of(c);
-	const dim3 g_((unsigned)((n + 255) / 256)), b_(256);
-	hao_ed_task_t *dt = c->al_task.p; uint32_t *order = c->al_order.p; hao_ed_result_t *dr = c->al_res.p;
-	if (nword == 1) hipLaunchKernelGGL((hao_al_kernel<uint64_t, HAO_AL_ED, false>), g_, b_, 0, c->stream, R, dt, order, n, (uint64_t*)nullptr, (uint64_t)0, dr, (hao_trace_result_t*)nullptr, (uint8_t*)nullptr, (uint16_t*)nullptr, 0u);
-	else if (nword == 2) hipLaunchKernelGGL((hao_al_kernel<hao_u128, HAO_AL_ED, false>), g_, b_, 0, c->stream, R, dt, order, n, (uint64_t*)nullptr, (uint64_t)0, dr, (hao_trace_result_t*)nullptr, (uint8_t*)nullptr, (uint16_t*)nullptr, 0u);
-	else if (nword == 3) hipLaunchKernelGGL((hao_al_kernel<hao_wide<3>, HAO_AL_ED, false>), g_, b_, 0, c->stream, R, dt, order, n, (uint64_t*)nullptr, (uint64_t)0, dr, (hao_trace_result_t*)nullptr, (uint8_t*)nullptr, (uint16_t*)nullptr, 0u);
-	else hipLaunchKernelGGL((hao_al_kernel<hao_wide<4>, HAO_AL_ED, false>), g_, b_, 0, c->stream, R, dt, order, n, (uint64_t*)nullptr, (uint64_t)0, dr, (hao_trace_result_t*)nullptr, (uint8_t*)nullptr, (uint16_t*)nullptr, 0u);
-	HAO_CHECK_LAUNCH();
-	return HAO_OK;
+	return hao_al_sweep<HAO_AL_ED, false>(c, R, c->al_task.p, c->al_order.p, n, 1u << (nword - 1), nullptr, 0, c->al_res.p, nullptr, nullptr, nullptr, 0u);
 }
 
 // the delivery path's alignment (HAO_DELIVER_ED, hao_batch.hpp): n pairs (overlap, window) of the batch's ol->list in text order -> err[n] / pe[n] of the output set
@@ -96,10 +102,7 @@ int hao_al_ed_deliver(hao_ctx *c, const hao_ovlp_t *ol, const hao_ed_pair *pairs
 	const dim3 g_((unsigned)((n + 255) / 256)), b_(256);
 	const uint32_t nword = hao_al_nword(thre);
 	if (place == HAO_PLACE_REF) hipLaunchKernelGGL((hao_ed_deliver_kernel<uint64_t, HAO_PLACE_REF>), g_, b_, 0, c->stream, R, ol, pairs, n, wl, thre, err, pe, A, werr);
-	else if (nword == 1) hipLaunchKernelGGL((hao_ed_deliver_kernel<uint64_t>), g_, b_, 0, c->stream, R, ol, pairs, n, wl, thre, err, pe, hao_ref_args{nullptr, nullptr, nullptr}, (uint8_t*)nullptr);
-	else if (nword == 2) hipLaunchKernelGGL((hao_ed_deliver_kernel<hao_u128>), g_, b_, 0, c->stream, R, ol, pairs, n, wl, thre, err, pe, hao_ref_args{nullptr, nullptr, nullptr}, (uint8_t*)nullptr);
-	else if (nword == 3) hipLaunchKernelGGL((hao_ed_deliver_kernel<hao_wide<3> >), g_, b_, 0, c->stream, R, ol, pairs, n, wl, thre, err, pe, hao_ref_args{nullptr, nullptr, nullptr}, (uint8_t*)nullptr);
-	else hipLaunchKernelGGL((hao_ed_deliver_kernel<hao_wide<4> >), g_, b_, 0, c->stream, R, ol, pairs, n, wl, thre, err, pe, hao_ref_args{nullptr, nullptr, nullptr}, (uint8_t*)nullptr);
+	else hao_by_nword(nword, [&](auto w) { hipLaunchKernelGGL((hao_ed_deliver_kernel<typename decltype(w)::type>), g_, b_, 0, c->stream, R, ol, pairs, n, wl, thre, err, pe, hao_ref_args{nullptr, nullptr, nullptr}, (uint8_t*)nullptr); });
 	HAO_CHECK_LAUNCH();
 	return HAO_OK;
 }
@@ -118,10 +121,8 @@ int hao_al_trace_grid(hao_ctx *c, const hao_ovlp_t *ol, const hao_ed_pair *pairs
 	HIP_TRY(G.want.reserve(n + 1)); HIP_TRY(G.sel.reserve(n + 1)); HIP_TRY(G.ctr.reserve(2)); HIP_TRY(c->d_cursor.reserve(2));
 	HIP_TRY(hipMemsetAsync(ps16, 0xff, n * 2, c->stream)); HIP_TRY(hipMemsetAsync(ncig16, 0, n * 2, c->stream)); HIP_TRY(hipMemsetAsync(G.ctr.p, 0, 16, c->stream));
 	hipLaunchKernelGGL(hao_tg_flag_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, R.len, ol, pairs, n, wl, thre, err, G.want.p, G.ctr.p); HAO_CHECK_LAUNCH();
-	size_t tb = 0;
 	const auto idx = rocprim::make_counting_iterator<uint32_t>(0);
-	HIP_TRY(rocprim::select(nullptr, tb, idx, G.want.p, G.sel.p, (uint64_t*)c->d_cursor.p, n, c->stream)); HIP_TRY(hao_tmp(c, tb));
-	HIP_TRY(rocprim::select(c->d_tmp.p, tb, idx, G.want.p, G.sel.p, (uint64_t*)c->d_cursor.p, n, c->stream));
+	if (int rc = hao_select(c, idx, G.want.p, G.sel.p, (uint64_t*)c->d_cursor.p, n)) return rc;
 	if (int rc = hao_peek(c, c->d_cursor.p, 1, PK_TG_TRACED)) return rc;
 	if (int rc = hao_peek(c, G.ctr.p, 2, PK_TG_CTR)) return rc;
 	HIP_TRY(hipStreamSynchronize(c->stream));
@@ -130,19 +131,16 @@ int hao_al_trace_grid(hao_ctx *c, const hao_ovlp_t *ol, const hao_ed_pair *pairs
 	c->timer.mark("trace_sel");
 	HIP_TRY(cig.reserve(bound + 1)); HIP_TRY(G.off.reserve(T + 2)); HIP_TRY(hipMemsetAsync(G.off.p, 0, 8, c->stream));      // (off[0] = 0: no traced pair, every offset is 0)
 	if (T) {
-		// column scratch: 24 bytes per band word, text column (t_len <= wl, + slot 0) and selected pair, in slices whose columns fit ~4 GB; rows of 2 thre + 3 entries per slice
+		// column scratch: 24 bytes per band word, text column (t_len <= wl, + slot 0) and selected pair, in slices whose columns fit the budget (hao_col_slice); rows of 2 thre + 3 entries per slice
 		const uint64_t cw = 3 * (uint64_t)nword, ncol = (uint64_t)wl + 1;
-		const uint64_t slice = std::max<uint64_t>(256, std::min<uint64_t>((T + 255) & ~255ULL, ((4ULL << 30) / (8 * cw * ncol)) & ~255ULL));
+		const uint64_t slice = hao_col_slice(c, T, 8 * cw * ncol);
 		HIP_TRY(G.path.reserve(cw * ncol * slice + 1)); HIP_TRY(G.rows.reserve(slice * cap + 1)); HIP_TRY(G.cnt.reserve(slice + 2)); HIP_TRY(G.loc.reserve(slice + 2));
 		const dim3 b_(256);
 		for (uint64_t lo = 0; lo < T; lo += slice) {
 			const uint64_t m = std::min<uint64_t>(slice, T - lo);
 			const dim3 g2((unsigned)((m + 255) / 256));
 			HIP_TRY(hipMemsetAsync(G.cnt.p + m, 0, 8, c->stream));
-			if (nword == 1) hipLaunchKernelGGL((hao_trace_grid_kernel<uint64_t>), g2, b_, 0, c->stream, R, ol, pairs, G.sel.p + lo, m, wl, thre, G.path.p, slice, G.rows.p, cap, G.cnt.p, ps16, ncig16);
-			else if (nword == 2) hipLaunchKernelGGL((hao_trace_grid_kernel<hao_u128>), g2, b_, 0, c->stream, R, ol, pairs, G.sel.p + lo, m, wl, thre, G.path.p, slice, G.rows.p, cap, G.cnt.p, ps16, ncig16);
-			else if (nword == 3) hipLaunchKernelGGL((hao_trace_grid_kernel<hao_wide<3> >), g2, b_, 0, c->stream, R, ol, pairs, G.sel.p + lo, m, wl, thre, G.path.p, slice, G.rows.p, cap, G.cnt.p, ps16, ncig16);
-			else hipLaunchKernelGGL((hao_trace_grid_kernel<hao_wide<4> >), g2, b_, 0, c->stream, R, ol, pairs, G.sel.p + lo, m, wl, thre, G.path.p, slice, G.rows.p, cap, G.cnt.p, ps16, ncig16);
+			hao_by_nword(nword, [&](auto w) { hipLaunchKernelGGL((hao_trace_grid_kernel<typename decltype(w)::type>), g2, b_, 0, c->stream, R, ol, pairs, G.sel.p + lo, m, wl, thre, G.path.p, slice, G.rows.p, cap, G.cnt.p, ps16, ncig16); });
 			HAO_CHECK_LAUNCH();
 			if (int rc = hao_excl_scan_u64(c, G.cnt.p, G.loc.p, m + 1)) return rc;
 			hipLaunchKernelGGL(hao_tg_compact_kernel, g2, b_, 0, c->stream, G.rows.p, cap, G.loc.p, m, G.off.p + lo, cig.p, (uint64_t)cig.cap); HAO_CHECK_LAUNCH();
@@ -195,10 +193,10 @@ int hao_al_rescue(hao_ctx *c, const hao_ref_io &io)
 	hipLaunchKernelGGL((hao_rs_gap_kernel<true>), go, b_, 0, c->stream, A, G.ctr.p, G.rbase.p, G.st.p, G.rec.p); HAO_CHECK_LAUNCH();
 	uint64_t rounds = 0;
 	if (na) {
-		// column scratch: 24 bytes per text column (t_len <= wl, + slot 0) and lane, in slices of the states whose columns fit ~4 GB; a slice runs its rounds to the end
+		// column scratch: 24 bytes per text column (t_len <= wl, + slot 0) and lane, in slices of the states whose columns fit the budget (hao_col_slice); a slice runs its rounds to the end
 		const hao_ed_reads R = hao_al_reads_of(c);
 		const uint64_t ncol = (uint64_t)wl + 1;
-		const uint64_t slice = std::max<uint64_t>(256, std::min<uint64_t>((na + 255) & ~255ULL, ((4ULL << 30) / (24 * ncol)) & ~255ULL));
+		const uint64_t slice = hao_col_slice(c, na, 24 * ncol);
 		HIP_TRY(G.path.reserve(3 * ncol * slice + 1));
 		for (uint64_t lo = 0; lo < na; lo += slice) {
 			const uint64_t m = std::min<uint64_t>(slice, na - lo);
@@ -225,7 +223,7 @@ int hao_al_rescue(hao_ctx *c, const hao_ref_io &io)
 	if (int rc = hao_peek(c, G.ctr.p + 5, 1, PK_RS_TOTAL)) return rc;
 	HIP_TRY(hipStreamSynchronize(c->stream));
 	c->rs_total = c->peeked(PK_RS_TOTAL); c->rs_rounds = rounds; c->rs_active = na; c->rs_slots = ns; c->rs_nw = n_wins;
-	if (G.path.cap > (1ULL << 27)) G.path.release();      // (more than 1 GB of column scratch is not kept between calls)
+	hao_release_above(G.path, HAO_SCRATCH_KEEP);
 	return HAO_OK;
 }
 
@@ -262,13 +260,11 @@ int hao_al_wlist(hao_ctx *c, const hao_ref_io &io)
 	const uint32_t cap = 2 * 31 + 3 + (2 * wl + 62) / 0x3fff;      // (hao_tg_bound for thre <= 31 and a window of wl bases)
 	if (M) {
 		// text order: the records that need a sweep to the front, by (query read, grid window); stable, so overlaps of one window keep their order
-		size_t tb = 0;
-		HIP_TRY(rocprim::radix_sort_pairs(nullptr, tb, G.key.p, G.key2.p, G.idx.p, G.sel.p, N, 0, wbits + rbits, c->stream)); HIP_TRY(hao_tmp(c, tb));
-		HIP_TRY(rocprim::radix_sort_pairs(c->d_tmp.p, tb, G.key.p, G.key2.p, G.idx.p, G.sel.p, N, 0, wbits + rbits, c->stream));
-		// column scratch: 24 bytes per text column (t_len <= wl, + slot 0) and lane, in slices whose columns fit ~4 GB; two rows of `cap` entries per swept record
+		if (int rc = hao_sort_pairs(c, G.key.p, G.key2.p, G.idx.p, G.sel.p, N, wbits + rbits)) return rc;
+		// column scratch: 24 bytes per text column (t_len <= wl, + slot 0) and lane, in slices whose columns fit the budget (hao_col_slice); two rows of `cap` entries per swept record
 		const hao_ed_reads R = hao_al_reads_of(c);
 		const uint64_t ncol = (uint64_t)wl + 1;
-		const uint64_t slice = std::max<uint64_t>(256, std::min<uint64_t>((M + 255) & ~255ULL, ((4ULL << 30) / (24 * ncol)) & ~255ULL));
+		const uint64_t slice = hao_col_slice(c, M, 24 * ncol);
 		HIP_TRY(G.path.reserve(3 * ncol * slice + 1)); HIP_TRY(G.rows.reserve(M * 2 * (uint64_t)cap + 1));
 		for (uint64_t lo = 0; lo < M; lo += slice) {
 			const uint64_t m = std::min<uint64_t>(slice, M - lo);
@@ -282,8 +278,7 @@ int hao_al_wlist(hao_ctx *c, const hao_ref_io &io)
 	if (int rc = hao_peek(c, o_cigoff.p + N, 1, PK_WL_NCIG)) return rc;
 	if (int rc = hao_peek(c, G.ctr.p, 6, PK_WL_CTR)) return rc;
 	HIP_TRY(hipStreamSynchronize(c->stream));
-	if (G.path.cap > (1ULL << 27)) G.path.release();      // (more than 1 GB of column scratch is not kept between calls)
-	if (G.rows.cap > (1ULL << 29)) G.rows.release();      // (nor more than 1 GB of rows)
+	hao_release_above(G.path, HAO_SCRATCH_KEEP); hao_release_above(G.rows, HAO_SCRATCH_KEEP);
 	if (c->peeked(PK_WL_NCIG) > bound) { hao_set_err(c, "window lists: more cigar entries than their bound"); return HAO_EUNSUPP; }      // (hao_tg_bound rules it out)
 	if (c->peeked(PK_WL_CTR, 4) || c->peeked(PK_WL_CTR, 5)) {      // (a broken invariant is an error, not an untraced window)
 		hao_set_err(c, "window lists: " + std::to_string(c->peeked(PK_WL_CTR, 5)) + " records whose task could not be rebuilt from the rescue records, " + std::to_string(c->peeked(PK_WL_CTR, 4)) + " whose traced sweep lost the distance-only alignment or overran its row");
@@ -293,80 +288,91 @@ int hao_al_wlist(hao_ctx *c, const hao_ref_io &io)
 	return HAO_OK;
 }
 
+// ---- the host-fed calls: prologue, check, run, copy out ----
+// prologue (`who`: the entry point, for its messages; args_ok: its argument check): the view or today's refusal; what the grid calls left in the shared task /
+// result scratch is gone (hao_window_trace_grid's results follow the same rule).  The caller returns at once when this fails or the call is empty.
+static int hao_al_host_fed(hao_ctx *c, const char *who, bool args_ok, uint64_t n_tasks, hao_read_view *V)
+{
+	if (!args_ok) return HAO_EINVAL;
+	if (int rc = hao_view_refresh(c)) return rc;
+	if (!hao_reads_view(c, V)) { hao_set_err(c, std::string(who) + " needs the bases of both reads: single-device mode only"); return HAO_EUNSUPP; }
+	c->win.on_host_fed();
+	if (n_tasks >= (1ULL << 32)) { hao_set_err(c, std::string(who) + ": more than 2^32 tasks in one call"); return HAO_EUNSUPP; }
+	return HAO_OK;
+}
+// the range checks (the reference indexes its strings unchecked; a device kernel must not): every task inside its reads, thre <= max_thre, both lengths <= max_len,
+// and the rules of the call's kind -
+//   HAO_AL_RULE_ED, the distance-only calls: abs_diag <= 2 thre, and p_len - t_len + abs_diag inside the band's words - the final scan would read VP / VN bits beyond
+//     them (the reference then indexes the neighbouring vectors of its bit_extz_t)
+//   HAO_AL_RULE_SEMI, the traced calls in semi-global mode: the band covers the pattern (0 <= p_len - t_len + abs_diag <= 2 thre, t_len > abs_diag, abs_diag <= 2 thre)
+// *words (may be null): bit (nword - 1) = some band of at most four words needs nword 64-bit words (the reference's cal_exz_infi picks nword =
+// ceil((2 thre + 1) / 64), Correct.cpp:14508-14565); *tn_max (may be null): the longest text, 1 at the least
+// (always inlined, and the refusal out of line: a distance-only call of 400 000 tasks lasts 2 ms, and this loop with the limits and rules as run-time values costs 0.3 ms of it)
+enum { HAO_AL_RULE_ED = 1, HAO_AL_RULE_SEMI = 2 };
+__attribute__((noinline)) static int hao_al_refuse(hao_ctx *c, const char *who, uint64_t i, const char *why) { hao_set_err(c, std::string(who) + ": task " + std::to_string(i) + why); return HAO_EINVAL; }
+__attribute__((always_inline)) static inline int hao_al_check_tasks(hao_ctx *c, const char *who, const hao_read_view &V, const hao_ed_task_t *tasks, uint64_t n, uint32_t max_thre, uint32_t max_len, int rules, uint32_t *words, uint64_t *tn_max)
+{
+	uint32_t w = 0; uint64_t tn = 1;
+	for (uint64_t i = 0; i < n; ++i) {
+		const hao_ed_task_t &t = tasks[i];
+		if (t.p_rid >= V.n || t.t_rid >= V.n || (uint64_t)t.p_pos + t.p_len > V.h_len[t.p_rid] || (uint64_t)t.t_pos + t.t_len > V.h_len[t.t_rid] ||
+			t.thre > max_thre || t.p_len > max_len || t.t_len > max_len || ((rules & HAO_AL_RULE_ED) && t.abs_diag > 2 * t.thre)) return hao_al_refuse(c, who, i, " out of range");
+		const uint32_t nw = hao_al_nword(t.thre); const int64_t ai = (int64_t)t.p_len - (int64_t)t.t_len + (int64_t)t.abs_diag;
+		if ((rules & HAO_AL_RULE_ED) && nw > 1 && ai > 64 * (int64_t)nw) return hao_al_refuse(c, who, i, ": p_len - t_len + abs_diag beyond the band's words");
+		if ((rules & HAO_AL_RULE_SEMI) && (ai < 0 || ai > 2 * (int64_t)t.thre || t.t_len <= t.abs_diag || t.abs_diag > 2 * t.thre)) return hao_al_refuse(c, who, i, ": the band does not cover the pattern");
+		if (nw <= 4) w |= 1u << (nw - 1);
+		tn = std::max<uint64_t>(tn, t.t_len);
+	}
+	if (words) *words = w;
+	if (tn_max) *tn_max = tn;
+	return HAO_OK;
+}
+// the traced calls' result buffers: begin reserves them and zeroes the flags and the cigar rows (tasks without an alignment get no cigar: their rows read as zeros,
+// not as an earlier call's entries); end copies results and cigars out and keeps no more than HAO_SCRATCH_KEEP of column scratch or of cigar rows
+static int hao_al_traced_begin(hao_ctx *c, uint64_t n, uint32_t cigar_cap)
+{
+	HIP_TRY(c->al_tres.reserve(n)); HIP_TRY(c->al_want.reserve(n)); HIP_TRY(c->al_cig.reserve(n * (uint64_t)cigar_cap + 1));
+	HIP_TRY(hipMemsetAsync(c->al_want.p, 0, n, c->stream));
+	if (cigar_cap) HIP_TRY(hipMemsetAsync(c->al_cig.p, 0, n * (uint64_t)cigar_cap * 2, c->stream));
+	return HAO_OK;
+}
+static int hao_al_traced_end(hao_ctx *c, uint64_t n, uint32_t cigar_cap, hao_trace_result_t *out, uint16_t *cigars)
+{
+	HIP_TRY(hipMemcpyAsync(out, c->al_tres.p, n * sizeof(hao_trace_result_t), hipMemcpyDeviceToHost, c->stream));
+	if (cigar_cap) HIP_TRY(hipMemcpyAsync(cigars, c->al_cig.p, n * (uint64_t)cigar_cap * 2, hipMemcpyDeviceToHost, c->stream));
+	HIP_TRY(hipStreamSynchronize(c->stream));
+	hao_release_above(c->al_path, HAO_SCRATCH_KEEP); hao_release_above(c->al_cig, HAO_SCRATCH_KEEP);
+	return HAO_OK;
+}
+
 extern "C" {
 
 int hao_window_ed_batch(hao_ctx *c, const hao_ed_task_t *tasks, uint64_t n_tasks, hao_ed_result_t *out)
 {
-	if (!c || (!tasks && n_tasks) || (!out && n_tasks)) return HAO_EINVAL;
-	if (int rc = hao_view_refresh(c)) return rc;
-	HAO_STAGE_VIEW(c, V, "hao_window_ed_batch needs the bases of both reads");
-	c->win.on_host_fed();      // (the task / result scratch is shared with the grid calls: what they left is gone, and hao_window_trace_grid's results follow the same rule)
-	if (n_tasks == 0) return HAO_OK;
-	if (n_tasks >= (1ULL << 32)) { hao_set_err(c, "hao_window_ed_batch: more than 2^32 tasks in one call"); return HAO_EUNSUPP; }
-	uint32_t words = 0;      // bit (nword - 1): some band needs nword 64-bit words (the reference's cal_exz_infi picks nword = ceil((2 thre + 1) / 64), Correct.cpp:14508-14565)
-	for (uint64_t i = 0; i < n_tasks; ++i) {      // the reference indexes its strings unchecked; a device kernel must not
-		const hao_ed_task_t &t = tasks[i];
-		if (t.p_rid >= V.n || t.t_rid >= V.n || (uint64_t)t.p_pos + t.p_len > V.h_len[t.p_rid] || (uint64_t)t.t_pos + t.t_len > V.h_len[t.t_rid] ||
-			t.thre > HAO_ED_MAX_THRE || t.abs_diag > 2 * t.thre) { hao_set_err(c, "hao_window_ed_batch: task " + std::to_string(i) + " out of range"); return HAO_EINVAL; }
-		const uint32_t nw = hao_al_nword(t.thre);
-		if (nw > 1 && (int64_t)t.p_len - (int64_t)t.t_len + (int64_t)t.abs_diag > 64 * (int64_t)nw) {      // the final scan would read VP / VN bits beyond the band's words (the reference then indexes the neighbouring vectors of its bit_extz_t)
-			hao_set_err(c, "hao_window_ed_batch: task " + std::to_string(i) + ": p_len - t_len + abs_diag beyond the band's words"); return HAO_EINVAL; }
-		words |= 1u << (nw - 1);
-	}
+	hao_read_view V; uint32_t words = 0;
+	if (int rc = hao_al_host_fed(c, "hao_window_ed_batch", c && (tasks || !n_tasks) && (out || !n_tasks), n_tasks, &V); rc || !n_tasks) return rc;
+	if (int rc = hao_al_check_tasks(c, "hao_window_ed_batch", V, tasks, n_tasks, HAO_ED_MAX_THRE, UINT32_MAX, HAO_AL_RULE_ED, &words, nullptr)) return rc;
 	HIP_TRY(hipSetDevice(c->device));
 	if (int rc = hao_al_upload_sorted(c, tasks, n_tasks)) return rc;
 	HIP_TRY(c->al_res.reserve(n_tasks));
-	DevBuf<hao_ed_task_t> &dt = c->al_task; DevBuf<uint32_t> &order = c->al_order; DevBuf<hao_ed_result_t> &dr = c->al_res;
-	const hao_ed_reads R = hao_al_reads_of(c);
-	const dim3 g_((unsigned)((n_tasks + 255) / 256)), b_(256);
-	if (words & 1u) { hipLaunchKernelGGL((hao_al_kernel<uint64_t, HAO_AL_ED, false>), g_, b_, 0, c->stream, R, dt.p, order.p, n_tasks, (uint64_t*)nullptr, (uint64_t)0, dr.p, (hao_trace_result_t*)nullptr, (uint8_t*)nullptr, (uint16_t*)nullptr, 0u); HAO_CHECK_LAUNCH(); }
-	if (words & 2u) { hipLaunchKernelGGL((hao_al_kernel<hao_u128, HAO_AL_ED, false>), g_, b_, 0, c->stream, R, dt.p, order.p, n_tasks, (uint64_t*)nullptr, (uint64_t)0, dr.p, (hao_trace_result_t*)nullptr, (uint8_t*)nullptr, (uint16_t*)nullptr, 0u); HAO_CHECK_LAUNCH(); }
-	if (words & 4u) { hipLaunchKernelGGL((hao_al_kernel<hao_wide<3>, HAO_AL_ED, false>), g_, b_, 0, c->stream, R, dt.p, order.p, n_tasks, (uint64_t*)nullptr, (uint64_t)0, dr.p, (hao_trace_result_t*)nullptr, (uint8_t*)nullptr, (uint16_t*)nullptr, 0u); HAO_CHECK_LAUNCH(); }
-	if (words & 8u) { hipLaunchKernelGGL((hao_al_kernel<hao_wide<4>, HAO_AL_ED, false>), g_, b_, 0, c->stream, R, dt.p, order.p, n_tasks, (uint64_t*)nullptr, (uint64_t)0, dr.p, (hao_trace_result_t*)nullptr, (uint8_t*)nullptr, (uint16_t*)nullptr, 0u); HAO_CHECK_LAUNCH(); }
-	HIP_TRY(hipMemcpyAsync(out, dr.p, n_tasks * sizeof(hao_ed_result_t), hipMemcpyDeviceToHost, c->stream));
+	if (int rc = hao_al_sweep<HAO_AL_ED, false>(c, hao_al_reads_of(c), c->al_task.p, c->al_order.p, n_tasks, words, nullptr, 0, c->al_res.p, nullptr, nullptr, nullptr, 0u)) return rc;
+	HIP_TRY(hipMemcpyAsync(out, c->al_res.p, n_tasks * sizeof(hao_ed_result_t), hipMemcpyDeviceToHost, c->stream));
 	HIP_TRY(hipStreamSynchronize(c->stream));
 	return HAO_OK;
 }
 
 int hao_window_trace_batch(hao_ctx *c, int mode, const hao_ed_task_t *tasks, uint64_t n_tasks, hao_trace_result_t *out, uint16_t *cigars, uint32_t cigar_cap)
 {
-	if (!c || (mode < HAO_ALIGN_GLOBAL || mode > HAO_ALIGN_SEMI) || (!tasks && n_tasks) || (!out && n_tasks) || (!cigars && n_tasks && cigar_cap)) return HAO_EINVAL;
-	if (int rc = hao_view_refresh(c)) return rc;
-	HAO_STAGE_VIEW(c, V, "hao_window_trace_batch needs the bases of both reads");
-	c->win.on_host_fed();
-	if (n_tasks == 0) return HAO_OK;
-	if (n_tasks >= (1ULL << 32)) { hao_set_err(c, "hao_window_trace_batch: more than 2^32 tasks in one call"); return HAO_EUNSUPP; }
-	uint64_t tn_max = 1; uint32_t words = 0;      // bit (nword - 1): some band needs nword 64-bit words
-	for (uint64_t i = 0; i < n_tasks; ++i) {      // the reference indexes its strings unchecked; a device kernel must not
-		const hao_ed_task_t &t = tasks[i];
-		if (t.p_rid >= V.n || t.t_rid >= V.n || (uint64_t)t.p_pos + t.p_len > V.h_len[t.p_rid] || (uint64_t)t.t_pos + t.t_len > V.h_len[t.t_rid] ||
-			t.thre > HAO_ED_MAX_THRE) { hao_set_err(c, "hao_window_trace_batch: task " + std::to_string(i) + " out of range"); return HAO_EINVAL; }
-		words |= 1u << (hao_al_nword(t.thre) - 1);
-		if (mode == HAO_ALIGN_SEMI) {
-			const int64_t ai = (int64_t)t.p_len - (int64_t)t.t_len + (int64_t)t.abs_diag;
-			if (ai < 0 || ai > 2 * (int64_t)t.thre || t.t_len <= t.abs_diag || t.abs_diag > 2 * t.thre) { hao_set_err(c, "hao_window_trace_batch: task " + std::to_string(i) + ": the band does not cover the pattern"); return HAO_EINVAL; }
-		}
-		if (t.t_len > tn_max) tn_max = t.t_len;
-	}
+	hao_read_view V; uint32_t words = 0; uint64_t tn_max = 1;
+	if (int rc = hao_al_host_fed(c, "hao_window_trace_batch", c && mode >= HAO_ALIGN_GLOBAL && mode <= HAO_ALIGN_SEMI && (tasks || !n_tasks) && (out || !n_tasks) && (cigars || !n_tasks || !cigar_cap), n_tasks, &V); rc || !n_tasks) return rc;
+	// (no rule on abs_diag outside semi-global mode: the three other modes take any diagonal, as in hao_window_trace_long)
+	if (int rc = hao_al_check_tasks(c, "hao_window_trace_batch", V, tasks, n_tasks, HAO_ED_MAX_THRE, UINT32_MAX, mode == HAO_ALIGN_SEMI ? HAO_AL_RULE_SEMI : 0, &words, &tn_max)) return rc;
 	HIP_TRY(hipSetDevice(c->device));
 	if (int rc = hao_al_upload_sorted(c, tasks, n_tasks)) return rc;
-	DevBuf<hao_ed_task_t> &dt = c->al_task; DevBuf<uint32_t> &order = c->al_order; DevBuf<hao_trace_result_t> &dr = c->al_tres; DevBuf<uint16_t> &dc = c->al_cig; DevBuf<uint8_t> &want = c->al_want;
-	HIP_TRY(dr.reserve(n_tasks)); HIP_TRY(want.reserve(n_tasks)); HIP_TRY(dc.reserve(n_tasks * (uint64_t)cigar_cap + 1));
-	HIP_TRY(hipMemsetAsync(want.p, 0, n_tasks, c->stream));
-	if (cigar_cap) HIP_TRY(hipMemsetAsync(dc.p, 0, n_tasks * (uint64_t)cigar_cap * 2, c->stream));      // tasks without an alignment get no cigar: their rows read as zeros, not as an earlier call's entries
+	if (int rc = hao_al_traced_begin(c, n_tasks, cigar_cap)) return rc;
 	const hao_ed_reads R = hao_al_reads_of(c);
-	int rc;
-	if (mode == HAO_ALIGN_EXT_FWD) rc = hao_al_trace_run<HAO_AL_EXT_FWD>(c, R, dt.p, order.p, n_tasks, words, tn_max, dr.p, want.p, dc.p, cigar_cap);
-	else if (mode == HAO_ALIGN_EXT_BWD) rc = hao_al_trace_run<HAO_AL_EXT_BWD>(c, R, dt.p, order.p, n_tasks, words, tn_max, dr.p, want.p, dc.p, cigar_cap);
-	else if (mode == HAO_ALIGN_SEMI) rc = hao_al_trace_run<HAO_AL_SEMI>(c, R, dt.p, order.p, n_tasks, words, tn_max, dr.p, want.p, dc.p, cigar_cap);
-	else rc = hao_al_trace_run<HAO_AL_GLOBAL>(c, R, dt.p, order.p, n_tasks, words, tn_max, dr.p, want.p, dc.p, cigar_cap);
-	if (rc) return rc;
-	HIP_TRY(hipMemcpyAsync(out, dr.p, n_tasks * sizeof(hao_trace_result_t), hipMemcpyDeviceToHost, c->stream));
-	if (cigar_cap) HIP_TRY(hipMemcpyAsync(cigars, dc.p, n_tasks * (uint64_t)cigar_cap * 2, hipMemcpyDeviceToHost, c->stream));
-	HIP_TRY(hipStreamSynchronize(c->stream));
-	if (c->al_path.cap > (1ULL << 27)) c->al_path.release();      // (more than 1 GB of column scratch is not kept between calls)
-	if (c->al_cig.cap > (1ULL << 29)) c->al_cig.release();        // (nor more than 1 GB of cigar rows)
-	return HAO_OK;
+	if (int rc = hao_by_mode(mode, [&](auto M) { return hao_al_trace_run<decltype(M)::value>(c, R, c->al_task.p, c->al_order.p, n_tasks, words, tn_max, c->al_tres.p, c->al_want.p, c->al_cig.p, cigar_cap); })) return rc;
+	return hao_al_traced_end(c, n_tasks, cigar_cap, out, cigars);
 }
 
 }
@@ -401,6 +407,17 @@ template<int MODE, bool TRACE> static int hao_alc_launch(hao_ctx *c, const hao_e
 	HAO_CHECK_LAUNCH();
 	return HAO_OK;
 }
+// the first sweep of the cooperative kernel over classes 1 - 4 (lo[k] .. lo[k + 1]: class k's stretch of `order`): keeps nothing, marks in want[] the pairs that end
+// within their threshold; after(k, m) follows the launch of class k's m pairs
+template<int MODE, typename F> static int hao_alc_first(hao_ctx *c, const hao_ed_reads &R, const uint32_t *order, const uint64_t lo[6], hao_trace_result_t *dr, uint8_t *want, F after)
+{
+	for (int k = 1; k <= 4; ++k) if (lo[k + 1] > lo[k]) {
+		const uint64_t m = lo[k + 1] - lo[k];
+		if (int rc = hao_alc_launch<MODE, false>(c, R, k, order + lo[k], m, nullptr, nullptr, nullptr, dr, want, nullptr, 0u)) return rc;
+		if (int rc = after(k, m)) return rc;
+	}
+	return HAO_OK;
+}
 // the traced modes over the plan's classes: class 0 through hao_al_trace_run, the others in two sweeps of the cooperative kernel - the first keeps nothing and marks
 // the pairs that end within their threshold, the second keeps three words per band word and column for those, in slices whose columns fit c->sw.al_slice bytes
 template<int MODE> static int hao_alc_trace_run(hao_ctx *c, const hao_ed_reads &R, const hao_ed_task_t *tasks, const hao_alc_plan &P, const std::vector<uint32_t> &ord, uint64_t n,
@@ -409,8 +426,8 @@ template<int MODE> static int hao_alc_trace_run(hao_ctx *c, const hao_ed_reads &
 	const uint32_t *order = c->al_order.p;
 	if (P.lo[1]) { if (int rc = hao_al_trace_run<MODE>(c, R, c->al_task.p, order, P.lo[1], P.words, P.tn_max0, dr, want, dc, cap)) return rc; }
 	if (P.lo[5] == P.lo[1]) return HAO_OK;
-	for (int k = 1; k <= 4; ++k) if (P.lo[k + 1] > P.lo[k]) {
-		if (int rc = hao_alc_launch<MODE, false>(c, R, k, order + P.lo[k], P.lo[k + 1] - P.lo[k], nullptr, nullptr, nullptr, dr, want, nullptr, 0u)) return rc; }
+	if (int rc = hao_alc_first<MODE>(c, R, order, P.lo, dr, want, [](int, uint64_t) { return (int)HAO_OK; })) return rc;
+	// (selection on the host and exact per-pair blocks; the ladder's hao_ld_first / hao_ld_second select on the device and pack class-uniform blocks - merging them is a change of its own)
 	std::vector<uint8_t> hw(n);
 	HIP_TRY(hipMemcpyAsync(hw.data(), want, n, hipMemcpyDeviceToHost, c->stream));
 	HIP_TRY(hipStreamSynchronize(c->stream));
@@ -435,43 +452,22 @@ template<int MODE> static int hao_alc_trace_run(hao_ctx *c, const hao_ed_reads &
 	HIP_TRY(hipStreamSynchronize(c->stream));      // (sel / off leave scope)
 	return HAO_OK;
 }
-// the range checks both long calls share (the reference indexes its strings unchecked; a device kernel must not)
-static bool hao_alc_in_range(const hao_read_view &V, const hao_ed_task_t &t)
-{
-	return t.p_rid < V.n && t.t_rid < V.n && (uint64_t)t.p_pos + t.p_len <= V.h_len[t.p_rid] && (uint64_t)t.t_pos + t.t_len <= V.h_len[t.t_rid] &&
-		t.thre <= HAO_ED_LONG_MAX_THRE && t.p_len <= HAO_ED_LONG_MAX_LEN && t.t_len <= HAO_ED_LONG_MAX_LEN;
-}
 
 extern "C" {
 
 int hao_window_ed_long(hao_ctx *c, const hao_ed_task_t *tasks, uint64_t n_tasks, hao_ed_result_t *out)
 {
-	if (!c || (!tasks && n_tasks) || (!out && n_tasks)) return HAO_EINVAL;
-	if (int rc = hao_view_refresh(c)) return rc;
-	HAO_STAGE_VIEW(c, V, "hao_window_ed_long needs the bases of both reads");
-	c->win.on_host_fed();
-	if (n_tasks == 0) return HAO_OK;
-	if (n_tasks >= (1ULL << 32)) { hao_set_err(c, "hao_window_ed_long: more than 2^32 tasks in one call"); return HAO_EUNSUPP; }
-	for (uint64_t i = 0; i < n_tasks; ++i) {
-		const hao_ed_task_t &t = tasks[i];
-		if (!hao_alc_in_range(V, t) || t.abs_diag > 2 * t.thre) { hao_set_err(c, "hao_window_ed_long: task " + std::to_string(i) + " out of range"); return HAO_EINVAL; }
-		const uint32_t nw = hao_al_nword(t.thre);
-		if (nw > 1 && (int64_t)t.p_len - (int64_t)t.t_len + (int64_t)t.abs_diag > 64 * (int64_t)nw) {      // (hao_window_ed_batch's rule: the final scan stays inside the band's words)
-			hao_set_err(c, "hao_window_ed_long: task " + std::to_string(i) + ": p_len - t_len + abs_diag beyond the band's words"); return HAO_EINVAL; }
-	}
+	hao_read_view V;
+	if (int rc = hao_al_host_fed(c, "hao_window_ed_long", c && (tasks || !n_tasks) && (out || !n_tasks), n_tasks, &V); rc || !n_tasks) return rc;
+	// (hao_window_ed_batch's rules; only the limits differ)
+	if (int rc = hao_al_check_tasks(c, "hao_window_ed_long", V, tasks, n_tasks, HAO_ED_LONG_MAX_THRE, HAO_ED_LONG_MAX_LEN, HAO_AL_RULE_ED, nullptr, nullptr)) return rc;
 	HIP_TRY(hipSetDevice(c->device));
 	hao_alc_plan P; std::vector<uint32_t> ord;
 	if (int rc = hao_alc_upload(c, tasks, n_tasks, P, ord)) return rc;
 	HIP_TRY(c->al_res.reserve(n_tasks));
 	hao_ed_task_t *dt = c->al_task.p; uint32_t *order = c->al_order.p; hao_ed_result_t *dr = c->al_res.p;
 	const hao_ed_reads R = hao_al_reads_of(c);
-	if (P.lo[1]) {
-		const dim3 g_((unsigned)((P.lo[1] + 255) / 256)), b_(256); const uint64_t n0 = P.lo[1];
-		if (P.words & 1u) { hipLaunchKernelGGL((hao_al_kernel<uint64_t, HAO_AL_ED, false>), g_, b_, 0, c->stream, R, dt, order, n0, (uint64_t*)nullptr, (uint64_t)0, dr, (hao_trace_result_t*)nullptr, (uint8_t*)nullptr, (uint16_t*)nullptr, 0u); HAO_CHECK_LAUNCH(); }
-		if (P.words & 2u) { hipLaunchKernelGGL((hao_al_kernel<hao_u128, HAO_AL_ED, false>), g_, b_, 0, c->stream, R, dt, order, n0, (uint64_t*)nullptr, (uint64_t)0, dr, (hao_trace_result_t*)nullptr, (uint8_t*)nullptr, (uint16_t*)nullptr, 0u); HAO_CHECK_LAUNCH(); }
-		if (P.words & 4u) { hipLaunchKernelGGL((hao_al_kernel<hao_wide<3>, HAO_AL_ED, false>), g_, b_, 0, c->stream, R, dt, order, n0, (uint64_t*)nullptr, (uint64_t)0, dr, (hao_trace_result_t*)nullptr, (uint8_t*)nullptr, (uint16_t*)nullptr, 0u); HAO_CHECK_LAUNCH(); }
-		if (P.words & 8u) { hipLaunchKernelGGL((hao_al_kernel<hao_wide<4>, HAO_AL_ED, false>), g_, b_, 0, c->stream, R, dt, order, n0, (uint64_t*)nullptr, (uint64_t)0, dr, (hao_trace_result_t*)nullptr, (uint8_t*)nullptr, (uint16_t*)nullptr, 0u); HAO_CHECK_LAUNCH(); }
-	}
+	if (P.lo[1]) { if (int rc = hao_al_sweep<HAO_AL_ED, false>(c, R, dt, order, P.lo[1], P.words, nullptr, 0, dr, nullptr, nullptr, nullptr, 0u)) return rc; }
 	for (int k = 1; k <= 4; ++k) if (P.lo[k + 1] > P.lo[k]) {
 		if (int rc = hao_alc_launch<HAO_AL_ED, false>(c, R, k, order + P.lo[k], P.lo[k + 1] - P.lo[k], nullptr, nullptr, dr, nullptr, nullptr, nullptr, 0u)) return rc; }
 	HIP_TRY(hipMemcpyAsync(out, dr, n_tasks * sizeof(hao_ed_result_t), hipMemcpyDeviceToHost, c->stream));
@@ -481,40 +477,17 @@ int hao_window_ed_long(hao_ctx *c, const hao_ed_task_t *tasks, uint64_t n_tasks,
 
 int hao_window_trace_long(hao_ctx *c, int mode, const hao_ed_task_t *tasks, uint64_t n_tasks, hao_trace_result_t *out, uint16_t *cigars, uint32_t cigar_cap)
 {
-	if (!c || (mode < HAO_ALIGN_GLOBAL || mode > HAO_ALIGN_SEMI) || (!tasks && n_tasks) || (!out && n_tasks) || (!cigars && n_tasks && cigar_cap)) return HAO_EINVAL;
-	if (int rc = hao_view_refresh(c)) return rc;
-	HAO_STAGE_VIEW(c, V, "hao_window_trace_long needs the bases of both reads");
-	c->win.on_host_fed();
-	if (n_tasks == 0) return HAO_OK;
-	if (n_tasks >= (1ULL << 32)) { hao_set_err(c, "hao_window_trace_long: more than 2^32 tasks in one call"); return HAO_EUNSUPP; }
-	for (uint64_t i = 0; i < n_tasks; ++i) {
-		const hao_ed_task_t &t = tasks[i];
-		if (!hao_alc_in_range(V, t)) { hao_set_err(c, "hao_window_trace_long: task " + std::to_string(i) + " out of range"); return HAO_EINVAL; }
-		if (mode == HAO_ALIGN_SEMI) {
-			const int64_t ai = (int64_t)t.p_len - (int64_t)t.t_len + (int64_t)t.abs_diag;
-			if (ai < 0 || ai > 2 * (int64_t)t.thre || t.t_len <= t.abs_diag || t.abs_diag > 2 * t.thre) { hao_set_err(c, "hao_window_trace_long: task " + std::to_string(i) + ": the band does not cover the pattern"); return HAO_EINVAL; }
-		}
-	}
+	hao_read_view V;
+	if (int rc = hao_al_host_fed(c, "hao_window_trace_long", c && mode >= HAO_ALIGN_GLOBAL && mode <= HAO_ALIGN_SEMI && (tasks || !n_tasks) && (out || !n_tasks) && (cigars || !n_tasks || !cigar_cap), n_tasks, &V); rc || !n_tasks) return rc;
+	// (hao_window_trace_batch's rules; only the limits differ)
+	if (int rc = hao_al_check_tasks(c, "hao_window_trace_long", V, tasks, n_tasks, HAO_ED_LONG_MAX_THRE, HAO_ED_LONG_MAX_LEN, mode == HAO_ALIGN_SEMI ? HAO_AL_RULE_SEMI : 0, nullptr, nullptr)) return rc;
 	HIP_TRY(hipSetDevice(c->device));
 	hao_alc_plan P; std::vector<uint32_t> ord;
 	if (int rc = hao_alc_upload(c, tasks, n_tasks, P, ord)) return rc;
-	DevBuf<hao_trace_result_t> &dr = c->al_tres; DevBuf<uint16_t> &dc = c->al_cig; DevBuf<uint8_t> &want = c->al_want;
-	HIP_TRY(dr.reserve(n_tasks)); HIP_TRY(want.reserve(n_tasks)); HIP_TRY(dc.reserve(n_tasks * (uint64_t)cigar_cap + 1));
-	HIP_TRY(hipMemsetAsync(want.p, 0, n_tasks, c->stream));
-	if (cigar_cap) HIP_TRY(hipMemsetAsync(dc.p, 0, n_tasks * (uint64_t)cigar_cap * 2, c->stream));      // (tasks without an alignment: rows of zeros)
+	if (int rc = hao_al_traced_begin(c, n_tasks, cigar_cap)) return rc;
 	const hao_ed_reads R = hao_al_reads_of(c);
-	int rc;
-	if (mode == HAO_ALIGN_EXT_FWD) rc = hao_alc_trace_run<HAO_AL_EXT_FWD>(c, R, tasks, P, ord, n_tasks, dr.p, want.p, dc.p, cigar_cap);
-	else if (mode == HAO_ALIGN_EXT_BWD) rc = hao_alc_trace_run<HAO_AL_EXT_BWD>(c, R, tasks, P, ord, n_tasks, dr.p, want.p, dc.p, cigar_cap);
-	else if (mode == HAO_ALIGN_SEMI) rc = hao_alc_trace_run<HAO_AL_SEMI>(c, R, tasks, P, ord, n_tasks, dr.p, want.p, dc.p, cigar_cap);
-	else rc = hao_alc_trace_run<HAO_AL_GLOBAL>(c, R, tasks, P, ord, n_tasks, dr.p, want.p, dc.p, cigar_cap);
-	if (rc) return rc;
-	HIP_TRY(hipMemcpyAsync(out, dr.p, n_tasks * sizeof(hao_trace_result_t), hipMemcpyDeviceToHost, c->stream));
-	if (cigar_cap) HIP_TRY(hipMemcpyAsync(cigars, dc.p, n_tasks * (uint64_t)cigar_cap * 2, hipMemcpyDeviceToHost, c->stream));
-	HIP_TRY(hipStreamSynchronize(c->stream));
-	if (c->al_path.cap > (1ULL << 27)) c->al_path.release();      // (more than 1 GB of column scratch is not kept between calls)
-	if (c->al_cig.cap > (1ULL << 29)) c->al_cig.release();        // (nor more than 1 GB of cigar rows)
-	return HAO_OK;
+	if (int rc = hao_by_mode(mode, [&](auto M) { return hao_alc_trace_run<decltype(M)::value>(c, R, tasks, P, ord, n_tasks, c->al_tres.p, c->al_want.p, c->al_cig.p, cigar_cap); })) return rc;
+	return hao_al_traced_end(c, n_tasks, cigar_cap, out, cigars);
 }
 
 }
@@ -526,14 +499,8 @@ template<int MODE> static int hao_ld_first(hao_ctx *c, const hao_ed_reads &R, in
 {
 	hao_ctx::Ladder &G = c->ld; const uint32_t *order = c->al_order.p;
 	if (lo[1] > lo[0]) { if (int rc = hao_al_trace_run<MODE>(c, R, c->al_task.p, order + lo[0], lo[1] - lo[0], words, tn_max0, dr, want, dc, cap)) return rc; }
-	for (int k = 1; k <= 4; ++k) if (lo[k + 1] > lo[k]) {
-		const uint64_t m = lo[k + 1] - lo[k];
-		if (int rc = hao_alc_launch<MODE, false>(c, R, k, order + lo[k], m, nullptr, nullptr, nullptr, dr, want, nullptr, 0u)) return rc;
-		size_t tb = 0;
-		HIP_TRY(rocprim::select(nullptr, tb, order + lo[k], G.sel.p + lo[k], G.selcnt.p + mode * 4 + (k - 1), m, hao_al_flagged{want}, c->stream)); HIP_TRY(hao_tmp(c, tb));
-		HIP_TRY(rocprim::select(c->d_tmp.p, tb, order + lo[k], G.sel.p + lo[k], G.selcnt.p + mode * 4 + (k - 1), m, hao_al_flagged{want}, c->stream));
-	}
-	return HAO_OK;
+	// (selection on the device and class-uniform blocks; hao_alc_trace_run selects on the host and packs exact per-pair blocks - merging them is a change of its own)
+	return hao_alc_first<MODE>(c, R, order, lo, dr, want, [&](int k, uint64_t m) { return hao_select(c, order + lo[k], hao_al_flagged{want}, G.sel.p + lo[k], G.selcnt.p + mode * 4 + (k - 1), m); });
 }
 // the second sweep of class k's n_sel selected pairs (sel: their slots), every pair with a column block of pw words, in slices that fit the column budget
 template<int MODE> static int hao_ld_second(hao_ctx *c, const hao_ed_reads &R, int k, const uint32_t *sel, uint64_t n_sel, uint64_t pw, hao_trace_result_t *dr, uint16_t *dc, uint32_t cap)
@@ -573,9 +540,7 @@ int hao_al_ladder(hao_ctx *c, const hao_ovlp_t *ol, uint64_t n_ol, const uint64_
 		const dim3 gm((unsigned)((m + 255) / 256));
 		HIP_TRY(hipMemsetAsync(G.ctr.p + HAO_LD_RND, 0, HAO_LD_RND_N * 8, c->stream)); HIP_TRY(hipMemsetAsync(G.selcnt.p, 0, 16 * 8, c->stream)); HIP_TRY(hipMemsetAsync(c->al_want.p, 0, m, c->stream));
 		hipLaunchKernelGGL(hao_ld_task_kernel, gm, b_, 0, c->stream, A, j, G.att.p, open, m, c->al_task.p, G.coord.p, c->al_k1.p, c->al_i1.p, G.ctr.p); HAO_CHECK_LAUNCH();
-		size_t tb = 0;
-		HIP_TRY(rocprim::radix_sort_pairs(nullptr, tb, c->al_k1.p, c->al_k2.p, c->al_i1.p, c->al_order.p, m, 0, 64, c->stream)); HIP_TRY(hao_tmp(c, tb));
-		HIP_TRY(rocprim::radix_sort_pairs(c->d_tmp.p, tb, c->al_k1.p, c->al_k2.p, c->al_i1.p, c->al_order.p, m, 0, 64, c->stream));
+		if (int rc = hao_al_sort_by_text(c, m)) return rc;
 		if (int rc = hao_peek(c, G.ctr.p + HAO_LD_RND, HAO_LD_RND_N, PK_LD_ROUND)) return rc;
 		HIP_TRY(hipStreamSynchronize(c->stream));
 		auto rnd = [&](int k) { return (uint64_t)c->peeked(PK_LD_ROUND, k - HAO_LD_RND); };
@@ -589,12 +554,8 @@ int hao_al_ladder(hao_ctx *c, const hao_ovlp_t *ol, uint64_t n_ol, const uint64_
 		HIP_TRY(rows.reserve(m * (uint64_t)cap + 1)); W.rows[j] = rows.p; W.cap[j] = cap;
 		hao_trace_result_t *dr = c->al_tres.p; uint8_t *want = c->al_want.p;
 		for (int md = 0; md < 4; ++md) if (lo[md][5] > lo[md][0]) {
-			const uint32_t words = (uint32_t)rnd(HAO_LD_WORDS + md); const uint64_t tn0 = std::max<uint64_t>(1, rnd(HAO_LD_TN + md)); int rc;
-			if (md == HAO_ALIGN_EXT_FWD) rc = hao_ld_first<HAO_AL_EXT_FWD>(c, R, md, lo[md], words, tn0, dr, want, rows.p, cap);
-			else if (md == HAO_ALIGN_EXT_BWD) rc = hao_ld_first<HAO_AL_EXT_BWD>(c, R, md, lo[md], words, tn0, dr, want, rows.p, cap);
-			else if (md == HAO_ALIGN_SEMI) rc = hao_ld_first<HAO_AL_SEMI>(c, R, md, lo[md], words, tn0, dr, want, rows.p, cap);
-			else rc = hao_ld_first<HAO_AL_GLOBAL>(c, R, md, lo[md], words, tn0, dr, want, rows.p, cap);
-			if (rc) return rc;
+			const uint32_t words = (uint32_t)rnd(HAO_LD_WORDS + md); const uint64_t tn0 = std::max<uint64_t>(1, rnd(HAO_LD_TN + md));
+			if (int rc = hao_by_mode(md, [&](auto M) { return hao_ld_first<decltype(M)::value>(c, R, md, lo[md], words, tn0, dr, want, rows.p, cap); })) return rc;
 		}
 		bool coop = false; for (int md = 0; md < 4; ++md) coop = coop || lo[md][5] > lo[md][1];
 		if (coop) {
@@ -604,12 +565,8 @@ int hao_al_ladder(hao_ctx *c, const hao_ovlp_t *ol, uint64_t n_ol, const uint64_
 				const uint64_t n_sel = c->peeked(PK_LD_SEL, md * 4 + (k - 1)), pw = rnd(HAO_LD_PW + md * 4 + (k - 1));
 				if (!n_sel) continue;
 				if (n_sel > lo[md][k + 1] - lo[md][k] || !pw) { hao_set_err(c, "hao_window_ladder: more selected pairs than tasks"); return HAO_EUNSUPP; }
-				const uint32_t *sel = G.sel.p + lo[md][k]; int rc;
-				if (md == HAO_ALIGN_EXT_FWD) rc = hao_ld_second<HAO_AL_EXT_FWD>(c, R, k, sel, n_sel, pw, dr, rows.p, cap);
-				else if (md == HAO_ALIGN_EXT_BWD) rc = hao_ld_second<HAO_AL_EXT_BWD>(c, R, k, sel, n_sel, pw, dr, rows.p, cap);
-				else if (md == HAO_ALIGN_SEMI) rc = hao_ld_second<HAO_AL_SEMI>(c, R, k, sel, n_sel, pw, dr, rows.p, cap);
-				else rc = hao_ld_second<HAO_AL_GLOBAL>(c, R, k, sel, n_sel, pw, dr, rows.p, cap);
-				if (rc) return rc;
+				const uint32_t *sel = G.sel.p + lo[md][k];
+				if (int rc = hao_by_mode(md, [&](auto M) { return hao_ld_second<decltype(M)::value>(c, R, k, sel, n_sel, pw, dr, rows.p, cap); })) return rc;
 			}
 		}
 		hipLaunchKernelGGL(hao_ld_commit_kernel, gm, b_, 0, c->stream, j, G.att.p, open, m, c->al_task.p, G.coord.p, dr, cap, G.res.p, G.ncig.p, G.rowref.p, next, G.ctr.p); HAO_CHECK_LAUNCH();

@@ -19,6 +19,27 @@ def scenario_reads(name):
     return _CACHE[name]
 
 
+MANY_SLICES = {"HAO_DBG_TEST": "al_slice=8"}      # hao_col_slice's floor: every slice of a traced sweep has 256 pairs
+
+
+def scenario_engine(name, env=None):
+    """an engine over the scenario's reads, created with `env` in the environment (the switches are read once, when the engine is created) -> (engine, reads)"""
+    from hifiasm_amd.api import Engine
+    rs, okw = scenario_reads(name)
+    old = {k: os.environ.get(k) for k in (env or {})}
+    os.environ.update(env or {})
+    try:
+        e = Engine(0, **okw)
+    finally:
+        for k, v in old.items():
+            if v is None:
+                del os.environ[k]
+            else:
+                os.environ[k] = v
+    e.set_readset(rs)
+    return e, rs
+
+
 def load_golden(name):
     z = np.load(os.path.join(GOLDEN, f"{name}.npz"))
     d = {k: z[k] for k in z.files}

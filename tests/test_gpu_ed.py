@@ -5,7 +5,7 @@ forward / backward extension, semi-global): error count, end points and cigars. 
 import numpy as np
 import pytest
 
-from helpers import ed_tasks, ed_global_tasks, ed_semi_trace_tasks, ed_ext_tasks, scenario_reads, scenario_oracle
+from helpers import ed_tasks, ed_global_tasks, ed_semi_trace_tasks, ed_ext_tasks, scenario_reads, scenario_oracle, scenario_engine, MANY_SLICES
 
 pytestmark = pytest.mark.gpu
 SETS = [("hifi", False), ("ont", False), ("nn", False), ("edge", False), ("rr", False), ("hifi_15k", False), ("hifi", True), ("ont", True), ("hifi_15k", True)]
@@ -63,3 +63,19 @@ def test_window_trace(name, wide, mode, gen):
         with pytest.raises(HaoError):
             e.window_trace_batch(badt, mode=3)
     e.close()
+
+
+def test_window_trace_in_many_slices():
+    """test_window_trace's assertion for the semi-global mode on the smallest set of SETS (edge: 1296 tasks, of which the oracle aligns 1034), with a column
+    budget of 8 bytes: the second sweep walks slices of 256 pairs - four whole ones and a partial one - where the default budget makes it one"""
+    name, mode = "edge", 3
+    o = scenario_oracle(name)
+    t = ed_semi_trace_tasks(name, n_reads=40, seed=7 + mode, wide=False)
+    want, wcig = o.window_trace(t, cap=136, mode=mode)
+    assert (want[:, 0] != NOALN).sum() >= 257                   # the pairs of the second sweep: those that align within their threshold
+    e, _ = scenario_engine(name, MANY_SLICES)
+    got, gcig = e.window_trace_batch(t, cap=136, mode=mode)
+    e.close()
+    assert (got == want).all(), np.flatnonzero((got != want).any(axis=1))[:10]
+    bad = [q for q in range(t.shape[0]) if not (gcig[q, :want[q, 5]] == wcig[q, :want[q, 5]]).all()]
+    assert not bad, bad[:10]

@@ -18,7 +18,7 @@ import os
 import numpy as np
 import pytest
 
-from helpers import scenario_reads, scenario_oracle
+from helpers import scenario_reads, scenario_oracle, scenario_engine, MANY_SLICES
 import rescue_model as RM
 
 pytestmark = pytest.mark.gpu
@@ -40,17 +40,14 @@ GRID_THRE = 31
 GOLD_KEY = {("hifi", 775, 0.04): "hifi", ("ont", 375, 0.07): "ont", ("hifi", 775, 0.004): "hifi004", ("ont", 375, 0.015): "ont015", ("fz2", 1500, 0.006): "fz2w"}
 
 
-def _engine(name):
-    from hifiasm_amd.api import Engine
-    rs, okw = scenario_reads(name)
-    e = Engine(0, **okw)
-    e.set_readset(rs); e.ha_ft_gen(); e.ha_pt_gen()
+def _engine(name, env=None):
+    e, rs = scenario_engine(name, env)
+    e.ha_ft_gen(); e.ha_pt_gen()
     return e, rs
 
 
-def check_read(e, o_align, rs, r, wl, e_rate, res_r, seen):
-    ol, fc, fo, _ = e.h_ec_lchain(r)
-    want = RM.read_rescue(ol, fc, fo, rs.lengths, wl, e_rate, res_r, o_align)
+def check_read(e, r, want, seen):
+    """want: tests/rescue_model.py's overlaps of read r"""
     ov, wins = e.fetch_rescue(r)
     assert ov.shape[0] == len(want) == len(wins)
     n = 0
@@ -65,9 +62,10 @@ def check_read(e, o_align, rs, r, wl, e_rate, res_r, seen):
     return n, len(want)
 
 
-@pytest.mark.parametrize("name,wl,e_rate", CASES)
-def test_rescue_blocking_equals_the_model(name, wl, e_rate):
-    e, rs = _engine(name)
+def _blocking_case(name, wl, e_rate, env=None, min_states=0):
+    """min_states: the overlaps in which the model meets an unaligned window before an aligned one ("gap") - each of them takes a state of the stage's sliced
+    rounds - are at least that many, asserted before the stage runs"""
+    e, rs = _engine(name, env)
     o = scenario_oracle(name)
     align = RM.oracle_aligner(o)
     seen = {}
@@ -76,13 +74,19 @@ def test_rescue_blocking_equals_the_model(name, wl, e_rate):
         n, unres = e.window_ed_ref(wl, e_rate)
         assert unres == 0
         T, R = e.fetch_ed_grid(n)
-        total = e.window_rescue_ref()
-        k = got_total = n_ol = 0
+        wants, k = [], 0
         for r in range(rs.n):
-            m = RM.M.read_tasks(*e.h_ec_lchain(r)[:3], rs.lengths, wl, e_rate).shape[0]
-            a, b = check_read(e, align, rs, r, wl, e_rate, R[k:k + m], seen)
-            got_total += a; n_ol += b; k += m
-        assert k == n and got_total == total
+            ol, fc, fo, _ = e.h_ec_lchain(r)
+            m = RM.M.read_tasks(ol, fc, fo, rs.lengths, wl, e_rate).shape[0]
+            wants.append(RM.read_rescue(ol, fc, fo, rs.lengths, wl, e_rate, R[k:k + m], align)); k += m
+        assert k == n
+        assert sum("gap" in w["events"] for want in wants for w in want) >= min_states
+        total = e.window_rescue_ref()
+        got_total = n_ol = 0
+        for r in range(rs.n):
+            a, b = check_read(e, r, wants[r], seen)
+            got_total += a; n_ol += b
+        assert got_total == total
         assert n_ol > 100
         ends = [rs.n - 1] + [r for r in range(rs.n) if e.h_ec_lchain(r)[0].shape[0] == 0][:1]      # the two ends of the records' CSR: the batch's last read, a read without overlaps
         for r in ends:
@@ -104,6 +108,18 @@ def test_rescue_blocking_equals_the_model(name, wl, e_rate):
         assert not missing, (missing, seen)
     finally:
         e.close()
+
+
+@pytest.mark.parametrize("name,wl,e_rate", CASES)
+def test_rescue_blocking_equals_the_model(name, wl, e_rate):
+    _blocking_case(name, wl, e_rate)
+
+
+@pytest.mark.parametrize("case", [("ont", 375, 0.015)])      # (the emulated twin takes a smaller case of CASES: tests/test_simt_rescue_cpu.py)
+def test_rescue_blocking_in_many_slices(case):
+    """the case of CASES with the most overlaps that need a rescue (ont at 375 / 1.5 %: 5693 in which the model meets a gap), with a column budget of 8 bytes: the
+    rounds run over slices of 256 states, the last one partial, where the default budget makes it one slice"""
+    _blocking_case(*case, env=MANY_SLICES, min_states=257)
 
 
 def test_contract():

@@ -7,18 +7,16 @@ for bit, with both slots in flight over batches that do not start at read 0.  Th
 import numpy as np
 import pytest
 
-from helpers import ed_tasks_grid_all, scenario_reads, scenario_oracle
+from helpers import ed_tasks_grid_all, scenario_reads, scenario_oracle, scenario_engine, MANY_SLICES
 
 pytestmark = pytest.mark.gpu
 NOALN = 2**31 - 1
 CASES = [("hifi", 375, 15), ("hifi", 375, 40), ("nn", 375, 15), ("rr", 375, 15), ("hifi", 775, 70), ("nn", 775, 100), ("edge", 100, 3), ("rr", 775, 100)]
 
 
-def _engine(name):
-    from hifiasm_amd.api import Engine
-    rs, okw = scenario_reads(name)
-    e = Engine(0, **okw)
-    e.set_readset(rs); e.ha_ft_gen(); e.ha_pt_gen()
+def _engine(name, env=None):
+    e, rs = scenario_engine(name, env)
+    e.ha_ft_gen(); e.ha_pt_gen()
     return e, rs
 
 
@@ -57,15 +55,18 @@ def _check_traced(e, o, t, r, off, cg, thre):
     return idx.size
 
 
-@pytest.mark.parametrize("name,window,thre", CASES)
-def test_grid_pairs_traced_on_the_device(name, window, thre):
-    e, rs = _engine(name)
+def _grid_case(name, window, thre, env=None, min_traced=0):
+    """min_traced: the pairs the oracle aligns inside the semi-global domain - the pairs of the sliced sweep - are at least that many (thre <= 63), asserted first"""
+    e, rs = _engine(name, env)
     o = scenario_oracle(name)
     try:
         lo, hi = (0, rs.n) if name != "hifi" else (7, rs.n - 5)      # (a batch that does not start at read 0)
-        (n, nt, nc, nu), t, r, off, cg = _blocking(e, lo, hi, window, thre)
+        e.overlap_batch(lo, hi)
         ols = [e.h_ec_lchain(q)[0] for q in range(lo, hi)]
         want_t = ed_tasks_grid_all(rs.lengths, ols, lo, window, thre)
+        if min_traced:
+            assert int(((o.window_ed(want_t)[:, 0] != NOALN) & _semi_domain(want_t)).sum()) >= min_traced
+        (n, nt, nc, nu), t, r, off, cg = _blocking(e, lo, hi, window, thre)
         assert n == want_t.shape[0] and (n > 200 or name == "edge")
         assert (t == want_t).all(), np.flatnonzero((t != want_t).any(axis=1))[:10]
         ne = e.window_ed_grid(window, thre)
@@ -80,6 +81,18 @@ def test_grid_pairs_traced_on_the_device(name, window, thre):
         print(f"[trace grid] {name} window {window} thre {thre}: {n} pairs, {nt} traced, {nu} aligned but untraced, {nc} cigar entries")
     finally:
         e.close()
+
+
+@pytest.mark.parametrize("name,window,thre", CASES)
+def test_grid_pairs_traced_on_the_device(name, window, thre):
+    _grid_case(name, window, thre)
+
+
+@pytest.mark.parametrize("case", [("rr", 375, 15)])      # (the emulated twin takes a smaller case of CASES: tests/test_simt_trace_grid_cpu.py)
+def test_grid_pairs_traced_in_many_slices(case):
+    """the case of CASES with the most traced pairs (rr at 375 / 15: 75 166 of 148 235), with a column budget of 8 bytes: the traced sweep, its scan and its
+    compaction walk slices of 256 pairs, the last one partial, where the default budget makes it one slice"""
+    _grid_case(*case, env=MANY_SLICES, min_traced=257)
 
 
 def _parts(which):

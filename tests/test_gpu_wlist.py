@@ -18,7 +18,7 @@ On the sampled reads of tests/golden/wlist.npz (the reference's own functions) t
 import numpy as np
 import pytest
 
-from helpers import scenario_reads, scenario_oracle
+from helpers import scenario_reads, scenario_oracle, scenario_engine, MANY_SLICES
 import rescue_model as RM
 import wlist_model as WM
 
@@ -41,17 +41,15 @@ EXPECT = {("hifi", 775, 0.04): COMMON + ("backward_traced", "anchor_traced", "ve
 GOLD_KEY = {("hifi", 775, 0.04): "hifi", ("hifi", 775, 0.004): "hifi004", ("ont", 375, 0.015): "ont015", ("fz2", 1500, 0.006): "fz2w", ("nn", 200, 0.01): "nn200", ("hifi", 375, 0.01): "hifi375"}
 
 
-def _engine(name):
-    from hifiasm_amd.api import Engine
-    rs, okw = scenario_reads(name)
-    e = Engine(0, **okw)
-    e.set_readset(rs); e.ha_ft_gen(); e.ha_pt_gen()
+def _engine(name, env=None):
+    e, rs = scenario_engine(name, env)
+    e.ha_ft_gen(); e.ha_pt_gen()
     return e, rs
 
 
-@pytest.mark.parametrize("name,wl,e_rate", CASES)
-def test_wlist_blocking_equals_the_model(name, wl, e_rate):
-    e, rs = _engine(name)
+def _blocking_case(name, wl, e_rate, env=None, min_swept=0):
+    """min_swept: the windows the model sweeps - the records of the stage's sliced sweep - are at least that many, asserted before the stage runs"""
+    e, rs = _engine(name, env)
     o = scenario_oracle(name)
     align, trace0 = RM.oracle_aligner(o), WM.oracle_tracer(o)
     asked = {}
@@ -67,15 +65,19 @@ def test_wlist_blocking_equals_the_model(name, wl, e_rate):
         n, unres = e.window_ed_ref(wl, e_rate)
         assert unres == 0
         T, R = e.fetch_ed_grid(n)
-        total = e.window_rescue_ref()
-        out = e.window_wlist_ref()
-        assert e.window_wlist_ref() == out                                       # again on the same batch: the same result
-        k = n_rec = n_swept = n_cig = n_untr = n_ol = n_tried = 0
+        wants, k = [], 0
         for r in range(rs.n):
             ol, fc, fo, _ = e.h_ec_lchain(r)
             m = RM.M.read_tasks(ol, fc, fo, rs.lengths, wl, e_rate).shape[0]
-            rr, want = WM.read_wlist(ol, fc, fo, rs.lengths, wl, e_rate, R[k:k + m], align, trace)
+            wants.append(WM.read_wlist(ol, fc, fo, rs.lengths, wl, e_rate, R[k:k + m], align, trace))
             k += m
+        assert sum(sw for rr, want in wants for ww, wc, ev, sw, nt in want) >= min_swept
+        total = e.window_rescue_ref()
+        out = e.window_wlist_ref()
+        assert e.window_wlist_ref() == out                                       # again on the same batch: the same result
+        n_rec = n_swept = n_cig = n_untr = n_ol = n_tried = 0
+        for r in range(rs.n):
+            rr, want = wants[r]
             got = e.fetch_wlist(r)
             ov, rwins = e.fetch_rescue(r)                                        # (still fetchable)
             assert len(got) == len(want) == ov.shape[0]
@@ -118,6 +120,18 @@ def test_wlist_blocking_equals_the_model(name, wl, e_rate):
         assert not missing, (missing, seen)
     finally:
         e.close()
+
+
+@pytest.mark.parametrize("name,wl,e_rate", CASES)
+def test_wlist_blocking_equals_the_model(name, wl, e_rate):
+    _blocking_case(name, wl, e_rate)
+
+
+@pytest.mark.parametrize("case", [("nn", 200, 0.01)])      # (the emulated twin takes a smaller case of CASES: tests/test_simt_wlist_cpu.py)
+def test_wlist_blocking_in_many_slices(case):
+    """the case of CASES with the most swept windows (nn at 200 / 1 %: 44 065), with a column budget of 8 bytes: the traced sweep walks slices of 256 records, the
+    last one partial, where the default budget makes it one slice"""
+    _blocking_case(*case, env=MANY_SLICES, min_swept=257)
 
 
 def test_contract():
