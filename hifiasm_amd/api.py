@@ -91,6 +91,7 @@ ABI_SYMBOLS = [
     "hao_window_wlist_ref", "hao_fetch_wlist", "hao_deliver_wlist", "hao_unpack_wlist",
     "hao_dist_gather_reads", "hao_reads_digest", "hao_index_load_dist", "hao_shard_layout",
     "hao_window_ladder", "hao_fetch_ladder", "hao_ladder_thresholds",
+    "hao_window_ladder_adv", "hao_fetch_ladder_adv", "hao_ladder_adv_thresholds",
 ]
 
 
@@ -101,6 +102,9 @@ LADDER_REQ = np.dtype([("ol", np.uint32), ("mode", np.uint32), ("qs", np.int32),
 LADDER_RES = np.dtype([("rung", np.uint32), ("thre", np.int32), ("qs", np.int32), ("qe", np.int32), ("ts", np.int32), ("te", np.int32), ("aux_beg", np.int32), ("flags", np.uint32),
                        ("err", np.int32), ("a_ps", np.int32), ("a_pe", np.int32), ("a_ts", np.int32), ("a_te", np.int32), ("n_cigar", np.int32)])
 LADDER_REFUSED, LADDER_UNTRACED = 1, 2
+# hao_ladder_adv_res_t (hao_window_ladder_adv), its further flag and the rung id of the exact shortcut
+LADDER_ADV_RES = np.dtype([("done", np.int32)] + [(n, LADDER_RES.fields[n][0]) for n in LADDER_RES.names])
+LADDER_REPEAT, LADDER_RUNG_EXACT = 4, 6
 WLIST_PRIMARY, WLIST_UNTRACED = 3, 1 << 19      # hao_wlist_win_t::info: source of a first-placement window the rescue did not trace; the untraced flag
 
 
@@ -230,6 +234,9 @@ def lib():
         L.hao_window_ladder.argtypes = [vp, vp, C.c_uint64, C.c_double, C.c_int64, C.c_int64, vp, vp, vp, C.c_uint64, u64p]
         L.hao_fetch_ladder.argtypes = [vp, vp, C.c_uint64, u64p, u64p]
         L.hao_ladder_thresholds.argtypes = [C.c_int64, C.c_int64, C.c_double, C.c_int64, C.c_int64, C.POINTER(C.c_int32)]
+        L.hao_window_ladder_adv.argtypes = [vp, vp, C.c_uint64, C.c_double, C.c_int64, C.c_int64, C.c_int64, C.c_int64, vp, vp, vp, C.c_uint64, u64p]
+        L.hao_fetch_ladder_adv.argtypes = [vp, vp, C.c_uint64, u64p, u64p]
+        L.hao_ladder_adv_thresholds.argtypes = [C.c_int64, C.c_int64, C.c_double, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
         L.hao_index_save.argtypes = [vp, C.c_char_p, C.c_int32, vp]
         L.hao_index_load.argtypes = [vp, C.c_char_p, C.POINTER(C.c_int32)]
         L.hao_index_load_dist.argtypes = [vp, C.c_char_p, u64p, C.POINTER(C.c_int32)]
@@ -684,6 +691,16 @@ class Engine:
         """hao_window_ladder over the current batch: req = LADDER_REQ records (or int rows ol, mode, qs, qe, ts, te, estimate_err) -> (LADDER_RES records, cig_off
         int64 [n + 1], cigars uint16).  cap = None: the stage runs once and the entries, which stay resident, are fetched at their size (hao_fetch_ladder); a
         number: the entries come back only when they fit it (cigars is None otherwise; cig_off[-1] is the capacity needed)"""
+        return self._ladder(req, cap, LADDER_RES, "hao_window_ladder", self.L.hao_fetch_ladder,
+                            lambda *a: self.L.hao_window_ladder(self.h, a[0], a[1], C.c_double(e_rate), C.c_int64(maxl), C.c_int64(maxe), *a[2:]))
+
+    def window_ladder_adv(self, req, e_rate, wl, maxl, maxe, force_l, cap=None):
+        """hao_window_ladder_adv (hc_aln_exz_adv's ladder: early returns, exact shortcut, five rungs, absolute coordinates) over the current batch; requests, cap and
+        the returned triple as for window_ladder, the records being LADDER_ADV_RES; estimate_err = -1 asks for ql * e_rate (ql <= wl)"""
+        return self._ladder(req, cap, LADDER_ADV_RES, "hao_window_ladder_adv", self.L.hao_fetch_ladder_adv,
+                            lambda *a: self.L.hao_window_ladder_adv(self.h, a[0], a[1], C.c_double(e_rate), C.c_int64(wl), C.c_int64(maxl), C.c_int64(maxe), C.c_int64(force_l), *a[2:]))
+
+    def _ladder(self, req, cap, res_dtype, who, fetch, call):
         q = np.asarray(req)
         if q.dtype != LADDER_REQ:
             rows = np.asarray(req, dtype=np.int64).reshape(-1, 7)
@@ -691,13 +708,12 @@ class Engine:
             for k, f in enumerate(("ol", "mode", "qs", "qe", "ts", "te", "estimate_err")):
                 q[f] = rows[:, k]
         q = np.ascontiguousarray(q); n = q.shape[0]
-        res = np.zeros(n, dtype=LADDER_RES); off = np.zeros(n + 1, dtype=np.uint64); need = C.c_uint64()
+        res = np.zeros(n, dtype=res_dtype); off = np.zeros(n + 1, dtype=np.uint64); need = C.c_uint64()
         cig = np.zeros(max(1, cap or 0), dtype=np.uint16)
-        self._ck(self.L.hao_window_ladder(self.h, q.ctypes.data_as(C.c_void_p), n, C.c_double(e_rate), C.c_int64(maxl), C.c_int64(maxe), res.ctypes.data_as(C.c_void_p),
-                                          off.ctypes.data_as(C.c_void_p), cig.ctypes.data_as(C.c_void_p), cap or 0, C.byref(need)), "hao_window_ladder")
+        self._ck(call(q.ctypes.data_as(C.c_void_p), n, res.ctypes.data_as(C.c_void_p), off.ctypes.data_as(C.c_void_p), cig.ctypes.data_as(C.c_void_p), cap or 0, C.byref(need)), who)
         if cap is None:
             cig = np.zeros(max(1, need.value), dtype=np.uint16)
-            self._ck(self.L.hao_fetch_ladder(self.h, cig.ctypes.data_as(C.c_void_p), cig.shape[0], None, None), "hao_fetch_ladder")
+            self._ck(fetch(self.h, cig.ctypes.data_as(C.c_void_p), cig.shape[0], None, None), who + ": fetch")
             return res, off.astype(np.int64), cig[:need.value]
         return res, off.astype(np.int64), (cig[:need.value] if need.value <= cap else None)
 
@@ -705,6 +721,12 @@ class Engine:
         """the requests that were open in each of the last hao_window_ladder call's four rounds"""
         r = (C.c_uint64 * 4)()
         self._ck(self.L.hao_fetch_ladder(self.h, None, 0, None, r), "hao_fetch_ladder")
+        return [int(x) for x in r]
+
+    def ladder_adv_rounds(self):
+        """the requests that were open in each of the last hao_window_ladder_adv call's five rounds"""
+        r = (C.c_uint64 * 5)()
+        self._ck(self.L.hao_fetch_ladder_adv(self.h, None, 0, None, r), "hao_fetch_ladder_adv")
         return [int(x) for x in r]
 
     def window_ed_grid(self, window=375, thre=15):
@@ -861,6 +883,14 @@ def ladder_thresholds(ql, estimate_err, e_rate, maxl, maxe):
     t = (C.c_int32 * 4)()
     n = lib().hao_ladder_thresholds(ql, estimate_err, C.c_double(e_rate), maxl, maxe, t)
     return [int(x) for x in t], n
+
+
+def ladder_adv_thresholds(ql, estimate_err, e_rate, wl, maxl, maxe, force_l):
+    """hao_ladder_adv_thresholds: the five raw rungs of hc_aln_exz_adv for a request as the device computes them (-1: skipped), whether the gate is open, and the
+    number of attempts (negative: estimate_err < 0 with ql > wl)"""
+    t = (C.c_int32 * 5)(); g = C.c_int32(0)
+    n = lib().hao_ladder_adv_thresholds(ql, estimate_err, C.c_double(e_rate), wl, maxl, maxe, force_l, t, C.byref(g))
+    return [int(x) for x in t], bool(g.value), n
 
 
 def ref_thresholds(window, e_rate):

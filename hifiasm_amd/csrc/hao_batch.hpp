@@ -238,6 +238,7 @@ static int hao_ed_ref_run(hao_ctx *c, uint32_t wl, double e_rate, uint64_t *n_ta
 int hao_al_rescue(hao_ctx *c, const hao_ref_io &io);      // (hao_f3.hip)
 int hao_al_wlist(hao_ctx *c, const hao_ref_io &io);
 int hao_al_ladder(hao_ctx *c, const hao_ovlp_t *ol, uint64_t n_ol, const uint64_t *fc, const uint64_t *fc_off, uint64_t n, double e_rate, int64_t maxl, int64_t maxe, uint64_t *n_cigar, uint64_t rounds_out[4]);      // (the threshold ladder, hao_ladder.cuh)
+int hao_al_ladder_adv(hao_ctx *c, const hao_ovlp_t *ol, uint64_t n_ol, const uint64_t *fc, const uint64_t *fc_off, uint64_t n, double e_rate, int64_t wl, int64_t maxl, int64_t maxe, int64_t force_l, uint64_t *n_cigar, uint64_t rounds_out[5]);      // (the same under hc_aln_exz_adv's rules)
 // the batch as the blocking chain has it: hao_ed_ref_run's table, pair list and results per pair (c->al_res); results into the context's own buffers
 static hao_ref_io hao_ref_io_ctx(hao_ctx *c)
 {

@@ -555,43 +555,58 @@ int hao_fetch_wlist(hao_ctx *c, uint64_t rid, uint64_t *n_ol, const uint64_t **w
 	return HAO_OK;
 }
 
-// the threshold ladder (hao_ladder.cuh, hao_f3.hip): requests up, the stage over the batch's final ol->list and fake cigars, results / offsets / entries down
-static int hao_ladder_run(hao_ctx *c, const hao_ladder_req_t *req, uint64_t n, double e_rate, int64_t maxl, int64_t maxe, hao_ladder_res_t *out, uint64_t *cig_off, uint16_t *cigars, uint64_t cigar_cap, uint64_t *n_cigar)
+// the threshold ladder (hao_ladder.cuh, hao_f3.hip): requests up, the stage over the batch's final ol->list and fake cigars, results / offsets / entries down.
+// adv: hao_window_ladder_adv (out: hao_ladder_adv_res_t records); else hao_window_ladder (out: hao_ladder_res_t records; wl and force_l unused)
+static int hao_ladder_run(hao_ctx *c, bool adv, const hao_ladder_req_t *req, uint64_t n, double e_rate, int64_t wl, int64_t maxl, int64_t maxe, int64_t force_l, void *out, uint64_t *cig_off, uint16_t *cigars, uint64_t cigar_cap, uint64_t *n_cigar)
 {
+	const std::string who = adv ? "hao_window_ladder_adv" : "hao_window_ladder";
 	hao_ctx::Batch &B = *c->batch; hao_ctx::Batch::OutSet &O = B.O(); hao_ctx::Ladder &G = c->ld;
-	*n_cigar = 0; c->ld_valid = false; c->ld_ncig = 0; for (int j = 0; j < 4; ++j) c->ld_rounds[j] = 0;
-	{ HAO_STAGE_VIEW(c, V, "hao_window_ladder needs the bases of both reads"); (void)V; }
-	if (!(e_rate >= 0 && e_rate <= 1) || maxl < 0 || maxe < 0 || maxe > HAO_ED_LONG_MAX_THRE) { hao_set_err(c, "hao_window_ladder: e_rate outside [0, 1], maxl negative, or maxe negative or beyond HAO_ED_LONG_MAX_THRE"); return HAO_EINVAL; }
-	if (n >= (1ULL << 32)) { hao_set_err(c, "hao_window_ladder: more than 2^32 requests in one call"); return HAO_EUNSUPP; }
+	*n_cigar = 0; c->ld_valid = false; c->ld_adv = adv; c->ld_ncig = 0; for (int j = 0; j < 5; ++j) c->ld_rounds[j] = 0;
+	if (adv) { HAO_STAGE_VIEW(c, V, "hao_window_ladder_adv needs the bases of both reads"); (void)V; }
+	else { HAO_STAGE_VIEW(c, V, "hao_window_ladder needs the bases of both reads"); (void)V; }
+	if (!(e_rate >= 0 && e_rate <= 1) || maxl < 0 || maxe < 0 || maxe > HAO_ED_LONG_MAX_THRE || wl < 0 || force_l < 0) { hao_set_err(c, who + ": e_rate outside [0, 1], maxl" + (adv ? ", wl or force_l" : "") + " negative, or maxe negative or beyond HAO_ED_LONG_MAX_THRE"); return HAO_EINVAL; }
+	if (n >= (1ULL << 32)) { hao_set_err(c, who + ": more than 2^32 requests in one call"); return HAO_EUNSUPP; }
 	c->win.on_host_fed();      // (the task / result scratch is shared with the other window-alignment calls)
 	if (n == 0) { cig_off[0] = 0; c->ld_valid = true; return HAO_OK; }
 	HIP_TRY(G.req.reserve(n));
 	HIP_TRY(hipMemcpyAsync(G.req.p, req, n * sizeof(hao_ladder_req_t), hipMemcpyHostToDevice, c->stream));
-	if (int rc = hao_al_ladder(c, O.ol_out.p, B.n_ol, O.fc_out.p, O.fc_out_off.p, n, e_rate, maxl, maxe, n_cigar, c->ld_rounds)) return rc;
-	HIP_TRY(hipMemcpyAsync(out, G.res.p, n * sizeof(hao_ladder_res_t), hipMemcpyDeviceToHost, c->stream));
+	if (int rc = adv ? hao_al_ladder_adv(c, O.ol_out.p, B.n_ol, O.fc_out.p, O.fc_out_off.p, n, e_rate, wl, maxl, maxe, force_l, n_cigar, c->ld_rounds)
+	                 : hao_al_ladder(c, O.ol_out.p, B.n_ol, O.fc_out.p, O.fc_out_off.p, n, e_rate, maxl, maxe, n_cigar, c->ld_rounds)) return rc;
+	if (adv) HIP_TRY(hipMemcpyAsync(out, G.res_adv.p, n * sizeof(hao_ladder_adv_res_t), hipMemcpyDeviceToHost, c->stream));
+	else HIP_TRY(hipMemcpyAsync(out, G.res.p, n * sizeof(hao_ladder_res_t), hipMemcpyDeviceToHost, c->stream));
 	HIP_TRY(hipMemcpyAsync(cig_off, G.off.p, (n + 1) * 8, hipMemcpyDeviceToHost, c->stream));
 	if (*n_cigar && *n_cigar <= cigar_cap) HIP_TRY(hipMemcpyAsync(cigars, G.cig.p, *n_cigar * 2, hipMemcpyDeviceToHost, c->stream));
 	HIP_TRY(hipStreamSynchronize(c->stream));
-	hao_release_above(c->al_path, HAO_SCRATCH_KEEP);
-	for (int j = 0; j < 4; ++j) hao_release_above(G.rows[j], HAO_SCRATCH_KEEP);
+	hao_release_above(c->al_path, HAO_SCRATCH_KEEP);      // (the buffers that grow with the requests alone - requests, results, lists, offsets - keep their largest size, like every per-item buffer of the context)
+	for (int j = 0; j < 5; ++j) hao_release_above(G.rows[j], HAO_SCRATCH_KEEP);
 	c->ld_ncig = *n_cigar; c->ld_valid = true;
 	return HAO_OK;
 }
 
-int hao_fetch_ladder(hao_ctx *c, uint16_t *cigars, uint64_t cigar_cap, uint64_t *n_cigar, uint64_t rounds[4])
+// the resident entries and the per-round open counts of the last ladder call, which must have been the one this fetch belongs to (n_rounds: 4, or 5 for the adv call)
+static int hao_fetch_ladder_of(hao_ctx *c, bool adv, uint16_t *cigars, uint64_t cigar_cap, uint64_t *n_cigar, uint64_t *rounds, int n_rounds)
 {
 	if (!c) return HAO_EINVAL;
-	if (!c->ld_valid) { hao_set_err(c, "hao_fetch_ladder: no results of hao_window_ladder are resident"); return HAO_EINVAL; }
+	const std::string who = adv ? "hao_fetch_ladder_adv" : "hao_fetch_ladder";
+	if (!c->ld_valid || c->ld_adv != adv) { hao_set_err(c, who + ": no results of " + (adv ? "hao_window_ladder_adv" : "hao_window_ladder") + " are resident"); return HAO_EINVAL; }
 	if (n_cigar) *n_cigar = c->ld_ncig;
-	if (rounds) for (int j = 0; j < 4; ++j) rounds[j] = c->ld_rounds[j];
+	if (rounds) for (int j = 0; j < n_rounds; ++j) rounds[j] = c->ld_rounds[j];
 	if (cigars && c->ld_ncig && c->ld_ncig <= cigar_cap) { HIP_TRY(hipSetDevice(c->device)); HIP_TRY(hipMemcpy(cigars, c->ld.cig.p, c->ld_ncig * 2, hipMemcpyDeviceToHost)); }
 	return HAO_OK;
 }
+int hao_fetch_ladder(hao_ctx *c, uint16_t *cigars, uint64_t cigar_cap, uint64_t *n_cigar, uint64_t rounds[4]) { return hao_fetch_ladder_of(c, false, cigars, cigar_cap, n_cigar, rounds, 4); }
+int hao_fetch_ladder_adv(hao_ctx *c, uint16_t *cigars, uint64_t cigar_cap, uint64_t *n_cigar, uint64_t rounds[5]) { return hao_fetch_ladder_of(c, true, cigars, cigar_cap, n_cigar, rounds, 5); }
 
 int hao_window_ladder(hao_ctx *c, const hao_ladder_req_t *req, uint64_t n_req, double e_rate, int64_t maxl, int64_t maxe, hao_ladder_res_t *out, uint64_t *cig_off, uint16_t *cigars, uint64_t cigar_cap, uint64_t *n_cigar)
 {
 	if (!c || !cig_off || !n_cigar || (n_req && (!req || !out)) || (cigar_cap && !cigars)) return HAO_EINVAL;
-	return hao_window_stage(c, "ladder", [&] { return hao_ladder_run(c, req, n_req, e_rate, maxl, maxe, out, cig_off, cigars, cigar_cap, n_cigar); });
+	return hao_window_stage(c, "ladder", [&] { return hao_ladder_run(c, false, req, n_req, e_rate, 0, maxl, maxe, 0, out, cig_off, cigars, cigar_cap, n_cigar); });
+}
+
+int hao_window_ladder_adv(hao_ctx *c, const hao_ladder_req_t *req, uint64_t n_req, double e_rate, int64_t wl, int64_t maxl, int64_t maxe, int64_t force_l, hao_ladder_adv_res_t *out, uint64_t *cig_off, uint16_t *cigars, uint64_t cigar_cap, uint64_t *n_cigar)
+{
+	if (!c || !cig_off || !n_cigar || (n_req && (!req || !out)) || (cigar_cap && !cigars)) return HAO_EINVAL;
+	return hao_window_stage(c, "ladder_adv", [&] { return hao_ladder_run(c, true, req, n_req, e_rate, wl, maxl, maxe, force_l, out, cig_off, cigars, cigar_cap, n_cigar); });
 }
 
 int hao_deliver_wlist(hao_ctx *c, int slot, hao_wlist_delivery_t *out) { return hao_deliver_part(c, slot, out, &hao_ctx::Batch::Slot::wl, HAO_DELIVER_WLIST, "hao_deliver_wlist", "HAO_DELIVER_WLIST"); }

@@ -280,9 +280,11 @@ struct hao_ctx {
 	// cigar rows of each round (kept until the CSR array is filled), the CSR array, 64 counters
 	struct Ladder {
 		DevBuf<hao_ladder_req_t> req; DevBuf<hao_ladder_res_t> res; DevBuf<int32_t> att; DevBuf<uint64_t> ncig, rowref, off, poff, selcnt; DevBuf<uint32_t> open[2], sel; DevBuf<hao_ld_coord> coord;
-		DevBuf<uint16_t> rows[4], cig; DevBuf<unsigned long long> ctr;
+		DevBuf<uint16_t> rows[5], cig; DevBuf<unsigned long long> ctr;
+		// hao_window_ladder_adv only: its results, the exact shortcut's list and one-entry cigars, the threshold of each request's last attempt (pthre)
+		DevBuf<hao_ladder_adv_res_t> res_adv; DevBuf<uint32_t> xlist; DevBuf<uint16_t> xrow; DevBuf<int32_t> pth;
 	} ld;
-	bool ld_valid = false; uint64_t ld_ncig = 0, ld_rounds[4] = { 0, 0, 0, 0 };      // hao_fetch_ladder: the last call's entries are resident in ld.cig; their number; the open requests of each round
+	bool ld_valid = false, ld_adv = false; uint64_t ld_ncig = 0, ld_rounds[5] = { 0, 0, 0, 0, 0 };      // hao_fetch_ladder[_adv]: the last call's entries are resident in ld.cig (ld_adv: it was hao_window_ladder_adv); their number; the open requests of each round
 	// f3 with traceback on the grid (hao_trace_grid.cuh): the stage's scratch, compute stream only (hao_window_trace_grid and HAO_DELIVER_TRACE share it) -
 	// flags and selected pairs, entry counts and their scans, the compact array's offsets, the column scratch, the rows of one slice, two counters
 	struct TraceGrid {

@@ -514,32 +514,41 @@ template<int MODE> static int hao_ld_second(hao_ctx *c, const hao_ed_reads &R, i
 	return HAO_OK;
 }
 
-// n requests (already in c->ld.req) over the overlaps ol[n_ol] and their fake cigars: results in c->ld.res, CSR offsets in c->ld.off (n + 1), entries in c->ld.cig;
-// *n_cigar = the entries.  Host round trips: one for the checks, per round one for its counters, one per mode with narrow bands (hao_al_trace_run's selection) and
-// one for the cooperative classes' selections, one for the total at the end.
-int hao_al_ladder(hao_ctx *c, const hao_ovlp_t *ol, uint64_t n_ol, const uint64_t *fc, const uint64_t *fc_off, uint64_t n, double e_rate, int64_t maxl, int64_t maxe, uint64_t *n_cigar, uint64_t rounds_out[4])
+// n requests (already in c->ld.req) over the overlaps ol[n_ol] and their fake cigars: results in c->ld.res (ADV: c->ld.res_adv), CSR offsets in c->ld.off (n + 1), entries
+// in c->ld.cig; *n_cigar = the entries.  Host round trips: one for the checks, per round one for its counters, one per mode with narrow bands (hao_al_trace_run's selection) and
+// one for the cooperative classes' selections, one for the total at the end.  ADV (hao_ladder.cuh: the rule set of hc_aln_exz_adv, with wl and force_l): up to five rounds,
+// and the exact shortcut's kernel between the set-up and the first read-back, so that it costs no round trip of its own.
+template<bool ADV> static int hao_ld_run(hao_ctx *c, const char *who, typename hao_ld_rule<ADV>::res_t *res, const hao_ovlp_t *ol, uint64_t n_ol, const uint64_t *fc, const uint64_t *fc_off, uint64_t n,
+		double e_rate, int64_t wl, int64_t maxl, int64_t maxe, int64_t force_l, uint64_t *n_cigar, uint64_t *rounds_out)
 {
+	constexpr int NA = hao_ld_rule<ADV>::N_ATT;      // attempts per request = the most rounds
+	const std::string w_ = who;
 	hao_ctx::Ladder &G = c->ld; *n_cigar = 0;
 	hao_read_view V; (void)hao_reads_view(c, &V);
 	const hao_ed_reads R = hao_al_reads_of(c);
-	HIP_TRY(G.res.reserve(n)); HIP_TRY(G.att.reserve(4 * n)); HIP_TRY(G.ncig.reserve(n + 1)); HIP_TRY(G.rowref.reserve(n)); HIP_TRY(G.off.reserve(n + 2)); HIP_TRY(G.open[0].reserve(n)); HIP_TRY(G.open[1].reserve(n));
+	HIP_TRY(G.att.reserve(NA * n)); HIP_TRY(G.ncig.reserve(n + 1)); HIP_TRY(G.rowref.reserve(n)); HIP_TRY(G.off.reserve(n + 2)); HIP_TRY(G.open[0].reserve(n)); HIP_TRY(G.open[1].reserve(n));
 	HIP_TRY(G.sel.reserve(n)); HIP_TRY(G.selcnt.reserve(16)); HIP_TRY(G.coord.reserve(n)); HIP_TRY(G.ctr.reserve(64)); HIP_TRY(G.cig.reserve(1));
 	HIP_TRY(c->al_task.reserve(n)); HIP_TRY(c->al_k1.reserve(n)); HIP_TRY(c->al_k2.reserve(n)); HIP_TRY(c->al_i1.reserve(n)); HIP_TRY(c->al_order.reserve(n)); HIP_TRY(c->al_tres.reserve(n)); HIP_TRY(c->al_want.reserve(n));
 	HIP_TRY(hipMemsetAsync(G.ctr.p, 0, 64 * 8, c->stream));
-	hao_ld_args A; A.req = G.req.p; A.n_req = n; A.ol = ol; A.n_ol = n_ol; A.fc = fc; A.fc_off = fc_off; A.len = V.len; A.n_reads = V.n; A.e_rate = e_rate; A.maxl = maxl; A.maxe = maxe; A.coop_all = c->sw.al_coop ? 1 : 0;
+	hao_ld_args A; A.req = G.req.p; A.n_req = n; A.ol = ol; A.n_ol = n_ol; A.fc = fc; A.fc_off = fc_off; A.len = V.len; A.n_reads = V.n; A.e_rate = e_rate; A.maxl = maxl; A.maxe = maxe; A.coop_all = c->sw.al_coop ? 1 : 0; A.wl = wl; A.force_l = force_l;
 	const dim3 b_(256), gn((unsigned)((n + 255) / 256));
-	hipLaunchKernelGGL(hao_ld_thre_kernel, gn, b_, 0, c->stream, A, G.att.p, G.res.p, G.ncig.p, G.open[0].p, G.ctr.p); HAO_CHECK_LAUNCH();
+	if (ADV) { HIP_TRY(G.xlist.reserve(n)); HIP_TRY(G.xrow.reserve(n)); HIP_TRY(G.pth.reserve(n)); }
+	hipLaunchKernelGGL(hao_ld_thre_kernel<ADV>, gn, b_, 0, c->stream, A, G.att.p, res, G.ncig.p, G.open[0].p, G.xlist.p, G.pth.p, G.ctr.p); HAO_CHECK_LAUNCH();
+	if constexpr (ADV) { hipLaunchKernelGGL(hao_ld_exact_kernel, gn, b_, 0, c->stream, A, R, (const uint32_t*)G.xlist.p, n, (const int32_t*)G.att.p, res, G.ncig.p, G.rowref.p, G.xrow.p, G.open[0].p, G.ctr.p); HAO_CHECK_LAUNCH(); }
 	if (int rc = hao_peek(c, G.ctr.p, 2, PK_LD_SETUP)) return rc;
 	HIP_TRY(hipStreamSynchronize(c->stream));
-	if (c->peeked(PK_LD_SETUP)) { hao_set_err(c, "hao_window_ladder: " + std::to_string(c->peeked(PK_LD_SETUP)) + " requests out of range (overlap index, mode, estimate_err, coordinates, or a length beyond HAO_ED_LONG_MAX_LEN)"); return HAO_EINVAL; }
+	if (c->peeked(PK_LD_SETUP)) { hao_set_err(c, w_ + ": " + std::to_string(c->peeked(PK_LD_SETUP)) + " requests out of range (overlap index, mode, estimate_err, coordinates, or a length beyond HAO_ED_LONG_MAX_LEN)"); return HAO_EINVAL; }
 	uint64_t m = c->peeked(PK_LD_SETUP, 1);
-	hao_ld_rows W; for (int j = 0; j < 4; ++j) { W.rows[j] = nullptr; W.cap[j] = 0; rounds_out[j] = 0; }
-	for (int j = 0; j < 4 && m; ++j) {
+	if (m > n) { hao_set_err(c, w_ + ": more open requests than requests"); return HAO_EUNSUPP; }
+	hao_ld_rows W; for (int j = 0; j <= HAO_LD_ROUNDS; ++j) { W.rows[j] = nullptr; W.cap[j] = 0; }
+	for (int j = 0; j < NA; ++j) rounds_out[j] = 0;
+	if (ADV) { W.rows[HAO_LD_ROUNDS] = G.xrow.p; W.cap[HAO_LD_ROUNDS] = 1; }
+	for (int j = 0; j < NA && m; ++j) {
 		rounds_out[j] = m;
 		const uint32_t *open = G.open[j & 1].p; uint32_t *next = G.open[(j + 1) & 1].p;
 		const dim3 gm((unsigned)((m + 255) / 256));
 		HIP_TRY(hipMemsetAsync(G.ctr.p + HAO_LD_RND, 0, HAO_LD_RND_N * 8, c->stream)); HIP_TRY(hipMemsetAsync(G.selcnt.p, 0, 16 * 8, c->stream)); HIP_TRY(hipMemsetAsync(c->al_want.p, 0, m, c->stream));
-		hipLaunchKernelGGL(hao_ld_task_kernel, gm, b_, 0, c->stream, A, j, G.att.p, open, m, c->al_task.p, G.coord.p, c->al_k1.p, c->al_i1.p, G.ctr.p); HAO_CHECK_LAUNCH();
+		hipLaunchKernelGGL(hao_ld_task_kernel<ADV>, gm, b_, 0, c->stream, A, j, (const int32_t*)G.att.p, open, m, c->al_task.p, G.coord.p, c->al_k1.p, c->al_i1.p, G.pth.p, G.ctr.p); HAO_CHECK_LAUNCH();
 		if (int rc = hao_al_sort_by_text(c, m)) return rc;
 		if (int rc = hao_peek(c, G.ctr.p + HAO_LD_RND, HAO_LD_RND_N, PK_LD_ROUND)) return rc;
 		HIP_TRY(hipStreamSynchronize(c->stream));
@@ -549,7 +558,7 @@ int hao_al_ladder(hao_ctx *c, const hao_ovlp_t *ol, uint64_t n_ol, const uint64_
 		uint64_t lo[4][6], at = 0, n_task = 0;
 		for (int md = 0; md < 4; ++md) { for (int k = 0; k < 5; ++k) { lo[md][k] = at; at += rnd(HAO_LD_CNT + md * 5 + k); } lo[md][5] = at; }
 		n_task = at;
-		if (n_task > m) { hao_set_err(c, "hao_window_ladder: more tasks than open requests"); return HAO_EUNSUPP; }
+		if (n_task > m) { hao_set_err(c, w_ + ": more tasks than open requests"); return HAO_EUNSUPP; }
 		DevBuf<uint16_t> &rows = G.rows[j];
 		HIP_TRY(rows.reserve(m * (uint64_t)cap + 1)); W.rows[j] = rows.p; W.cap[j] = cap;
 		hao_trace_result_t *dr = c->al_tres.p; uint8_t *want = c->al_want.p;
@@ -564,18 +573,18 @@ int hao_al_ladder(hao_ctx *c, const hao_ovlp_t *ol, uint64_t n_ol, const uint64_
 			for (int md = 0; md < 4; ++md) for (int k = 1; k <= 4; ++k) {
 				const uint64_t n_sel = c->peeked(PK_LD_SEL, md * 4 + (k - 1)), pw = rnd(HAO_LD_PW + md * 4 + (k - 1));
 				if (!n_sel) continue;
-				if (n_sel > lo[md][k + 1] - lo[md][k] || !pw) { hao_set_err(c, "hao_window_ladder: more selected pairs than tasks"); return HAO_EUNSUPP; }
+				if (n_sel > lo[md][k + 1] - lo[md][k] || !pw) { hao_set_err(c, w_ + ": more selected pairs than tasks"); return HAO_EUNSUPP; }
 				const uint32_t *sel = G.sel.p + lo[md][k];
 				if (int rc = hao_by_mode(md, [&](auto M) { return hao_ld_second<decltype(M)::value>(c, R, k, sel, n_sel, pw, dr, rows.p, cap); })) return rc;
 			}
 		}
-		hipLaunchKernelGGL(hao_ld_commit_kernel, gm, b_, 0, c->stream, j, G.att.p, open, m, c->al_task.p, G.coord.p, dr, cap, G.res.p, G.ncig.p, G.rowref.p, next, G.ctr.p); HAO_CHECK_LAUNCH();
+		hipLaunchKernelGGL(hao_ld_commit_kernel<ADV>, gm, b_, 0, c->stream, j, (const int32_t*)G.att.p, open, m, (const hao_ed_task_t*)c->al_task.p, (const hao_ld_coord*)G.coord.p, (const hao_trace_result_t*)dr, cap, res, G.ncig.p, G.rowref.p, next, G.ctr.p); HAO_CHECK_LAUNCH();
 		// the next round's list becomes the open one; its count crosses with the checks of the next round - here, to size that round's launches
 		HIP_TRY(hipMemcpyAsync(G.ctr.p + HAO_LD_OPEN, G.ctr.p + HAO_LD_NEXT, 8, hipMemcpyDeviceToDevice, c->stream)); HIP_TRY(hipMemsetAsync(G.ctr.p + HAO_LD_NEXT, 0, 8, c->stream));
 		if (int rc = hao_peek(c, G.ctr.p, 2, PK_LD_SETUP)) return rc;
 		HIP_TRY(hipStreamSynchronize(c->stream));
 		m = c->peeked(PK_LD_SETUP, 1);
-		if (m > n) { hao_set_err(c, "hao_window_ladder: more open requests than requests"); return HAO_EUNSUPP; }
+		if (m > n) { hao_set_err(c, w_ + ": more open requests than requests"); return HAO_EUNSUPP; }
 	}
 	HIP_TRY(hipMemsetAsync(G.ncig.p + n, 0, 8, c->stream));
 	if (int rc = hao_excl_scan_u64(c, G.ncig.p, G.off.p, n + 1)) return rc;
@@ -583,11 +592,30 @@ int hao_al_ladder(hao_ctx *c, const hao_ovlp_t *ol, uint64_t n_ol, const uint64_
 	if (int rc = hao_peek(c, G.ctr.p + HAO_LD_NEXT, 2, PK_LD_END)) return rc;
 	HIP_TRY(hipStreamSynchronize(c->stream));
 	const uint64_t total = c->peeked(PK_LD_END);
-	if (c->peeked(PK_LD_END, 1)) { hao_set_err(c, "hao_window_ladder: " + std::to_string(c->peeked(PK_LD_END, 1)) + " cigars longer than their row"); return HAO_EUNSUPP; }      // (2 thre + 3 entries bound an alignment within thre)
+	if (c->peeked(PK_LD_END, 1)) { hao_set_err(c, w_ + ": " + std::to_string(c->peeked(PK_LD_END, 1)) + " cigars longer than their row"); return HAO_EUNSUPP; }      // (2 thre + 3 entries bound an alignment within thre)
 	HIP_TRY(G.cig.reserve(total + 1));
 	if (total) { hipLaunchKernelGGL(hao_ld_fill_kernel, dim3((unsigned)((n * 64 + 255) / 256)), b_, 0, c->stream, W, G.ncig.p, G.rowref.p, G.off.p, n, G.cig.p, total); HAO_CHECK_LAUNCH(); }
 	*n_cigar = total;
 	return HAO_OK;
+}
+
+int hao_al_ladder(hao_ctx *c, const hao_ovlp_t *ol, uint64_t n_ol, const uint64_t *fc, const uint64_t *fc_off, uint64_t n, double e_rate, int64_t maxl, int64_t maxe, uint64_t *n_cigar, uint64_t rounds_out[4])
+{
+	HIP_TRY(c->ld.res.reserve(n));
+	return hao_ld_run<false>(c, "hao_window_ladder", c->ld.res.p, ol, n_ol, fc, fc_off, n, e_rate, 0, maxl, maxe, 0, n_cigar, rounds_out);
+}
+int hao_al_ladder_adv(hao_ctx *c, const hao_ovlp_t *ol, uint64_t n_ol, const uint64_t *fc, const uint64_t *fc_off, uint64_t n, double e_rate, int64_t wl, int64_t maxl, int64_t maxe, int64_t force_l, uint64_t *n_cigar, uint64_t rounds_out[5])
+{
+	HIP_TRY(c->ld.res_adv.reserve(n));
+	return hao_ld_run<true>(c, "hao_window_ladder_adv", c->ld.res_adv.p, ol, n_ol, fc, fc_off, n, e_rate, wl, maxl, maxe, force_l, n_cigar, rounds_out);
+}
+
+extern "C" int hao_ladder_adv_thresholds(int64_t ql, int64_t estimate_err, double e_rate, int64_t wl, int64_t maxl, int64_t maxe, int64_t force_l, int32_t thre[5], int32_t *gate)
+{
+	if (!thre || !hao_ld_estimate(ql, e_rate, wl, &estimate_err)) return HAO_EINVAL;
+	const int n = hao_ld_rungs_adv(ql, estimate_err, e_rate, maxl, maxe, force_l, thre);
+	if (gate) *gate = n > 0;      // (an open gate always makes the first attempt)
+	return n;
 }
 
 extern "C" int hao_ladder_thresholds(int64_t ql, int64_t estimate_err, double e_rate, int64_t maxl, int64_t maxe, int32_t thre[4])

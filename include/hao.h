@@ -511,7 +511,7 @@ int hao_window_trace_long(hao_ctx *c, int mode, const hao_ed_task_t *tasks, uint
  * the batch calls.  HAO_EINVAL: maxe > HAO_ED_LONG_MAX_THRE or negative, maxl negative, e_rate outside [0, 1], and any request with `ol` outside the batch, a mode outside 0 - 3,
  * estimate_err outside [0, 2^30), coordinates outside 0 <= qs <= qe <= q_tot or (modes 0 - 2; mode 3 does not read ts / te) 0 <= ts <= te <= t_tot, or - for a request that passes the maxl / maxe gate - ql or a
  * text length an attempt derives beyond HAO_ED_LONG_MAX_LEN.
- * Not built: adjust_specific_ext_offset (:14424; the caller passes the interval and the mode it wants), hc_aln_exz_adv and its fifth rung, a streamed part. */
+ * Not built: adjust_specific_ext_offset (:14424; the caller passes the interval and the mode it wants), a streamed part.  (hc_aln_exz_adv: hao_window_ladder_adv, below.) */
 typedef struct { uint32_t ol, mode; int32_t qs, qe, ts, te, estimate_err; uint32_t reserved; } hao_ladder_req_t;      /* 32 bytes */
 typedef struct { uint32_t rung; int32_t thre, qs, qe, ts, te, aux_beg; uint32_t flags; int32_t err, a_ps, a_pe, a_ts, a_te, n_cigar; } hao_ladder_res_t;      /* 56 bytes */
 #define HAO_LADDER_REFUSED 1u
@@ -525,6 +525,43 @@ int hao_fetch_ladder(hao_ctx *c, uint16_t *cigars, uint64_t cigar_cap, uint64_t 
 /* TEST SUPPORT, not part of the stable interface (it may change or go with the kernel it mirrors): host code, no context - the rungs of one request as the
  * kernel computes them, thre[4] (-1 where the rung is skipped or the gate is shut); returns the number of attempts */
 int hao_ladder_thresholds(int64_t ql, int64_t estimate_err, double e_rate, int64_t maxl, int64_t maxe, int32_t thre[4]);
+
+/* The threshold ladder of hc_aln_exz_adv (Correct.cpp:16082-16165) on the device: hc_aln_exz's sibling, which the read-overlap path runs (chain_aln and sub_base_aln under
+ * gen_hc_fast_cigar, with MAX_SIN_L / MAX_SIN_E / FORCE_SIN_L for maxl / maxe / force_l).  Same request record, same rounds and sweeps as hao_window_ladder; the rules that differ:
+ *   entry      ts == te == -1 forces mode 3; ql == 0 && te - ts == 0 returns 1 with nothing aligned; ql <= 0 || te - ts <= 0 returns 0 - both on the request's own ts / te, so a
+ *              forced mode 3 and an extension whose far end is unset (te <= ts) never reach the aligner, an explicit mode 3 with ts < te does;
+ *   estimate   estimate_err < 0 stands for (int64)(ql * e_rate) when ql <= wl;
+ *   shortcut   ql <= 16: cal_exact_exz (:15725-15767) - the target interval of the mode (3: hao_ref_shift over the resident fake cigar; 1: te = ts + ql; 2: ts = te - ql), clamped
+ *              into [0, t_tot]; success when it has ql bases equal to the query's (strand y_pos_strand; an N equals an N only, as in the strings the reference compares): err 0, one
+ *              entry (0, ql).  It comes before the gate and does not depend on it;
+ *   gate       ql <= maxl && (estimate_err >> 1) <= maxe;
+ *   rungs      the four recipes of hc_aln_exz WITHOUT the cap at ql, rungs 2 - 4 skipped unless larger than the threshold computed before, and a fifth, thre = maxe, when
+ *              ql <= force_l;
+ *   attempt    cal_exz_infi_adv (:15617-15672): the coordinate step runs with min(thre, dd), dd = max(ql, te - ts) of the request; after the test the threshold becomes
+ *              min(thre, max of the NEW lengths); the attempt is abandoned (HAO_LADDER_REPEAT) unless that exceeds the threshold of the request's last attempt that got this
+ *              far; else the traced alignment runs in the band of that threshold;
+ *   result     absolute coordinates: a_ps, a_pe += ts and a_ts, a_te += qs of the attempt.
+ * Result: done = the function's return value; rung 0 none, 1 - 5 the attempt that aligned, HAO_LADDER_RUNG_EXACT the shortcut; thre = the clamped threshold the aligner was given
+ * (0 for rung 0 and the shortcut); qs .. aux_beg = what the aligner (or the shortcut's comparison) was given, the request's own for rung 0 (ts = te = -1 in forced mode 3); flags
+ * over all attempts; err .. n_cigar as in hao_window_ladder (rung 0: INT32_MAX, -1, no cigar), a_* absolute.  A HAO_LADDER_UNTRACED attempt counts as failed where the
+ * reference would have aligned (or exited), and one whose band does not cover the pattern has still set the last threshold tried: a request that carries that flag can therefore
+ * show HAO_LADDER_REPEAT and end on a later rung or on rung 0 where the reference would not - its result is the project's, not the reference's.  Cigars, capacity, residency, blocking, the shared task scratch,
+ * attached contexts and sharded engines: as for hao_window_ladder.  On the device: the set-up kernel, an exact-match kernel over the requests with ql <= 16 (those it settles
+ * never enter the rounds), then at most five rounds of hao_window_ladder's machinery under this rule set.
+ * HAO_EINVAL: maxe > HAO_ED_LONG_MAX_THRE or negative, maxl, wl or force_l negative, e_rate outside [0, 1], and any request with `ol` outside the batch, a mode outside 0 - 3,
+ * estimate_err >= 2^30, qs / qe outside 0 <= qs <= qe <= q_tot, or - past the two early returns - ts / te outside 0 <= ts < te <= t_tot (every mode: mode 3 reads te - ts),
+ * estimate_err < 0 with ql > wl, or - past the gate - ql or a length an attempt can derive beyond HAO_ED_LONG_MAX_LEN.
+ * Not built: cal_estimate_err over z->w_list (:15369; estimate_err < 0 with ql > wl is HAO_EINVAL), adjust_specific_ext_offset, a streamed part. */
+typedef struct { int32_t done; uint32_t rung; int32_t thre, qs, qe, ts, te, aux_beg; uint32_t flags; int32_t err, a_ps, a_pe, a_ts, a_te, n_cigar; } hao_ladder_adv_res_t;      /* 60 bytes */
+#define HAO_LADDER_REPEAT 4u          /* an attempt was abandoned because its clamped threshold did not exceed the last one tried (the pthre test) */
+#define HAO_LADDER_RUNG_EXACT 6u
+int hao_window_ladder_adv(hao_ctx *c, const hao_ladder_req_t *req, uint64_t n_req, double e_rate, int64_t wl, int64_t maxl, int64_t maxe, int64_t force_l,
+                          hao_ladder_adv_res_t *out, uint64_t *cig_off, uint16_t *cigars, uint64_t cigar_cap, uint64_t *n_cigar);
+/* hao_fetch_ladder for the last hao_window_ladder_adv call (each fetch serves its own call only: HAO_EINVAL after the other one); rounds[j]: the open requests of round j of five */
+int hao_fetch_ladder_adv(hao_ctx *c, uint16_t *cigars, uint64_t cigar_cap, uint64_t *n_cigar, uint64_t rounds[5]);
+/* TEST SUPPORT, like hao_ladder_thresholds: the five raw rungs of hc_aln_exz_adv for one request (-1: skipped, or the gate is shut); estimate_err < 0 is replaced as above
+ * (with ql > wl: HAO_EINVAL, a negative return).  *gate (may be NULL) = the gate is open; returns the number of attempts */
+int hao_ladder_adv_thresholds(int64_t ql, int64_t estimate_err, double e_rate, int64_t wl, int64_t maxl, int64_t maxe, int64_t force_l, int32_t thre[5], int32_t *gate);
 
 /* f3 with traceback on the device grid: the semi-global traced alignment (HAO_ALIGN_SEMI: ed_band_cal_semi_64_w_absent_diag_trace + gen_trace, the call
  * Correct.cpp:3897-3911 makes right after the distance-only one) of the grid pairs hao_window_ed_grid(window, thre) forms, in the same text order.  A pair is
