@@ -92,6 +92,7 @@ ABI_SYMBOLS = [
     "hao_dist_gather_reads", "hao_reads_digest", "hao_index_load_dist", "hao_shard_layout",
     "hao_window_ladder", "hao_fetch_ladder", "hao_ladder_thresholds",
     "hao_window_ladder_adv", "hao_fetch_ladder_adv", "hao_ladder_adv_thresholds",
+    "hao_window_estimate_err", "hao_fetch_ladder_adv_estimates", "hao_estimate_err_records",
 ]
 
 
@@ -237,6 +238,11 @@ def lib():
         L.hao_window_ladder_adv.argtypes = [vp, vp, C.c_uint64, C.c_double, C.c_int64, C.c_int64, C.c_int64, C.c_int64, vp, vp, vp, C.c_uint64, u64p]
         L.hao_fetch_ladder_adv.argtypes = [vp, vp, C.c_uint64, u64p, u64p]
         L.hao_ladder_adv_thresholds.argtypes = [C.c_int64, C.c_int64, C.c_double, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+        L.hao_window_estimate_err.argtypes = [vp, vp, C.c_uint64, C.c_double, C.c_int64, vp]
+        L.hao_fetch_ladder_adv_estimates.argtypes = [vp, vp, C.c_uint64]
+        L.hao_fetch_ladder_adv_estimates.restype = C.c_uint64
+        L.hao_estimate_err_records.argtypes = [vp, vp, C.c_uint64, C.c_int64, C.c_int64, C.c_int64, C.c_double]
+        L.hao_estimate_err_records.restype = C.c_int64
         L.hao_index_save.argtypes = [vp, C.c_char_p, C.c_int32, vp]
         L.hao_index_load.argtypes = [vp, C.c_char_p, C.POINTER(C.c_int32)]
         L.hao_index_load_dist.argtypes = [vp, C.c_char_p, u64p, C.POINTER(C.c_int32)]
@@ -696,18 +702,41 @@ class Engine:
 
     def window_ladder_adv(self, req, e_rate, wl, maxl, maxe, force_l, cap=None):
         """hao_window_ladder_adv (hc_aln_exz_adv's ladder: early returns, exact shortcut, five rungs, absolute coordinates) over the current batch; requests, cap and
-        the returned triple as for window_ladder, the records being LADDER_ADV_RES; estimate_err = -1 asks for ql * e_rate (ql <= wl)"""
+        the returned triple as for window_ladder, the records being LADDER_ADV_RES; estimate_err = -1 asks for ql * e_rate (ql <= wl) or, on a longer stretch, for
+        cal_estimate_err over the window lists the blocking chain (window_ed_ref, window_rescue_ref, window_wlist_ref) left on the device for the batch, built on this wl"""
         return self._ladder(req, cap, LADDER_ADV_RES, "hao_window_ladder_adv", self.L.hao_fetch_ladder_adv,
                             lambda *a: self.L.hao_window_ladder_adv(self.h, a[0], a[1], C.c_double(e_rate), C.c_int64(wl), C.c_int64(maxl), C.c_int64(maxe), C.c_int64(force_l), *a[2:]))
 
-    def _ladder(self, req, cap, res_dtype, who, fetch, call):
+    @staticmethod
+    def _ladder_req(req):
         q = np.asarray(req)
         if q.dtype != LADDER_REQ:
             rows = np.asarray(req, dtype=np.int64).reshape(-1, 7)
             q = np.zeros(rows.shape[0], dtype=LADDER_REQ)
             for k, f in enumerate(("ol", "mode", "qs", "qe", "ts", "te", "estimate_err")):
                 q[f] = rows[:, k]
-        q = np.ascontiguousarray(q); n = q.shape[0]
+        return np.ascontiguousarray(q)
+
+    def window_estimate_err(self, rows, e_rate, wl):
+        """hao_window_estimate_err: cal_estimate_err over the window lists the blocking chain left on the device for the current batch, built on window length wl;
+        rows = requests as for window_ladder_adv (ol, qs and qe are read) -> int64 [n], the function's value per request, a negative one included"""
+        q = self._ladder_req(rows); n = q.shape[0]
+        est = np.zeros(max(1, n), dtype=np.int64)
+        self._ck(self.L.hao_window_estimate_err(self.h, q.ctypes.data_as(C.c_void_p), n, C.c_double(e_rate), C.c_int64(wl), est.ctypes.data_as(C.c_void_p)), "hao_window_estimate_err")
+        return est[:n]
+
+    def ladder_adv_estimates(self):
+        """int64 [n]: the estimate each request of the last window_ladder_adv call ran with - its own where >= 0, ql * e_rate or the window lists' value where it
+        was negative, -1 behind an early return (hao_fetch_ladder_adv_estimates)"""
+        n = int(self.L.hao_fetch_ladder_adv_estimates(self.h, None, 0))
+        if n >= 1 << 63:
+            self._ck(n - (1 << 64), "hao_fetch_ladder_adv_estimates")
+        est = np.zeros(max(1, n), dtype=np.int64)
+        self.L.hao_fetch_ladder_adv_estimates(self.h, est.ctypes.data_as(C.c_void_p), n)
+        return est[:n]
+
+    def _ladder(self, req, cap, res_dtype, who, fetch, call):
+        q = self._ladder_req(req); n = q.shape[0]
         res = np.zeros(n, dtype=res_dtype); off = np.zeros(n + 1, dtype=np.uint64); need = C.c_uint64()
         cig = np.zeros(max(1, cap or 0), dtype=np.uint16)
         self._ck(call(q.ctypes.data_as(C.c_void_p), n, res.ctypes.data_as(C.c_void_p), off.ctypes.data_as(C.c_void_p), cig.ctypes.data_as(C.c_void_p), cap or 0, C.byref(need)), who)
@@ -891,6 +920,20 @@ def ladder_adv_thresholds(ql, estimate_err, e_rate, wl, maxl, maxe, force_l):
     t = (C.c_int32 * 5)(); g = C.c_int32(0)
     n = lib().hao_ladder_adv_thresholds(ql, estimate_err, C.c_double(e_rate), wl, maxl, maxe, force_l, t, C.byref(g))
     return [int(x) for x in t], bool(g.value), n
+
+
+def estimate_err_records(z, wins, wl, qs, qe, e_rate):
+    """hao_estimate_err_records (host code): cal_estimate_err as the device computes it over one overlap z (a row of h_ec_lchain's overlap array) and its window
+    records in ascending window order - fetch_wlist's int64 rows (grid window, y_start, y_end, err, ...) or raw hao_wlist_win_t words (uint32 [m, 4])"""
+    w = np.asarray(wins)
+    if w.dtype != np.uint32:
+        w = np.asarray(wins, dtype=np.int64).reshape(-1, w.shape[1] if w.ndim == 2 and w.shape[0] else 8)
+        raw = np.zeros((w.shape[0], 4), dtype=np.uint32)
+        raw[:, 0] = w[:, 1].astype(np.uint32); raw[:, 1] = w[:, 2].astype(np.uint32); raw[:, 2] = w[:, 0]; raw[:, 3] = w[:, 3] & 0xff
+        w = raw
+    w = np.ascontiguousarray(w.reshape(-1, 4)); zz = np.ascontiguousarray(np.asarray(z, dtype=np.int64).astype(np.uint32))
+    assert zz.shape == (12,)
+    return int(lib().hao_estimate_err_records(zz.ctypes.data_as(C.c_void_p), w.ctypes.data_as(C.c_void_p), w.shape[0], int(wl), int(qs), int(qe), C.c_double(e_rate)))
 
 
 def ref_thresholds(window, e_rate):

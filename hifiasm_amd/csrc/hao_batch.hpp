@@ -239,6 +239,7 @@ int hao_al_rescue(hao_ctx *c, const hao_ref_io &io);      // (hao_f3.hip)
 int hao_al_wlist(hao_ctx *c, const hao_ref_io &io);
 int hao_al_ladder(hao_ctx *c, const hao_ovlp_t *ol, uint64_t n_ol, const uint64_t *fc, const uint64_t *fc_off, uint64_t n, double e_rate, int64_t maxl, int64_t maxe, uint64_t *n_cigar, uint64_t rounds_out[4]);      // (the threshold ladder, hao_ladder.cuh)
 int hao_al_ladder_adv(hao_ctx *c, const hao_ovlp_t *ol, uint64_t n_ol, const uint64_t *fc, const uint64_t *fc_off, uint64_t n, double e_rate, int64_t wl, int64_t maxl, int64_t maxe, int64_t force_l, uint64_t *n_cigar, uint64_t rounds_out[5]);      // (the same under hc_aln_exz_adv's rules)
+int hao_al_estimate(hao_ctx *c, const hao_ovlp_t *ol, uint64_t n_ol, uint64_t n, double e_rate, int64_t wl, uint64_t *n_bad);      // (cal_estimate_err over the resident window lists, hao_ladder.cuh)
 // the batch as the blocking chain has it: hao_ed_ref_run's table, pair list and results per pair (c->al_res); results into the context's own buffers
 static hao_ref_io hao_ref_io_ctx(hao_ctx *c)
 {

@@ -561,12 +561,12 @@ static int hao_ladder_run(hao_ctx *c, bool adv, const hao_ladder_req_t *req, uin
 {
 	const std::string who = adv ? "hao_window_ladder_adv" : "hao_window_ladder";
 	hao_ctx::Batch &B = *c->batch; hao_ctx::Batch::OutSet &O = B.O(); hao_ctx::Ladder &G = c->ld;
-	*n_cigar = 0; c->ld_valid = false; c->ld_adv = adv; c->ld_ncig = 0; for (int j = 0; j < 5; ++j) c->ld_rounds[j] = 0;
+	*n_cigar = 0; c->ld_valid = false; c->ld_adv = adv; c->ld_ncig = 0; c->ld_n = 0; for (int j = 0; j < 5; ++j) c->ld_rounds[j] = 0;
 	if (adv) { HAO_STAGE_VIEW(c, V, "hao_window_ladder_adv needs the bases of both reads"); (void)V; }
 	else { HAO_STAGE_VIEW(c, V, "hao_window_ladder needs the bases of both reads"); (void)V; }
 	if (!(e_rate >= 0 && e_rate <= 1) || maxl < 0 || maxe < 0 || maxe > HAO_ED_LONG_MAX_THRE || wl < 0 || force_l < 0) { hao_set_err(c, who + ": e_rate outside [0, 1], maxl" + (adv ? ", wl or force_l" : "") + " negative, or maxe negative or beyond HAO_ED_LONG_MAX_THRE"); return HAO_EINVAL; }
 	if (n >= (1ULL << 32)) { hao_set_err(c, who + ": more than 2^32 requests in one call"); return HAO_EUNSUPP; }
-	c->win.on_host_fed();      // (the task / result scratch is shared with the other window-alignment calls)
+	c->win.on_host_fed();      // (the task / result scratch is shared with the other window-alignment calls; the batch's window records stay: hao_ld_run reads them)
 	if (n == 0) { cig_off[0] = 0; c->ld_valid = true; return HAO_OK; }
 	HIP_TRY(G.req.reserve(n));
 	HIP_TRY(hipMemcpyAsync(G.req.p, req, n * sizeof(hao_ladder_req_t), hipMemcpyHostToDevice, c->stream));
@@ -579,7 +579,7 @@ static int hao_ladder_run(hao_ctx *c, bool adv, const hao_ladder_req_t *req, uin
 	HIP_TRY(hipStreamSynchronize(c->stream));
 	hao_release_above(c->al_path, HAO_SCRATCH_KEEP);      // (the buffers that grow with the requests alone - requests, results, lists, offsets - keep their largest size, like every per-item buffer of the context)
 	for (int j = 0; j < 5; ++j) hao_release_above(G.rows[j], HAO_SCRATCH_KEEP);
-	c->ld_ncig = *n_cigar; c->ld_valid = true;
+	c->ld_ncig = *n_cigar; c->ld_n = n; c->ld_valid = true;
 	return HAO_OK;
 }
 
@@ -596,6 +596,42 @@ static int hao_fetch_ladder_of(hao_ctx *c, bool adv, uint16_t *cigars, uint64_t 
 }
 int hao_fetch_ladder(hao_ctx *c, uint16_t *cigars, uint64_t cigar_cap, uint64_t *n_cigar, uint64_t rounds[4]) { return hao_fetch_ladder_of(c, false, cigars, cigar_cap, n_cigar, rounds, 4); }
 int hao_fetch_ladder_adv(hao_ctx *c, uint16_t *cigars, uint64_t cigar_cap, uint64_t *n_cigar, uint64_t rounds[5]) { return hao_fetch_ladder_of(c, true, cigars, cigar_cap, n_cigar, rounds, 5); }
+
+uint64_t hao_fetch_ladder_adv_estimates(hao_ctx *c, int64_t *est, uint64_t cap)
+{
+	if (!c) return (uint64_t)(int64_t)HAO_EINVAL;
+	if (!c->ld_valid || !c->ld_adv) { hao_set_err(c, "hao_fetch_ladder_adv_estimates: no results of hao_window_ladder_adv are resident"); return (uint64_t)(int64_t)HAO_EINVAL; }
+	const uint64_t m = std::min<uint64_t>(cap, c->ld_n);
+	if (est && m) {
+		if (hipSetDevice(c->device) != hipSuccess || hipMemcpy(est, c->ld.est.p, m * 8, hipMemcpyDeviceToHost) != hipSuccess) { hao_set_err(c, "hao_fetch_ladder_adv_estimates: the copy failed"); return (uint64_t)(int64_t)HAO_ENODEV; }
+	}
+	return c->ld_n;
+}
+
+// hao_window_estimate_err: cal_estimate_err over the batch's resident window lists, one value per request; its own buffers, no transition of c->win
+static int hao_estimate_run(hao_ctx *c, const hao_ladder_req_t *req, uint64_t n, double e_rate, int64_t wl, int64_t *est)
+{
+	hao_ctx::Batch &B = *c->batch;
+	if (!c->win.wlist_records_resident()) { hao_set_err(c, "hao_window_estimate_err: no window lists of hao_window_wlist_ref are on the device for this batch (the blocking chain has not completed on it, or a grid call has run since)"); return HAO_EINVAL; }
+	if (wl <= 0 || wl != (int64_t)c->rf_tab_wl) { hao_set_err(c, "hao_window_estimate_err: wl is not the window length the lists were built on"); return HAO_EINVAL; }
+	if (!(e_rate >= 0 && e_rate <= 1)) { hao_set_err(c, "hao_window_estimate_err: e_rate outside [0, 1]"); return HAO_EINVAL; }
+	{ HAO_STAGE_VIEW(c, V, "hao_window_estimate_err needs the read lengths as the window stages see them"); (void)V; }      // (the gathered store has gone since hao_window_wlist_ref)
+	if (n >= (1ULL << 32)) { hao_set_err(c, "hao_window_estimate_err: more than 2^32 requests in one call"); return HAO_EUNSUPP; }
+	if (n == 0) return HAO_OK;
+	hao_ctx::Ladder &G = c->ld;
+	HIP_TRY(G.e_req.reserve(n));
+	HIP_TRY(hipMemcpyAsync(G.e_req.p, req, n * sizeof(hao_ladder_req_t), hipMemcpyHostToDevice, c->stream));
+	uint64_t bad = 0;
+	if (int rc = hao_al_estimate(c, B.O().ol_out.p, B.n_ol, n, e_rate, wl, &bad)) return rc;
+	if (bad) { hao_set_err(c, "hao_window_estimate_err: " + std::to_string(bad) + " requests out of range (overlap index, or qs / qe outside 0 <= qs <= qe <= q_tot)"); return HAO_EINVAL; }
+	HIP_TRY(hipMemcpyAsync(est, G.e_est.p, n * 8, hipMemcpyDeviceToHost, c->stream));
+	return HAO_OK;
+}
+int hao_window_estimate_err(hao_ctx *c, const hao_ladder_req_t *req, uint64_t n_req, double e_rate, int64_t wl, int64_t *est)
+{
+	if (!c || (n_req && (!req || !est))) return HAO_EINVAL;
+	return hao_window_stage(c, nullptr, [&] { return hao_estimate_run(c, req, n_req, e_rate, wl, est); });
+}
 
 int hao_window_ladder(hao_ctx *c, const hao_ladder_req_t *req, uint64_t n_req, double e_rate, int64_t maxl, int64_t maxe, hao_ladder_res_t *out, uint64_t *cig_off, uint16_t *cigars, uint64_t cigar_cap, uint64_t *n_cigar)
 {

@@ -171,13 +171,16 @@ static_assert(hao_peek_table_ok(), "read-back slots: a range beyond the mapped w
 //              it completes.  Summaries and rescue results lie in buffers of their own; the rescue stage READS the scratch, and the lists ask for its owner too
 //   host       bit s: stage s's fetch call holds host copies of the current results (cleared where the device side is)
 //   trace      hao_window_trace_grid's results are resident (buffers of their own)
+//   lists      the batch's window records are on the device (wl.woff / wl.wins, buffers of their own that no host-fed call writes: DESIGN.md 4): set when the chain
+//              completes, dropped with the batch, by a chain stage that starts (again) and by the grid call - NOT by a host-fed call, so the threshold ladder and
+//              hao_window_estimate_err find them call after call (hao_fetch_wlist keeps asking for the scratch's owner as well, as before)
 struct WinResident {
 	enum Stage { NONE, ED, RESCUE, WLIST };
 	void on_new_batch() { *this = WinResident(); }
 	void on_host_fed() { owner = NOBODY; n = 0; trace = false; }
-	void on_grid(uint64_t pairs) { owner = GRID; n = pairs; }
-	void on_ref_begin(Stage s) { if (chain >= s) chain = (Stage)(s - 1); host &= (1u << s) - 1; if (s == ED) { owner = NOBODY; n = 0; } }
-	void on_ref_done(Stage s, uint64_t pairs = 0) { chain = s; if (s == ED) { owner = REF; n = pairs; } }
+	void on_grid(uint64_t pairs) { owner = GRID; n = pairs; lists = false; }
+	void on_ref_begin(Stage s) { if (chain >= s) chain = (Stage)(s - 1); host &= (1u << s) - 1; if (s == ED) { owner = NOBODY; n = 0; } lists = false; }
+	void on_ref_done(Stage s, uint64_t pairs = 0) { chain = s; if (s == ED) { owner = REF; n = pairs; } if (s == WLIST) lists = true; }
 	void on_host_copy(Stage s) { host |= 1u << s; }
 	void on_trace_grid(bool done) { trace = done; }
 	uint64_t scratch_pairs() const { return owner == NOBODY ? 0 : n; }      // what hao_fetch_ed_grid serves (either grid call's)
@@ -185,9 +188,10 @@ struct WinResident {
 	bool ref_input_resident() const { return chain >= ED && owner == REF; }      // + hao_window_ed_ref's results per pair in al_res: the rescue stage's input
 	bool wlist_input_resident() const { return chain >= RESCUE && owner == REF; }
 	bool wlist_resident() const { return chain >= WLIST && owner == REF; }
+	bool wlist_records_resident() const { return lists; }      // the records alone: what cal_estimate_err reads (hao_ladder.cuh: hao_ld_estimate_wlist)
 	bool host_current(Stage s) const { return (host >> s) & 1u; }
 private:
-	enum Owner { NOBODY, GRID, REF } owner = NOBODY; uint64_t n = 0; Stage chain = NONE; uint32_t host = 0; bool trace = false;
+	enum Owner { NOBODY, GRID, REF } owner = NOBODY; uint64_t n = 0; Stage chain = NONE; uint32_t host = 0; bool trace = false, lists = false;
 };
 
 // A reference-placed batch whose ED stage has run, as hao_al_rescue and hao_al_wlist (hao_f3.hip) take it: filled from the context's own buffers by the blocking calls, from the
@@ -283,7 +287,11 @@ struct hao_ctx {
 		DevBuf<uint16_t> rows[5], cig; DevBuf<unsigned long long> ctr;
 		// hao_window_ladder_adv only: its results, the exact shortcut's list and one-entry cigars, the threshold of each request's last attempt (pthre)
 		DevBuf<hao_ladder_adv_res_t> res_adv; DevBuf<uint32_t> xlist; DevBuf<uint16_t> xrow; DevBuf<int32_t> pth;
+		DevBuf<int64_t> est;      // the estimate each request of the last hao_window_ladder_adv call ran with (hao_fetch_ladder_adv_estimates)
+		// hao_window_estimate_err's own requests, values and counter: the stage touches nothing the ladder calls left resident
+		DevBuf<hao_ladder_req_t> e_req; DevBuf<int64_t> e_est; DevBuf<unsigned long long> e_ctr;
 	} ld;
+	uint64_t ld_n = 0;      // the requests of the last ladder call
 	bool ld_valid = false, ld_adv = false; uint64_t ld_ncig = 0, ld_rounds[5] = { 0, 0, 0, 0, 0 };      // hao_fetch_ladder[_adv]: the last call's entries are resident in ld.cig (ld_adv: it was hao_window_ladder_adv); their number; the open requests of each round
 	// f3 with traceback on the grid (hao_trace_grid.cuh): the stage's scratch, compute stream only (hao_window_trace_grid and HAO_DELIVER_TRACE share it) -
 	// flags and selected pairs, entry counts and their scans, the compact array's offsets, the column scratch, the rows of one slice, two counters

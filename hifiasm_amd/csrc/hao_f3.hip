@@ -520,7 +520,7 @@ template<int MODE> static int hao_ld_second(hao_ctx *c, const hao_ed_reads &R, i
 // and the exact shortcut's kernel between the set-up and the first read-back, so that it costs no round trip of its own.
 template<bool ADV> static int hao_ld_run(hao_ctx *c, const char *who, typename hao_ld_rule<ADV>::res_t *res, const hao_ovlp_t *ol, uint64_t n_ol, const uint64_t *fc, const uint64_t *fc_off, uint64_t n,
 		double e_rate, int64_t wl, int64_t maxl, int64_t maxe, int64_t force_l, uint64_t *n_cigar, uint64_t *rounds_out)
-{
+{      // (ADV with c->win.wlist_records_resident(): the batch's window lists serve estimate_err < 0 on a stretch longer than wl, when wl is the window length they were built on)
 	constexpr int NA = hao_ld_rule<ADV>::N_ATT;      // attempts per request = the most rounds
 	const std::string w_ = who;
 	hao_ctx::Ladder &G = c->ld; *n_cigar = 0;
@@ -531,13 +531,15 @@ template<bool ADV> static int hao_ld_run(hao_ctx *c, const char *who, typename h
 	HIP_TRY(c->al_task.reserve(n)); HIP_TRY(c->al_k1.reserve(n)); HIP_TRY(c->al_k2.reserve(n)); HIP_TRY(c->al_i1.reserve(n)); HIP_TRY(c->al_order.reserve(n)); HIP_TRY(c->al_tres.reserve(n)); HIP_TRY(c->al_want.reserve(n));
 	HIP_TRY(hipMemsetAsync(G.ctr.p, 0, 64 * 8, c->stream));
 	hao_ld_args A; A.req = G.req.p; A.n_req = n; A.ol = ol; A.n_ol = n_ol; A.fc = fc; A.fc_off = fc_off; A.len = V.len; A.n_reads = V.n; A.e_rate = e_rate; A.maxl = maxl; A.maxe = maxe; A.coop_all = c->sw.al_coop ? 1 : 0; A.wl = wl; A.force_l = force_l;
+	const bool lists = ADV && c->win.wlist_records_resident() && c->rf_tab_wl && (int64_t)c->rf_tab_wl == wl;
+	A.wl_off = lists ? c->wl.woff.p : nullptr; A.wl_wins = lists ? c->wl.wins.p : nullptr; A.wl_len = lists ? (int64_t)c->rf_tab_wl : 0;
 	const dim3 b_(256), gn((unsigned)((n + 255) / 256));
-	if (ADV) { HIP_TRY(G.xlist.reserve(n)); HIP_TRY(G.xrow.reserve(n)); HIP_TRY(G.pth.reserve(n)); }
-	hipLaunchKernelGGL(hao_ld_thre_kernel<ADV>, gn, b_, 0, c->stream, A, G.att.p, res, G.ncig.p, G.open[0].p, G.xlist.p, G.pth.p, G.ctr.p); HAO_CHECK_LAUNCH();
+	if (ADV) { HIP_TRY(G.xlist.reserve(n)); HIP_TRY(G.xrow.reserve(n)); HIP_TRY(G.pth.reserve(n)); HIP_TRY(G.est.reserve(n)); }
+	hipLaunchKernelGGL(hao_ld_thre_kernel<ADV>, gn, b_, 0, c->stream, A, G.att.p, res, G.ncig.p, G.open[0].p, G.xlist.p, G.pth.p, G.est.p, G.ctr.p); HAO_CHECK_LAUNCH();
 	if constexpr (ADV) { hipLaunchKernelGGL(hao_ld_exact_kernel, gn, b_, 0, c->stream, A, R, (const uint32_t*)G.xlist.p, n, (const int32_t*)G.att.p, res, G.ncig.p, G.rowref.p, G.xrow.p, G.open[0].p, G.ctr.p); HAO_CHECK_LAUNCH(); }
 	if (int rc = hao_peek(c, G.ctr.p, 2, PK_LD_SETUP)) return rc;
 	HIP_TRY(hipStreamSynchronize(c->stream));
-	if (c->peeked(PK_LD_SETUP)) { hao_set_err(c, w_ + ": " + std::to_string(c->peeked(PK_LD_SETUP)) + " requests out of range (overlap index, mode, estimate_err, coordinates, or a length beyond HAO_ED_LONG_MAX_LEN)"); return HAO_EINVAL; }
+	if (c->peeked(PK_LD_SETUP)) { hao_set_err(c, w_ + ": " + std::to_string(c->peeked(PK_LD_SETUP)) + " requests out of range (overlap index, mode, estimate_err - negative on a stretch longer than wl without window lists of that window length on the batch, or a negative value from them -, coordinates, or a length beyond HAO_ED_LONG_MAX_LEN)"); return HAO_EINVAL; }
 	uint64_t m = c->peeked(PK_LD_SETUP, 1);
 	if (m > n) { hao_set_err(c, w_ + ": more open requests than requests"); return HAO_EUNSUPP; }
 	hao_ld_rows W; for (int j = 0; j <= HAO_LD_ROUNDS; ++j) { W.rows[j] = nullptr; W.cap[j] = 0; }
@@ -608,6 +610,29 @@ int hao_al_ladder_adv(hao_ctx *c, const hao_ovlp_t *ol, uint64_t n_ol, const uin
 {
 	HIP_TRY(c->ld.res_adv.reserve(n));
 	return hao_ld_run<true>(c, "hao_window_ladder_adv", c->ld.res_adv.p, ol, n_ol, fc, fc_off, n, e_rate, wl, maxl, maxe, force_l, n_cigar, rounds_out);
+}
+
+// hao_window_estimate_err (hao_capi_rest.hpp): n requests (already in c->ld.e_req) over the overlaps ol[n_ol] and the batch's resident window lists -> c->ld.e_est; *n_bad = the
+// requests outside the batch or their query read.  One kernel, a thread per request; nothing of the shared scratch
+int hao_al_estimate(hao_ctx *c, const hao_ovlp_t *ol, uint64_t n_ol, uint64_t n, double e_rate, int64_t wl, uint64_t *n_bad)
+{
+	hao_ctx::Ladder &G = c->ld;
+	hao_read_view V; (void)hao_reads_view(c, &V);
+	HIP_TRY(G.e_est.reserve(n)); HIP_TRY(G.e_ctr.reserve(1));
+	HIP_TRY(hipMemsetAsync(G.e_ctr.p, 0, 8, c->stream));
+	hipLaunchKernelGGL(hao_ld_estimate_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, (const hao_ladder_req_t*)G.e_req.p, n, ol, n_ol, V.len, V.n,
+		(const uint64_t*)c->wl.woff.p, (const hao_rs_win*)c->wl.wins.p, wl, e_rate, G.e_est.p, G.e_ctr.p); HAO_CHECK_LAUNCH();
+	unsigned long long bad = 0;
+	HIP_TRY(hipMemcpyAsync(&bad, G.e_ctr.p, 8, hipMemcpyDeviceToHost, c->stream));
+	HIP_TRY(hipStreamSynchronize(c->stream));
+	*n_bad = bad;
+	return HAO_OK;
+}
+
+extern "C" int64_t hao_estimate_err_records(const hao_ovlp_t *z, const hao_wlist_win_t *wins, uint64_t n, int64_t wl, int64_t qs, int64_t qe, double e_rate)
+{
+	static_assert(sizeof(hao_wlist_win_t) == sizeof(hao_rs_win), "hao_wlist_win_t is hao_rs_win");
+	return hao_ld_estimate_wlist(*z, (const hao_rs_win*)wins, n, wl, qs, qe, e_rate);
 }
 
 extern "C" int hao_ladder_adv_thresholds(int64_t ql, int64_t estimate_err, double e_rate, int64_t wl, int64_t maxl, int64_t maxe, int64_t force_l, int32_t thre[5], int32_t *gate)

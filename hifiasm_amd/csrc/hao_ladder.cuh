@@ -14,7 +14,7 @@
 //
 // The same machinery serves hc_aln_exz_adv (Correct.cpp:16082-16165; hao_window_ladder_adv), the sibling the read-overlap path runs: every kernel and the host runner
 // (hao_f3.hip: hao_ld_run) take the rule set as a template parameter ADV, and hao_ld_rule<ADV> names what it changes - the result record and the attempts per request.
-// Under ADV: the entry's early returns, estimate_err < 0, the gate on estimate_err >> 1, five raw rungs without the cap at ql (hao_ld_rungs_adv), cal_exz_infi_adv's
+// Under ADV: the entry's early returns, estimate_err < 0 (ql * e_rate, or cal_estimate_err over the batch's resident window lists: hao_ld_estimate_wlist), the gate on estimate_err >> 1, five raw rungs without the cap at ql (hao_ld_rungs_adv), cal_exz_infi_adv's
 // clamps by dd = max(ql, tl) before and after the coordinate step and its pthre test (per-request state across rounds: pth[]), absolute result coordinates, and between
 // set-up and the rounds hao_ld_exact_kernel, cal_exact_exz (:15725-15767) over the requests with ql <= 16 - those it settles never enter a round.
 #pragma once
@@ -66,13 +66,45 @@ HAO_AL_FN int hao_ld_rungs_adv(int64_t ql, int64_t estimate_err, double e_rate, 
 	if (ql <= force_l) { thre[4] = (int32_t)maxe; ++n; }
 	return n;
 }
-// estimate_err < 0 (:16092-16095): ql * e_rate when ql <= wl; false = the other branch (cal_estimate_err over z->w_list), which is not built
+// estimate_err < 0 (:16092-16095): ql * e_rate when ql <= wl; false = the other branch (cal_estimate_err over z->w_list: hao_ld_estimate_wlist, which needs the overlap's records)
 HAO_AL_FN bool hao_ld_estimate(int64_t ql, double e_rate, int64_t wl, int64_t *estimate_err)
 {
 	if (*estimate_err >= 0) return true;
 	if (ql > wl) return false;
 	*estimate_err = (int64_t)((double)ql * e_rate);
 	return true;
+}
+// cal_estimate_err (Correct.cpp:15369-15401) over the n records of overlap z as hao_window_wlist_ref leaves them (hao_wlist.cuh): aligned windows only, ascending, x_start /
+// x_end + 1 of a record = hao_ref_window of its grid window, error = info & 0xff (untraced records count like any other).  est, from the unclamped request, when the list is
+// empty or ends before the clamped qs (the exit at :15377 - the reference walks forward from get_win_id_by_s's guess, which on an ascending list ends at the first record
+// with x_end >= qs or beyond the last; the walk back at :15379 only adds records that do not reach qs).  Then, in record order: a record covered whole adds its error, a
+// partly covered one error * ovlp / length in double INTO the int64 sum (truncated at every step, as the reference's `tot +=` does), the uncovered rest * e_rate at the end.
+// FP64 in the reference's operation order; the build contracts nothing (-ffp-contract=off)
+HAO_AL_FN int64_t hao_ld_estimate_wlist(const hao_ovlp_t &z, const hao_rs_win *w, uint64_t n, int64_t wl, int64_t qs, int64_t qe, double e_rate)
+{
+	const int64_t est = (int64_t)((double)(qe - qs) * e_rate);
+	if (!n) return est;
+	if (qs < (int64_t)z.x_pos_s) qs = (int64_t)z.x_pos_s;
+	if (qe > (int64_t)z.x_pos_e + 1) qe = (int64_t)z.x_pos_e + 1;
+	uint64_t lo = 0, hi = n;      // first record with x_end >= qs
+	while (lo < hi) {
+		const uint64_t m = (lo + hi) >> 1; int64_t ws, wn; hao_ref_window(z, w[m].win, (uint32_t)wl, &ws, &wn);
+		if (ws + wn - 1 < qs) lo = m + 1; else hi = m;
+	}
+	if (lo == n) return est;
+	int64_t tot = 0, cov_l = 0;
+	for (uint64_t k = lo; k < n; ++k) {
+		int64_t ws, wn; hao_ref_window(z, w[k].win, (uint32_t)wl, &ws, &wn);
+		if (!(ws < qe)) break;
+		const int64_t we = ws + wn, os = qs > ws ? qs : ws, oe = qe < we ? qe : we, ovlp = oe > os ? oe - os : 0;
+		if (!ovlp) continue;
+		cov_l += ovlp;
+		const int64_t error = (int64_t)(w[k].info & 0xffu);
+		if (ovlp == we - ws) tot += error;
+		else tot = (int64_t)((double)tot + ((double)error) * ((double)ovlp) / ((double)(we - ws)));
+	}
+	tot = (int64_t)((double)tot + (double)((qe - qs) - cov_l) * e_rate);
+	return tot;
 }
 // adjust_ext_offset (Correct.cpp:14400-14422)
 HAO_AL_FN void hao_ld_adjust_ext(int64_t *qs, int64_t *qe, int64_t *ts, int64_t *te, int64_t ql, int64_t tl, int64_t thre, int mode)
@@ -95,6 +127,7 @@ struct hao_ld_args {
 	const hao_ovlp_t *ol; uint64_t n_ol; const uint64_t *fc, *fc_off; const uint32_t *len; uint64_t n_reads;
 	double e_rate; int64_t maxl, maxe; int coop_all;      // coop_all: HAO_DBG_FORCE=al_coop
 	int64_t wl, force_l;                                  // hc_aln_exz_adv's two further parameters (ADV only)
+	const uint64_t *wl_off; const hao_rs_win *wl_wins; int64_t wl_len;      // ADV only: the batch's window lists (hao_window_wlist_ref's record offsets per overlap and records) and the window length they were built on; null / 0 when none are resident
 };
 // what a rule set changes in the records: ADV = false hc_aln_exz, true hc_aln_exz_adv
 template<bool ADV> struct hao_ld_rule { typedef hao_ladder_res_t res_t; enum { N_ATT = 4 }; };
@@ -139,16 +172,31 @@ __device__ __forceinline__ bool hao_ld_coords(const hao_ld_args &A, const hao_la
 	return ok;
 }
 
+// hao_window_estimate_err: a thread per request (its ol, qs, qe only) - cal_estimate_err over the overlap's resident records, the value as it is; a request outside the batch
+// or its query read is counted in *bad and reads nothing
+__global__ __launch_bounds__(256) void hao_ld_estimate_kernel(const hao_ladder_req_t *req, uint64_t n, const hao_ovlp_t *ol, uint64_t n_ol, const uint32_t *len, uint64_t n_reads,
+		const uint64_t *woff, const hao_rs_win *wins, int64_t wl, double e_rate, int64_t *est, unsigned long long *bad)
+{
+	const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+	if (i >= n) return;
+	const hao_ladder_req_t q = req[i];
+	est[i] = -1;
+	if (q.ol >= n_ol) { atomicAdd(bad, 1ULL); return; }
+	const hao_ovlp_t z = ol[q.ol];
+	if (z.x_id >= n_reads || q.qs < 0 || q.qe < q.qs || (int64_t)q.qe > (int64_t)len[z.x_id]) { atomicAdd(bad, 1ULL); return; }
+	est[i] = hao_ld_estimate_wlist(z, wins + woff[q.ol], woff[q.ol + 1] - woff[q.ol], wl, q.qs, q.qe, e_rate);
+}
+
 // per request: checks, rungs, the preset result, the first open list.  att[N_ATT i + k] = the threshold of attempt k, rung id in the top byte (attempts are the rungs that
 // are not skipped).  ADV: the early returns, estimate_err < 0, raw rungs, pth[i] = -1; a request with ql <= 16 goes to xlist, not to the open list (hao_ld_exact_kernel)
-template<bool ADV> __global__ __launch_bounds__(256) void hao_ld_thre_kernel(hao_ld_args A, int32_t *att, typename hao_ld_rule<ADV>::res_t *res, uint64_t *ncig, uint32_t *open, uint32_t *xlist, int32_t *pth, unsigned long long *ctr)
+template<bool ADV> __global__ __launch_bounds__(256) void hao_ld_thre_kernel(hao_ld_args A, int32_t *att, typename hao_ld_rule<ADV>::res_t *res, uint64_t *ncig, uint32_t *open, uint32_t *xlist, int32_t *pth, int64_t *est_out, unsigned long long *ctr)
 {
 	constexpr int NA = hao_ld_rule<ADV>::N_ATT;
 	const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
 	if (i >= A.n_req) return;
 	const hao_ladder_req_t q = A.req[i];
 	typename hao_ld_rule<ADV>::res_t r; r.rung = 0; r.thre = 0; r.qs = q.qs; r.qe = q.qe; r.ts = q.ts; r.te = q.te; r.aux_beg = 0; r.flags = 0; r.err = HAO_AL_NONE; r.a_ps = r.a_pe = r.a_ts = r.a_te = -1; r.n_cigar = 0;
-	if constexpr (ADV) { r.done = 0; pth[i] = -1; }
+	if constexpr (ADV) { r.done = 0; pth[i] = -1; est_out[i] = -1; }
 	ncig[i] = 0; for (int k = 0; k < NA; ++k) att[NA * i + k] = -1;
 	bool bad = q.ol >= A.n_ol || q.mode > 3u || (!ADV && q.estimate_err < 0) || q.estimate_err >= (1 << 30), exact = false;
 	int mode = (int)q.mode, n = 0;
@@ -164,8 +212,11 @@ template<bool ADV> __global__ __launch_bounds__(256) void hao_ld_thre_kernel(hao
 				if (ql == 0 && tl == 0) { r.done = 1; live = false; }
 				else if (ql <= 0 || tl <= 0) live = false;
 				if (live && (q.ts < 0 || q.te > t_tot)) bad = true;
-				if (live && !bad && !hao_ld_estimate(ql, A.e_rate, A.wl, &est)) bad = true;
-				if (live && !bad) exact = ql <= 16;
+				if (live && !bad && !hao_ld_estimate(ql, A.e_rate, A.wl, &est)) {      // ql > wl: cal_estimate_err over the overlap's resident records; a negative value (a stretch that ends before the overlap starts) is a refused request
+					if (A.wl_off && A.wl_len == A.wl) est = hao_ld_estimate_wlist(z, A.wl_wins + A.wl_off[q.ol], A.wl_off[q.ol + 1] - A.wl_off[q.ol], A.wl, q.qs, q.qe, A.e_rate);
+					if (est < 0) bad = true;
+				}
+				if (live && !bad) { exact = ql <= 16; est_out[i] = est; }
 			} else {
 				if (mode != 3 && (q.ts < 0 || q.te < q.ts || q.te > t_tot)) bad = true;
 				if (mode == 3) { r.ts = r.te = -1; }

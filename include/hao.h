@@ -530,7 +530,8 @@ int hao_ladder_thresholds(int64_t ql, int64_t estimate_err, double e_rate, int64
  * gen_hc_fast_cigar, with MAX_SIN_L / MAX_SIN_E / FORCE_SIN_L for maxl / maxe / force_l).  Same request record, same rounds and sweeps as hao_window_ladder; the rules that differ:
  *   entry      ts == te == -1 forces mode 3; ql == 0 && te - ts == 0 returns 1 with nothing aligned; ql <= 0 || te - ts <= 0 returns 0 - both on the request's own ts / te, so a
  *              forced mode 3 and an extension whose far end is unset (te <= ts) never reach the aligner, an explicit mode 3 with ts < te does;
- *   estimate   estimate_err < 0 stands for (int64)(ql * e_rate) when ql <= wl;
+ *   estimate   estimate_err < 0 stands for (int64)(ql * e_rate) when ql <= wl, and for cal_estimate_err(z, wl, qs, qe, e_rate) (:15369-15401) over the overlap's window list
+ *              when ql > wl: the records hao_window_wlist_ref left on the device for this batch, when wl is the window length they were built on (see below);
  *   shortcut   ql <= 16: cal_exact_exz (:15725-15767) - the target interval of the mode (3: hao_ref_shift over the resident fake cigar; 1: te = ts + ql; 2: ts = te - ql), clamped
  *              into [0, t_tot]; success when it has ql bases equal to the query's (strand y_pos_strand; an N equals an N only, as in the strings the reference compares): err 0, one
  *              entry (0, ql).  It comes before the gate and does not depend on it;
@@ -550,8 +551,15 @@ int hao_ladder_thresholds(int64_t ql, int64_t estimate_err, double e_rate, int64
  * never enter the rounds), then at most five rounds of hao_window_ladder's machinery under this rule set.
  * HAO_EINVAL: maxe > HAO_ED_LONG_MAX_THRE or negative, maxl, wl or force_l negative, e_rate outside [0, 1], and any request with `ol` outside the batch, a mode outside 0 - 3,
  * estimate_err >= 2^30, qs / qe outside 0 <= qs <= qe <= q_tot, or - past the two early returns - ts / te outside 0 <= ts < te <= t_tot (every mode: mode 3 reads te - ts),
- * estimate_err < 0 with ql > wl, or - past the gate - ql or a length an attempt can derive beyond HAO_ED_LONG_MAX_LEN.
- * Not built: cal_estimate_err over z->w_list (:15369; estimate_err < 0 with ql > wl is HAO_EINVAL), adjust_specific_ext_offset, a streamed part. */
+ * estimate_err < 0 with ql > wl when no window lists of that window length are on the device for the batch or when the lists give a negative value (a stretch that ends before
+ * the overlap starts: the reference would carry the negative number through scale_ed_thre's uint32 cast; nothing is guessed), or - past the gate - ql or a length an attempt can
+ * derive beyond HAO_ED_LONG_MAX_LEN.
+ * The window lists: the blocking chain hao_window_ed_ref -> hao_window_rescue_ref -> hao_window_wlist_ref leaves the batch's records on the device, and they stay there for this
+ * call and hao_window_estimate_err - across any number of ladder calls and other host-fed window-alignment calls, which take the shared task scratch (and with it what
+ * hao_fetch_wlist serves) but not the records - until a new batch, a chain stage that runs again (then until the chain has completed again) or hao_window_ed_grid.  The lists
+ * of a batch delivered with HAO_DELIVER_WLIST live in its output set, not here: such a batch has none (HAO_EINVAL as above), nor has a sharded engine that could not run the
+ * chain.  The estimate is the reference's function on align_hc_ed_post_extz's list; the reference calls it after gen_extend_err_exz has been over the list, which is not built.
+ * Not built: adjust_specific_ext_offset, a streamed part, gen_extend_err_exz. */
 typedef struct { int32_t done; uint32_t rung; int32_t thre, qs, qe, ts, te, aux_beg; uint32_t flags; int32_t err, a_ps, a_pe, a_ts, a_te, n_cigar; } hao_ladder_adv_res_t;      /* 60 bytes */
 #define HAO_LADDER_REPEAT 4u          /* an attempt was abandoned because its clamped threshold did not exceed the last one tried (the pthre test) */
 #define HAO_LADDER_RUNG_EXACT 6u
@@ -562,6 +570,19 @@ int hao_fetch_ladder_adv(hao_ctx *c, uint16_t *cigars, uint64_t cigar_cap, uint6
 /* TEST SUPPORT, like hao_ladder_thresholds: the five raw rungs of hc_aln_exz_adv for one request (-1: skipped, or the gate is shut); estimate_err < 0 is replaced as above
  * (with ql > wl: HAO_EINVAL, a negative return).  *gate (may be NULL) = the gate is open; returns the number of attempts */
 int hao_ladder_adv_thresholds(int64_t ql, int64_t estimate_err, double e_rate, int64_t wl, int64_t maxl, int64_t maxe, int64_t force_l, int32_t thre[5], int32_t *gate);
+/* The estimates the last hao_window_ladder_adv call on this context ran with, one per request: the request's own where it was >= 0, (int64)(ql * e_rate) or the window lists'
+ * value where it was < 0, -1 behind an early return.  Resident like the call's cigars; writes min(cap, requests) entries into est (may be NULL) and returns the call's number of
+ * requests, or (uint64_t)HAO_EINVAL under hao_fetch_ladder_adv's conditions (no such call, one that failed, or hao_window_ladder since). */
+uint64_t hao_fetch_ladder_adv_estimates(hao_ctx *c, int64_t *est, uint64_t cap);
+/* cal_estimate_err (Correct.cpp:15369-15401) as a stage of its own over the window lists the blocking chain left on the device for the current batch (above): est[i] = the
+ * function's value for request i's ol, qs, qe (nothing else of the request is read), as it is - a negative one included.  Blocking; one kernel, a thread per request.  It
+ * takes no shared scratch and changes nothing another window-alignment call left resident: every fetch call serves afterwards what it served before.
+ * HAO_EINVAL: no batch, no lists on the device for it, wl other than the window length they were built on, e_rate outside [0, 1], a request with `ol` outside the batch or
+ * qs / qe outside 0 <= qs <= qe <= q_tot.  n_req == 0: HAO_OK. */
+int hao_window_estimate_err(hao_ctx *c, const hao_ladder_req_t *req, uint64_t n_req, double e_rate, int64_t wl, int64_t *est);
+/* TEST SUPPORT, not part of the stable interface, like hao_ladder_adv_thresholds: host code, no context - the function the two calls above run on the device, over the n records
+ * of one overlap z as hao_fetch_wlist hands them out (ascending windows) */
+int64_t hao_estimate_err_records(const hao_ovlp_t *z, const hao_wlist_win_t *wins, uint64_t n, int64_t wl, int64_t qs, int64_t qe, double e_rate);
 
 /* f3 with traceback on the device grid: the semi-global traced alignment (HAO_ALIGN_SEMI: ed_band_cal_semi_64_w_absent_diag_trace + gen_trace, the call
  * Correct.cpp:3897-3911 makes right after the distance-only one) of the grid pairs hao_window_ed_grid(window, thre) forms, in the same text order.  A pair is
